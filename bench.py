@@ -16,7 +16,9 @@ contexts by ONE process (rank 0 drives all N devices — SURVEY.md §8e, BASELIN
 of a torchrun launch only take part in the barriers and in the device-step measurement below).  `--contexts C` puts C
 contexts on every device (for a one-GPU box: the N-context code path on one device).
 
-Other numbers on the same JSON line (never `value`):
+A plain run does only what `value` needs: it makes the workload, writes the input files, warms up, times `--steps` steps
+(`ms_per_step` = the mean step) and prints the line; `--dump-outputs DIR` also writes what the last step computed (dump_outputs).
+`--full` adds the measurements below, each of them on the same JSON line (never `value`):
   device_step_mreads_s         the same work with the text RESIDENT IN HBM: aqc_reframe -> aqc_run -> aqc_qc_stat ->
                                aqc_format per chunk, no PCIe, no files (each rank on its own GPU; what rounds 1-2 printed as
                                `value`).  `roofline` is for its dominant kernel (fast_filter_overlap_kernel): HIP-event time
@@ -27,7 +29,7 @@ Other numbers on the same JSON line (never `value`):
   file_to_gz                   plain FASTQ in, .gz out (the outputs a third of the size: the file writers are not the bound)
   multi_input_file_to_file     K (--inputs, default 2) independent inputs through K pipes at once on the same GPU: the reference's own
                                parallelism is one seqFilter per input file (after.py:168-171), and K inputs write 4 K files
-`cpu_baseline` (N=1): the oracle (scalar C port of the reference loop) on one core over a bounded sample, checked against the
+`cpu_baseline` (--full, N=1): the oracle (scalar C port of the reference loop) on one core over a bounded sample, checked against the
 GPU's verdicts; plus the same port on every host core and a pure-Python stand-in.
 """
 import argparse
@@ -43,6 +45,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 L = 150
+DUMP_WINDOWS, DUMP_WINDOW_BYTES = 256, 4096   # --dump-outputs: the sample of an output file
+DUMP_LIMIT = 64_000_000                       # --dump-outputs: all arrays together
 
 
 def hbm_traffic(args, n_rec, live):
@@ -61,7 +65,7 @@ def hbm_traffic(args, n_rec, live):
             kb = {}
             for counter in ("FETCH_SIZE", "WRITE_SIZE"):
                 d = os.path.join(tmp, counter)
-                cmd = [rp, "--pmc", counter, "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__), "--device-only",
+                cmd = [rp, "--pmc", counter, "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__), "--full", "--device-only",
                        "--device-steps", "3", "--cpu-sample", "0", "--no-fused-step", "--workload", args.workload, "--pairs", str(int(n_rec))]
                 subprocess.run(cmd, cwd=tmp, env=dict(os.environ, AQC_BENCH_CHILD="1", TMPDIR="/tmp"), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
                                timeout=150, check=True)
@@ -93,6 +97,60 @@ def hbm_traffic(args, n_rec, live):
     return None, None
 
 
+def dump_outputs(dst, res, stats, outs, tag=""):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float64 / float32 .npy files in `dst` — the
+    pipe's result (records, chunks, bytes per output stream, anomaly), the statistics (counters, histograms, post-filter QC rows and
+    k-mers sorted by key) and the good / bad files.  A file (1.7 GB for config 3) is given by its SHA-256 (eight 32-bit words per file in
+    output_sha256) and by DUMP_WINDOWS windows of DUMP_WINDOW_BYTES at offsets drawn from a fixed seed and the file's size, or
+    the whole file when it is no larger (16 MB of float32 for config 3's four files)."""
+    import hashlib
+    import numpy as np
+    from afterqc_amd import capi
+
+    os.makedirs(dst, exist_ok=True)
+    total = [0]
+
+    def put(name, a, dtype=np.float64):
+        a = np.asarray(a).astype(dtype)
+        if a.size == 0:
+            raise RuntimeError("--dump-outputs: %s is empty" % name)
+        total[0] += a.nbytes
+        if total[0] > DUMP_LIMIT:
+            raise RuntimeError("--dump-outputs: more than %d bytes" % DUMP_LIMIT)
+        np.save(os.path.join(dst, name + tag + ".npy"), a)
+
+    put("pipe_result", [res.records, res.chunks] + list(res.bytes_out) + [res.anomaly, res.extra_bases])
+    put("counters", stats["counters"])
+    put("overlap_hist", stats["ovl"])
+    put("distance_hist", stats["dist"])
+    # the pipe samples the QC of the reads it passes (post-filter); the pre-filter rows are another pass of the CLI, empty here
+    names = {w: n for w, n in ((capi.QC_R1_POST, "r1_post"), (capi.QC_R2_POST, "r2_post")) if w in stats["qc"]}
+    for w, n in names.items():
+        put("qc_" + n, stats["qc"][w])
+    for w, n in names.items():
+        keys, counts, order = stats["kmers"][w]
+        i = np.argsort(keys, kind="stable")
+        k = keys[i].astype(np.uint64)
+        # a key is 8 bytes of bases: split in two 32-bit halves, exact in float64
+        put("kmers_" + n, np.stack([(k >> np.uint64(32)).astype(np.float64), (k & np.uint64(0xFFFFFFFF)).astype(np.float64),
+                                    counts[i].astype(np.float64), order[i].astype(np.float64)], axis=1))
+    digests = []
+    for n, (mate, kind, pth) in enumerate((m + 1, kind, p) for m, trio in enumerate(outs) for kind, p in zip(("good", "bad"), trio)):
+        size = os.path.getsize(pth)
+        h = hashlib.sha256()
+        with open(pth, "rb") as f:
+            for piece in iter(lambda: f.read(1 << 24), b""):
+                h.update(piece)
+            if size <= DUMP_WINDOWS * DUMP_WINDOW_BYTES:
+                sample = os.pread(f.fileno(), size, 0)
+            else:
+                starts = np.sort(np.random.default_rng(1000 + n).integers(0, size - DUMP_WINDOW_BYTES + 1, DUMP_WINDOWS))
+                sample = b"".join(os.pread(f.fileno(), DUMP_WINDOW_BYTES, int(s)) for s in starts)
+        put("R%d_%s_sample" % (mate, kind), np.frombuffer(sample, dtype=np.uint8), np.float32)
+        digests.append(np.frombuffer(h.digest(), dtype=">u4"))
+    put("output_sha256", digests)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -122,7 +180,16 @@ def main():
     ap.add_argument("--workload", default="config3", choices=["config3", "config2", "config5"],
                     help="config3 (default, the metric's workload): PE 2x150; config2: SE 1x150 filter+trim only; "
                          "config5: PE 2x250 + 17-base barcode / verify prefix, barcode mode on")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beside `value`: the device steps and the roofline (with its "
+                    "rocprofv3 --pmc child runs), pinned -> pinned, K inputs, the 100 M-read input, .gz, the CPU baseline.  Without it a run "
+                    "sets up, warms up, times the file -> file steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / "
+                    "float64): the pipe's result, counters, histograms, post-filter QC rows and k-mers, and a seeded sample plus a SHA-256 of every output file")
     args = ap.parse_args()
+    if (args.device_only or args.text_step_only or args.spans_step_only) and not args.full:
+        ap.error("--device-only / --text-step-only / --spans-step-only measure the device step: add --full")
+    if args.steps < 1 and not args.device_only:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -147,8 +214,11 @@ def main():
     W = d["seq1"].shape[1]
     t_gen = time.time() - t_gen
 
-    import torch  # plumbing only (barrier / max-over-ranks); loaded before libafterqc_hip.so so both share one HIP runtime
-    dist = None
+    # torch is plumbing only (barrier / max-over-ranks), loaded before libafterqc_hip.so so both share one HIP runtime; a plain
+    # one-process run needs none of it and does not pay its import
+    torch = dist = None
+    if world > 1 or args.full:
+        import torch
     # AQC_BENCH_SHARE_GPU=1 (debug only): all ranks on GPU 0 with the gloo backend, to exercise the multi-rank code
     # path on a one-GPU box.  The driver's runs use one GPU per rank over RCCL.
     share_gpu = os.environ.get("AQC_BENCH_SHARE_GPU") == "1"
@@ -190,8 +260,12 @@ def main():
     reads_per_gpu = n_rec * (2 if paired else 1)
     text_in = sum(t[1] for t in texts)
 
+    def device_sync():
+        if torch is not None and torch.cuda.is_available():
+            torch.cuda.synchronize()
+
     def barrier():
-        torch.cuda.synchronize() if torch.cuda.is_available() else None
+        device_sync()
         if dist is not None:
             dist.barrier()
 
@@ -202,150 +276,151 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    # ================= A. the device step: text resident in HBM -> good / bad text in HBM (every rank, its own GPU) =========
-    # (a chunk is < 2 GiB of text per mate: 5 M records of 347 bytes fit one chunk, longer inputs are spread over the slots)
-    per_slot = min(n_rec, int(1.9e9 // w))
-    n_res = (n_rec + per_slot - 1) // per_slot
-    assert n_res <= eng.n_slots, "input too large to keep resident in %d slots" % eng.n_slots
-    t_up = time.perf_counter()
-    res_n = []
-    for sl in range(n_res):
-        lo, hi = sl * per_slot, min(n_rec, (sl + 1) * per_slot)
-        views = [(t[0].array[lo * w:], (hi - lo) * w) for t in texts]
-        if paired:
-            info = eng.frame(sl, views[0][0], views[0][1], True, views[1][0], views[1][1], True, first_index=first_index + lo)
-        else:
-            info = eng.frame(sl, views[0][0], views[0][1], True, first_index=first_index + lo)
-        assert int(info.n) == hi - lo, (int(info.n), hi - lo)
-        res_n.append((lo, hi))
-    for sl in range(n_res):
-        eng.sync(sl)
-    t_up = time.perf_counter() - t_up          # host -> HBM + first framing (reported)
-
-    def step(spans=False):
-        total = [0] * 6
-        for sl, (lo, hi) in enumerate(res_n):
-            eng.reframe(sl)
-            eng.run(sl)
-            n_qc = (hi - lo) if args.qc_sample <= 0 else max(0, min(hi - lo, args.qc_sample - 1 - (first_index + lo)))
-            if n_qc > 0:
-                eng.qc_stat(sl, capi.QC_R1_POST, 0, 0, n_qc, 1)
-                if paired:
-                    eng.qc_stat(sl, capi.QC_R2_POST, 1, 0, n_qc, 1)
-            # (returns once the sizes are known; the writer kernels are still queued)
-            if spans:
-                # what aqc_pipe_run does for plain-text outputs: the good records that go out as their own bytes are not copied
-                # (they are written from the host's input buffer), stream 0 holds only the rebuilt ones + the event list
-                sz, _ = eng.format_spans(sl, hi - lo, False)
+    # ================= A. (--full) the device step: text resident in HBM -> good / bad text in HBM (every rank, its own GPU) ==
+    good_frac = None
+    if args.full:
+        # (a chunk is < 2 GiB of text per mate: 5 M records of 347 bytes fit one chunk, longer inputs are spread over the slots)
+        per_slot = min(n_rec, int(1.9e9 // w))
+        n_res = (n_rec + per_slot - 1) // per_slot
+        assert n_res <= eng.n_slots, "input too large to keep resident in %d slots" % eng.n_slots
+        t_up = time.perf_counter()
+        res_n = []
+        for sl in range(n_res):
+            lo, hi = sl * per_slot, min(n_rec, (sl + 1) * per_slot)
+            views = [(t[0].array[lo * w:], (hi - lo) * w) for t in texts]
+            if paired:
+                info = eng.frame(sl, views[0][0], views[0][1], True, views[1][0], views[1][1], True, first_index=first_index + lo)
             else:
-                sz = eng.format(sl, hi - lo, False)
-            total = [a + b for a, b in zip(total, sz)]
-        return total
-
-    def sync_all():
+                info = eng.frame(sl, views[0][0], views[0][1], True, first_index=first_index + lo)
+            assert int(info.n) == hi - lo, (int(info.n), hi - lo)
+            res_n.append((lo, hi))
         for sl in range(n_res):
             eng.sync(sl)
+        t_up = time.perf_counter() - t_up          # host -> HBM + first framing (reported)
 
-    dsteps = max(1, args.device_steps)
-    for _ in range(min(3, max(1, args.warmup))):
-        sizes = step()
-    sync_all()
-    barrier()
-    for sl in range(n_res):
-        eng.timing_reset(sl)
-    t0 = time.perf_counter()
-    for _ in range(dsteps if not args.spans_step_only else 0):
-        sizes = step()
-    sync_all()
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-    dev_elapsed = max_over_ranks(time.perf_counter() - t0)
-    # ... and the same step the way the pipe runs it for plain-text outputs (aqc_format_spans)
-    spans_sizes = step(True)
-    sync_all()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(dsteps if not args.text_step_only else 0):
-        spans_sizes = step(True)
-    sync_all()
-    spans_elapsed = max_over_ranks(time.perf_counter() - t0)
-    # ... and the text step on a context created with AQC_FUSED=1 (opt-in): aqc_run's verdict kernel places every record
-    # and copies the whole good ones itself, aqc_format rebuilds the rest.  Same bytes; reported beside the default step.
-    fused = None
-    if paired and args.workload == "config3" and not args.spans_step_only and not args.no_fused_step:
-        old_f = os.environ.get("AQC_FUSED")
-        os.environ["AQC_FUSED"] = "1"
-        try:
-            eng_f = capi.Engine(device_index, max(1, n_res))
-        finally:
-            if old_f is None:
-                os.environ.pop("AQC_FUSED", None)
-            else:
-                os.environ["AQC_FUSED"] = old_f
-        eng_f.set_config(cfg)
-        eng_f.reset_stats()
-        for sl, (lo, hi) in enumerate(res_n):
-            views = [(t[0].array[lo * w:], (hi - lo) * w) for t in texts]
-            eng_f.frame(sl, views[0][0], views[0][1], True, views[1][0], views[1][1], True, first_index=first_index + lo)
-
-        def step_fused():
-            total, taken = [0] * 6, True
+        def step(spans=False):
+            total = [0] * 6
             for sl, (lo, hi) in enumerate(res_n):
-                eng_f.reframe(sl)
-                eng_f.run(sl)
+                eng.reframe(sl)
+                eng.run(sl)
                 n_qc = (hi - lo) if args.qc_sample <= 0 else max(0, min(hi - lo, args.qc_sample - 1 - (first_index + lo)))
                 if n_qc > 0:
-                    eng_f.qc_stat(sl, capi.QC_R1_POST, 0, 0, n_qc, 1)
-                    eng_f.qc_stat(sl, capi.QC_R2_POST, 1, 0, n_qc, 1)
-                sz = eng_f.format(sl, hi - lo, False)
-                taken = taken and eng_f.format_fused(sl)
+                    eng.qc_stat(sl, capi.QC_R1_POST, 0, 0, n_qc, 1)
+                    if paired:
+                        eng.qc_stat(sl, capi.QC_R2_POST, 1, 0, n_qc, 1)
+                # (returns once the sizes are known; the writer kernels are still queued)
+                if spans:
+                    # what aqc_pipe_run does for plain-text outputs: the good records that go out as their own bytes are not copied
+                    # (they are written from the host's input buffer), stream 0 holds only the rebuilt ones + the event list
+                    sz, _ = eng.format_spans(sl, hi - lo, False)
+                else:
+                    sz = eng.format(sl, hi - lo, False)
                 total = [a + b for a, b in zip(total, sz)]
-            return total, taken
+            return total
 
-        for _ in range(2):
-            fused_sizes, fused_taken = step_fused()
-        for sl in range(n_res):
-            eng_f.sync(sl)
+        def sync_all():
+            for sl in range(n_res):
+                eng.sync(sl)
+
+        dsteps = max(1, args.device_steps)
+        for _ in range(min(3, max(1, args.warmup))):
+            sizes = step()
+        sync_all()
         barrier()
-        t0 = time.perf_counter()
-        for _ in range(dsteps):
-            fused_sizes, fused_taken = step_fused()
-        for sl in range(n_res):
-            eng_f.sync(sl)
-        fused_elapsed = max_over_ranks(time.perf_counter() - t0)
-        fused = {"ms_per_step": round(1000.0 * fused_elapsed / dsteps, 4), "mreads_s": round(reads_per_gpu * world / max(fused_elapsed / dsteps, 1e-9) / 1e6, 2),
-                 "placement_taken": bool(fused_taken), "same_sizes_as_device_step": [int(x) for x in fused_sizes] == [int(x) for x in sizes] if not args.spans_step_only else None,
-                 "what": "the text step on a context created with AQC_FUSED=1: fast_filter_overlap_kernel<10,true,12,false,true> gives every record its place "
-                         "(in-batch scans + decoupled look-back over the batches) and copies the good records that go out as their own bytes; aqc_format "
-                         "patches / rebuilds the rest (no sizing passes, no whole-record copy kernel)"}
-        eng_f.close()
-    kms, klaunch = eng.timing_mean(0)
-    for sl in range(1, n_res):
-        k2, l2 = eng.timing_mean(sl)
-        kms = kms + k2                    # per step the kernel runs once per resident chunk: times add up
-    counters = eng.counters()
-    res_gpu = eng.fetch_results(0) if (rank == 0 and world == 1 and args.cpu_sample > 0 and paired) else None
-    if n_res > 1:
-        # With several chunks resident their slots' streams overlap: the dominant kernel of one chunk shares the GPU with
-        # the writer kernels of another and its event time says little about the kernel.  For the roofline line the
-        # kernel is timed again alone, chunk after chunk.
         for sl in range(n_res):
             eng.timing_reset(sl)
-        for _ in range(dsteps):
+        t0 = time.perf_counter()
+        for _ in range(dsteps if not args.spans_step_only else 0):
+            sizes = step()
+        sync_all()
+        device_sync()
+        dev_elapsed = max_over_ranks(time.perf_counter() - t0)
+        # ... and the same step the way the pipe runs it for plain-text outputs (aqc_format_spans)
+        spans_sizes = step(True)
+        sync_all()
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(dsteps if not args.text_step_only else 0):
+            spans_sizes = step(True)
+        sync_all()
+        spans_elapsed = max_over_ranks(time.perf_counter() - t0)
+        # ... and the text step on a context created with AQC_FUSED=1 (opt-in): aqc_run's verdict kernel places every record
+        # and copies the whole good ones itself, aqc_format rebuilds the rest.  Same bytes; reported beside the default step.
+        fused = None
+        if paired and args.workload == "config3" and not args.spans_step_only and not args.no_fused_step:
+            old_f = os.environ.get("AQC_FUSED")
+            os.environ["AQC_FUSED"] = "1"
+            try:
+                eng_f = capi.Engine(device_index, max(1, n_res))
+            finally:
+                if old_f is None:
+                    os.environ.pop("AQC_FUSED", None)
+                else:
+                    os.environ["AQC_FUSED"] = old_f
+            eng_f.set_config(cfg)
+            eng_f.reset_stats()
+            for sl, (lo, hi) in enumerate(res_n):
+                views = [(t[0].array[lo * w:], (hi - lo) * w) for t in texts]
+                eng_f.frame(sl, views[0][0], views[0][1], True, views[1][0], views[1][1], True, first_index=first_index + lo)
+
+            def step_fused():
+                total, taken = [0] * 6, True
+                for sl, (lo, hi) in enumerate(res_n):
+                    eng_f.reframe(sl)
+                    eng_f.run(sl)
+                    n_qc = (hi - lo) if args.qc_sample <= 0 else max(0, min(hi - lo, args.qc_sample - 1 - (first_index + lo)))
+                    if n_qc > 0:
+                        eng_f.qc_stat(sl, capi.QC_R1_POST, 0, 0, n_qc, 1)
+                        eng_f.qc_stat(sl, capi.QC_R2_POST, 1, 0, n_qc, 1)
+                    sz = eng_f.format(sl, hi - lo, False)
+                    taken = taken and eng_f.format_fused(sl)
+                    total = [a + b for a, b in zip(total, sz)]
+                return total, taken
+
+            for _ in range(2):
+                fused_sizes, fused_taken = step_fused()
             for sl in range(n_res):
-                eng.run(sl)
-                eng.sync(sl)
-        k_alone = eng.timing_mean(0)[0]
+                eng_f.sync(sl)
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(dsteps):
+                fused_sizes, fused_taken = step_fused()
+            for sl in range(n_res):
+                eng_f.sync(sl)
+            fused_elapsed = max_over_ranks(time.perf_counter() - t0)
+            fused = {"ms_per_step": round(1000.0 * fused_elapsed / dsteps, 4), "mreads_s": round(reads_per_gpu * world / max(fused_elapsed / dsteps, 1e-9) / 1e6, 2),
+                     "placement_taken": bool(fused_taken), "same_sizes_as_device_step": [int(x) for x in fused_sizes] == [int(x) for x in sizes] if not args.spans_step_only else None,
+                     "what": "the text step on a context created with AQC_FUSED=1: fast_filter_overlap_kernel<10,true,12,false,true> gives every record its place "
+                             "(in-batch scans + decoupled look-back over the batches) and copies the good records that go out as their own bytes; aqc_format "
+                             "patches / rebuilds the rest (no sizing passes, no whole-record copy kernel)"}
+            eng_f.close()
+        kms, klaunch = eng.timing_mean(0)
         for sl in range(1, n_res):
-            k_alone = k_alone + eng.timing_mean(sl)[0]
-        kms[capi.K_FILTER_OVERLAP] = k_alone[capi.K_FILTER_OVERLAP]
-    dev_ms = 1000.0 * dev_elapsed / dsteps
-    dev_value = reads_per_gpu * world / (dev_elapsed / dsteps) / 1e6
-    bytes_per_record = (4 * RL + 56) if paired else (2 * RL + 20)
-    k_ms = float(kms[capi.K_FILTER_OVERLAP])
-    achieved = n_rec * bytes_per_record / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-    text_out = int(sum(sizes))
-    good_frac = float(counters[capi.C_GOOD_READS]) / max(1.0, float(counters[capi.C_TOTAL_READS]))
+            k2, l2 = eng.timing_mean(sl)
+            kms = kms + k2                    # per step the kernel runs once per resident chunk: times add up
+        counters = eng.counters()
+        res_gpu = eng.fetch_results(0) if (rank == 0 and world == 1 and args.cpu_sample > 0 and paired) else None
+        if n_res > 1:
+            # With several chunks resident their slots' streams overlap: the dominant kernel of one chunk shares the GPU with
+            # the writer kernels of another and its event time says little about the kernel.  For the roofline line the
+            # kernel is timed again alone, chunk after chunk.
+            for sl in range(n_res):
+                eng.timing_reset(sl)
+            for _ in range(dsteps):
+                for sl in range(n_res):
+                    eng.run(sl)
+                    eng.sync(sl)
+            k_alone = eng.timing_mean(0)[0]
+            for sl in range(1, n_res):
+                k_alone = k_alone + eng.timing_mean(sl)[0]
+            kms[capi.K_FILTER_OVERLAP] = k_alone[capi.K_FILTER_OVERLAP]
+        dev_ms = 1000.0 * dev_elapsed / dsteps
+        dev_value = reads_per_gpu * world / (dev_elapsed / dsteps) / 1e6
+        bytes_per_record = (4 * RL + 56) if paired else (2 * RL + 20)
+        k_ms = float(kms[capi.K_FILTER_OVERLAP])
+        achieved = n_rec * bytes_per_record / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+        text_out = int(sum(sizes))
+        good_frac = float(counters[capi.C_GOOD_READS]) / max(1.0, float(counters[capi.C_TOTAL_READS]))
 
     # ================= B/C. ONE input through the whole-input pipe, driven by rank 0 over every device ========================
     if args.devices:
@@ -393,8 +468,8 @@ def main():
         for e in engines:
             e.reset_stats()
 
-    # ---- B. page-locked memory -> page-locked memory (PCIe inclusive): this rank's share only
-    if args.pipe_runs > 0 and rank == 0:
+    # ---- B. (--full) page-locked memory -> page-locked memory (PCIe inclusive): this rank's share only
+    if args.full and args.pipe_runs > 0 and rank == 0:
         inputs = [(t[0].array, t[1]) for t in texts]
         ts = []
         for it in range(args.pipe_runs + 1):            # the first run allocates the page-locked rings: not timed
@@ -460,8 +535,7 @@ def main():
             t1 = time.perf_counter()
             if driver:
                 last = pipe.run(paths, outs, chunk_records=K, qc_sample=args.qc_sample)
-            if torch.cuda.is_available():
-                torch.cuda.synchronize()
+            device_sync()
             if dist is not None:
                 dist.barrier()
             dt = max_over_ranks(time.perf_counter() - t1)
@@ -469,6 +543,13 @@ def main():
                 assert not last.anomaly and int(last.records) == n_rec * copies, (last.anomaly, int(last.records))
             if it >= args.warmup:
                 step_times.append(dt)
+        if driver and step_times:
+            # the engines' statistics were reset before the last step: they are its own
+            if good_frac is None:
+                c = sum(e.counters() for e in engines)
+                good_frac = float(c[capi.C_GOOD_READS]) / max(1.0, float(c[capi.C_TOTAL_READS]))
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, last, capi.merge_stats([capi.collect_stats(e, paired) for e in engines]), outs, tag)
         if rank == 0 and step_times:
             f2f = {"seconds_mean": round(sum(step_times) / len(step_times), 4), "seconds_min": round(min(step_times), 4),
                    "seconds_median": round(sorted(step_times)[len(step_times) // 2], 4),
@@ -478,7 +559,7 @@ def main():
         # ---- K inputs at once (rank 0, N = 1 runs): K file pairs, K contexts on the device(s), K pipes, 4 K output files.  One input
         #      cannot be written faster than its two big output files take (~10 GB/s per file on these hosts); the
         #      reference's own parallelism is per input file, and that shape is not bound by one file's write rate.
-        if args.inputs > 1 and rank == 0 and world == 1 and not args.device_only and step_times:
+        if args.full and args.inputs > 1 and rank == 0 and world == 1 and not args.device_only and step_times:
             import threading
             KI = args.inputs
             mi_eng, mi_pipe, mi_paths, mi_outs = [eng], [pipe], [paths], [outs]
@@ -534,7 +615,7 @@ def main():
         #      good files out).  The inputs are made clean first (tmpfs, or sync()): a run that starts with 35 GB of dirty input pages
         #      in the cache hits the cgroup's dirty limit half way through its own 34 GB of output and is throttled to the disk's
         #      write-back rate (round 4's soak: 20 Mreads/s) — which says something about the bench, not about the pipe.
-        if rank == 0 and world == 1 and args.big_copies > 1 and not args.device_only and step_times and args.workload == "config3":
+        if args.full and rank == 0 and world == 1 and args.big_copies > 1 and not args.device_only and step_times and args.workload == "config3":
             BC = args.big_copies
             need_out = int(1.15 * BC * text_out_estimate) if (text_out_estimate := int(sum(last.bytes_out))) else 0
             shm = "/dev/shm"
@@ -563,8 +644,7 @@ def main():
                     reset_all()
                     t1 = time.perf_counter()
                     rb = pipe.run(big_paths, big_outs, chunk_records=K, qc_sample=args.qc_sample)
-                    if torch.cuda.is_available():
-                        torch.cuda.synchronize()
+                    device_sync()
                     dtb = time.perf_counter() - t1
                     assert not rb.anomaly and int(rb.records) == n_rec * BC, (rb.anomaly, int(rb.records))
                     big = {"reads": reads_per_gpu * BC, "seconds": round(dtb, 3), "mreads_s": round(reads_per_gpu * BC / dtb / 1e6, 2), "input_gb": round(BC * text_in / 1e9, 2),
@@ -582,7 +662,7 @@ def main():
         # ---- N ranks, N GPUs: the OTHER shape next to `value` (one input over N GPUs, two output files: flat by design) — K = N inputs,
         #      one per GPU, every rank its own pipe on its own device over its own files, all at once: the shape that scales with the
         #      GPUs (files fan out).  Same barriers, max over ranks.  (With per-rank visibility `value` already IS this shape.)
-        if world > 1 and not per_rank and not args.device_only and args.inputs > 0:
+        if args.full and world > 1 and not per_rank and not args.device_only and args.inputs > 0:
             my_work = tempfile.mkdtemp(prefix="aqc_bench_k%d_" % rank, dir=base)
             try:
                 my_paths = []
@@ -604,8 +684,7 @@ def main():
                     barrier()
                     t1 = time.perf_counter()
                     r_k = my_pipe.run(my_paths, my_outs, chunk_records=K, qc_sample=args.qc_sample)
-                    if torch.cuda.is_available():
-                        torch.cuda.synchronize()
+                    device_sync()
                     if dist is not None:
                         dist.barrier()
                     dt = max_over_ranks(time.perf_counter() - t1)
@@ -623,7 +702,7 @@ def main():
         # ---- the same through gzip both ways: one-member inputs decoded by the host pool (the box's CPU quota is the bound),
         # .gz members built on the device
         gz_runs = args.gz_runs if args.gz_runs >= 0 else (3 if copies == 1 and shutil.which("gzip") else 0)
-        if gz_runs > 0 and rank == 0 and not args.device_only:
+        if args.full and gz_runs > 0 and rank == 0 and not args.device_only:
             import subprocess
             gz_paths = [p + ".gz" for p in paths]
             jobs = [subprocess.Popen(["gzip", "-2", "-c", p], stdout=open(g, "wb")) for p, g in zip(paths, gz_paths)]
@@ -710,7 +789,6 @@ def main():
           "config2": "config2: ONE input of %d synthetic SE 1x150 bp reads as one FASTQ file -> good / bad files, -f 5 -t 5, qc_sample %d" % (n_rec * copies, args.qc_sample),
           "config5": "config5 (plain text; gzip: tools/e2e_bench.py / --gz-runs): ONE input of %d synthetic PE 2x250 bp pairs + 17-base barcode/verify "
                      "prefix as two FASTQ files -> good / bad files, barcode mode, qc_sample %d" % (n_rec * copies, args.qc_sample)}[args.workload]
-    traffic, traffic_src = hbm_traffic(args, n_rec, live=(rank == 0 and world == 1 and not args.device_only and not args.no_pmc))
     out = {
         "metric": ({"config3": "Mreads/s (paired 2x150 bp) end-to-end good/bad split", "config2": "Mreads/s (single-end 1x150 bp, BASELINE config 2) end-to-end good/bad split",
                     "config5": "Mreads/s (paired 2x250 bp + barcodes, BASELINE config 5 shape) end-to-end good/bad split"}[args.workload]
@@ -725,40 +803,46 @@ def main():
                                    "process cannot drive them all), no collective" % (world, n_rec)) if per_rank else
                                   ("one input, chunks of %d records dealt round robin over %d context(s) on device(s) %s by one process, no collective" % (K, n_ctx, dev_list)),
                    "text_in_gb": round(text_in * copies / 1e9, 3), "timing": "%d runs, each bracketed by barrier + device sync; outputs of the previous run unlinked in between (untimed)" % len(step_times)},
-        "roofline": {"bound": "hbm", "kernel": "fast_filter_overlap_kernel (+ its deferral list kernel)", "achieved": round(achieved, 2),
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                     "traffic": traffic, "traffic_source": traffic_src,
-                     "kernel_ms": round(k_ms, 4), "launches": int(klaunch[capi.K_FILTER_OVERLAP]),
-                     "algorithmic_bytes_per_launch": n_rec * bytes_per_record,
-                     "qc_stat_ms_per_call": round(float(kms[capi.K_QC_STAT]), 4),
-                     "measured_in": "the device-step loop of this run (HIP events on the slot's stream)"},
-        "device_step_mreads_s": round(dev_value, 2),
-        "device_step_spans": {"ms_per_step": round(1000.0 * spans_elapsed / dsteps, 4), "mreads_s": round(reads_per_gpu * world / max(spans_elapsed / dsteps, 1e-9) / 1e6, 2),
-                              "rebuilt_good_and_bad_text_gb_per_gpu": round(sum(spans_sizes) / 1e9, 4),
-                              "what": "the device step as aqc_pipe_run issues it for plain-text outputs: aqc_reframe -> aqc_run -> aqc_qc_stat -> aqc_format_spans "
-                                      "— good records that go out as their own bytes are not copied on the device (the file writers take them from the "
-                                      "page-locked input buffer), only the bad / trimmed / corrected records are formatted"},
-        "device_step_fused": fused,
-        "device_step": {"ms_per_step": round(dev_ms, 4), "steps": dsteps, "text_in_gb_per_gpu": round(text_in / 1e9, 3),
-                        "text_out_gb_per_gpu": round(text_out / 1e9, 3), "step_text_gb_s": round((text_in + text_out) / (dev_ms * 1e-3) / 1e9, 1),
-                        "what": "text resident in HBM -> aqc_reframe -> aqc_run -> aqc_qc_stat -> aqc_format (no PCIe, no files), every rank on its own GPU: the step "
-                                "aqc_pipe_run issues by default.  The cheaper steps (`device_step_spans`, `device_step_fused`) are opt-in: as defaults they lose "
-                                "END TO END on a host bound by its two file writers (profiles/r05_spans_ab.txt, r06_spans_assemble_ab.txt)"},
-        "pinned_to_pinned_mreads_s": pinned["mreads_s"] if pinned else None,
-        "pinned_to_pinned": pinned, "file_to_file": f2f, "file_to_file_100M": big, "file_to_file_gz": f2f_gz, "file_to_gz": f2gz,
-        "multi_input_file_to_file_mreads_s": multi["mreads_s"] if multi else None, "multi_input_file_to_file": multi,
-        "good_reads_frac": round(good_frac, 5),
-        "gen_s": round(t_gen, 1), "text_render_s": round(t_txt, 1), "first_upload_s": round(t_up, 3),
+        "file_to_file": f2f,
+        "good_reads_frac": round(good_frac, 5) if good_frac is not None else None,
+        "gen_s": round(t_gen, 1), "text_render_s": round(t_txt, 1),
         # `value` is the contract's figure: reads over the MEAN of the timed steps.  The boxes differ by more than a round changes
         # (the same code: 48 - 56 Mreads/s over four boxes in round 5), and single steps by +-8 %: the median and the best step of
         # THIS run stand beside it, with the box's name
         "value_median": round(pipe_reads / sorted(step_times)[len(step_times) // 2] / 1e6, 3) if step_times else None,
         "value_best": round(pipe_reads / min(step_times) / 1e6, 3) if step_times else None,
-        "host": dict({"cpus": os.cpu_count(), "cpu_quota": _cpu_quota()}, **_host_identity()),
+        "host": dict({"cpus": os.cpu_count(), "cpu_quota": _cpu_quota()}, **_host_identity(query_gpu=args.full)),
     }
+    if args.full:
+        traffic, traffic_src = hbm_traffic(args, n_rec, live=(rank == 0 and world == 1 and not args.device_only and not args.no_pmc))
+        out.update({
+            "roofline": {"bound": "hbm", "kernel": "fast_filter_overlap_kernel (+ its deferral list kernel)", "achieved": round(achieved, 2),
+                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                         "traffic": traffic, "traffic_source": traffic_src,
+                         "kernel_ms": round(k_ms, 4), "launches": int(klaunch[capi.K_FILTER_OVERLAP]),
+                         "algorithmic_bytes_per_launch": n_rec * bytes_per_record,
+                         "qc_stat_ms_per_call": round(float(kms[capi.K_QC_STAT]), 4),
+                         "measured_in": "the device-step loop of this run (HIP events on the slot's stream)"},
+            "device_step_mreads_s": round(dev_value, 2),
+            "device_step_spans": {"ms_per_step": round(1000.0 * spans_elapsed / dsteps, 4), "mreads_s": round(reads_per_gpu * world / max(spans_elapsed / dsteps, 1e-9) / 1e6, 2),
+                                  "rebuilt_good_and_bad_text_gb_per_gpu": round(sum(spans_sizes) / 1e9, 4),
+                                  "what": "the device step as aqc_pipe_run issues it for plain-text outputs: aqc_reframe -> aqc_run -> aqc_qc_stat -> aqc_format_spans "
+                                          "— good records that go out as their own bytes are not copied on the device (the file writers take them from the "
+                                          "page-locked input buffer), only the bad / trimmed / corrected records are formatted"},
+            "device_step_fused": fused,
+            "device_step": {"ms_per_step": round(dev_ms, 4), "steps": dsteps, "text_in_gb_per_gpu": round(text_in / 1e9, 3),
+                            "text_out_gb_per_gpu": round(text_out / 1e9, 3), "step_text_gb_s": round((text_in + text_out) / (dev_ms * 1e-3) / 1e9, 1),
+                            "what": "text resident in HBM -> aqc_reframe -> aqc_run -> aqc_qc_stat -> aqc_format (no PCIe, no files), every rank on its own GPU: the step "
+                                    "aqc_pipe_run issues by default.  The cheaper steps (`device_step_spans`, `device_step_fused`) are opt-in: as defaults they lose "
+                                    "END TO END on a host bound by its two file writers (profiles/r05_spans_ab.txt, r06_spans_assemble_ab.txt)"},
+            "pinned_to_pinned_mreads_s": pinned["mreads_s"] if pinned else None,
+            "pinned_to_pinned": pinned, "file_to_file_100M": big, "file_to_file_gz": f2f_gz, "file_to_gz": f2gz,
+            "multi_input_file_to_file_mreads_s": multi["mreads_s"] if multi else None, "multi_input_file_to_file": multi,
+            "first_upload_s": round(t_up, 3),
+        })
 
-    # ---- CPU baseline (rank 0, N=1 only): the oracle, 1 core, bounded sample of the same workload
-    if rank == 0 and world == 1 and args.cpu_sample > 0 and paired:
+    # ---- (--full) CPU baseline (rank 0, N=1 only): the oracle, 1 core, bounded sample of the same workload
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0 and paired:
         from oracle import oracle
         m = min(args.cpu_sample, args.pairs)
         sub = capi.Batch.from_matrices(d["seq1"][:m], d["qual1"][:m], d["len1"][:m], d["seq2"][:m], d["qual2"][:m], d["len2"][:m])
@@ -823,19 +907,20 @@ def main():
         dist.destroy_process_group()
 
 
-def _host_identity():
-    """which box this ran on (numbers from different boxes differ by up to 25 % on the bandwidth-bound kernels): host name, and the
-    GPU's unique id where rocm-smi is at hand"""
+def _host_identity(query_gpu=True):
+    """which box this ran on (numbers from different boxes differ by up to 25 % on the bandwidth-bound kernels): host name, and with
+    `query_gpu` the GPU's unique id where rocm-smi is at hand"""
     import socket
     import subprocess
     out = {"hostname": socket.gethostname()}
-    try:
-        txt = subprocess.run(["rocm-smi", "--showuniqueid"], capture_output=True, text=True, timeout=20).stdout
-        ids = [ln.split(":")[-1].strip() for ln in txt.splitlines() if "Unique ID" in ln]
-        if ids:
-            out["gpu_unique_id"] = ids[0] if len(ids) == 1 else ids
-    except Exception:
-        pass
+    if query_gpu:
+        try:
+            txt = subprocess.run(["rocm-smi", "--showuniqueid"], capture_output=True, text=True, timeout=20).stdout
+            ids = [ln.split(":")[-1].strip() for ln in txt.splitlines() if "Unique ID" in ln]
+            if ids:
+                out["gpu_unique_id"] = ids[0] if len(ids) == 1 else ids
+        except Exception:
+            pass
     try:
         with open("/proc/cpuinfo") as f:
             for ln in f:

@@ -493,6 +493,25 @@ def e2e_cases():
             for (name, argv, spec, keep) in cases.CASES]
 
 
+def gen_native_editdistance():
+    """the reference's own C++ edit distance (oracle/_ref/libed.so, which oracle/Makefile compiles from the reference) on 3000
+    random pairs over ACGTN of 1 - 39 bases"""
+    import ctypes
+    import numpy as np
+    lib = os.path.join(ROOT, "oracle", "_ref", "libed.so")
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
+    ed = ctypes.CDLL(lib)
+    ed.edit_distance.argtypes = [ctypes.c_char_p, ctypes.c_uint, ctypes.c_char_p, ctypes.c_uint]
+    ed.edit_distance.restype = ctypes.c_uint
+    rng = np.random.default_rng(7)
+    out = []
+    for _ in range(3000):
+        a = bytes(rng.choice(list(b"ACGTN"), rng.integers(1, 40)).astype(np.uint8))
+        b = bytes(rng.choice(list(b"ACGTN"), rng.integers(1, 40)).astype(np.uint8))
+        out.append([a.decode(), b.decode(), int(ed.edit_distance(a, len(a), b, len(b)))])
+    return out
+
+
 def main():
     if not os.path.isdir(REF):
         print("reference not present at %s: golden vectors can only be regenerated in the build container" % REF)
@@ -510,6 +529,11 @@ def main():
         with gzip.open(os.path.join(HERE, "function_vectors.json.gz"), "wt") as f:
             json.dump(vec, f)
         print("function vectors:", {k: len(v) for k, v in vec.items()})
+    if not only or "ednative" in only:
+        vec = gen_native_editdistance()
+        with gzip.open(os.path.join(HERE, "editdistance_native.json.gz"), "wt") as f:
+            json.dump(vec, f)
+        print("native edit distance vectors:", len(vec))
     if not only or "text" in only:
         vec = gen_text_vectors()
         with gzip.open(os.path.join(HERE, "text_vectors.json.gz"), "wt") as f:

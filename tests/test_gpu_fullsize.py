@@ -130,7 +130,7 @@ def test_bench_two_ranks_shared_gpu(tmp_path):
     env = dict(os.environ, AQC_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--pairs", "500000", "--cpu-sample", "0"]
+           "--pairs", "500000", "--cpu-sample", "0", "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -145,6 +145,40 @@ def test_bench_two_ranks_shared_gpu(tmp_path):
     assert "one input" in out["config"]["parallelism"] or "ONE input" in out["config"]["parallelism"], out["config"]
     mi = out["multi_input_file_to_file"]
     assert mi and mi["inputs"] == 2 and mi["output_files"] == 8 and mi["mreads_s"] > 0, mi
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """bench.py without --full: the headline line alone over `--steps` timed steps, and --dump-outputs writes what the last step
+    computed (its own statistics, a sample and a digest of every output file), under 64 MB and the same on a second run"""
+    pairs, dumps = 200_000, []
+    for k in range(2):
+        dump = str(tmp_path / ("dump%d" % k))
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", str(pairs),
+               "--dump-outputs", dump]
+        p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 2 and out["config"]["timing"].startswith("2 runs") and out["unit"] == "Mreads/s" and out["higher_is_better"]
+        assert abs(out["value"] - 2 * pairs / (out["ms_per_step"] * 1e-3) / 1e6) < 1e-3 * out["value"]
+        for key in ("roofline", "device_step", "device_step_fused", "pinned_to_pinned", "file_to_file_gz", "multi_input_file_to_file", "cpu_baseline"):
+            assert key not in out, key
+        arrays = {f[:-4]: np.load(os.path.join(dump, f)) for f in sorted(os.listdir(dump))}
+        assert all(a.dtype in (np.float32, np.float64) and a.size for a in arrays.values())
+        assert {"qc_r1_post", "qc_r2_post", "kmers_r1_post", "kmers_r2_post"} <= arrays.keys()
+        assert sum(a.nbytes for a in arrays.values()) <= 64e6
+        res, c = arrays["pipe_result"], arrays["counters"]
+        assert res[0] == pairs and c[capi.C_TOTAL_READS] == pairs          # the last step's statistics alone
+        assert out["good_reads_frac"] == round(c[capi.C_GOOD_READS] / c[capi.C_TOTAL_READS], 5)
+        assert arrays["output_sha256"].shape == (4, 8)
+        for mate, stream in ((1, 0), (1, 1), (2, 0), (2, 1)):
+            sample = arrays["R%d_%s_sample" % (mate, ("good", "bad")[stream])]
+            assert sample.size == min(int(res[2 + 3 * (mate - 1) + stream]), 256 * 4096) and sample.max() < 128
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 def _hash_file(path, limit=None):

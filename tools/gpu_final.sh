@@ -8,7 +8,7 @@ rm -rf /tmp/pytest-of-* /tmp/aqc_* 2>/dev/null      # (a box may be one of this 
 if has smoke; then python -c "import __graft_entry__ as g; g.smoke()" > $D/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $D/smoke.log; fi
 if has tests; then timeout 2400 python -m pytest tests -m gpu -q > $D/all.log 2>&1; echo rc=$? >> $D/all.log; grep -v "^{\|options:$" $D/all.log | tail -4 | cut -c1-300; rm -rf /tmp/pytest-of-* 2>/dev/null; fi
 if has bench; then
-  python bench.py > $D/bench.json 2> $D/bench.err; tail -c 200 $D/bench.err
+  python bench.py --full > $D/bench.json 2> $D/bench.err; tail -c 200 $D/bench.err
   python - <<PY
 import json
 d = json.loads(open("$D/bench.json").read().strip().splitlines()[-1])

@@ -1,6 +1,7 @@
 #!/bin/bash
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out; export TMPDIR=/tmp
-timeout 900 python -m pytest tests -m gpu -x -q > gpurun_out/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -4 gpurun_out/pytest_gpu.log
+OUT=${OUT:-$(mktemp -d)}; mkdir -p "$OUT"; export OUT=$(cd "$OUT" && pwd)      # this script's logs: $OUT, or a new temporary folder
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
+timeout 900 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -4 $OUT/pytest_gpu.log
 python - <<'PY' 2>&1 | grep -v amdgpu.ids
 import time, sys, gzip
 import numpy as np
@@ -31,11 +32,11 @@ import zlib
 t0 = time.perf_counter(); zz = zlib.compress(sample[:16 << 20], 2); t1 = time.perf_counter()
 print("zlib level 2: ratio %.3f, %.0f MB/s" % ((16 << 20) / len(zz), (16 << 20) / (t1 - t0) / 1e6))
 PY
-timeout 600 python bench.py --steps 3 --warmup 1 --cpu-sample 0 --pipe-runs 1 --device-steps 3 --gz-runs 2 > gpurun_out/bench_gz.log 2> gpurun_out/bench_gz.err; echo "bench gz rc=$?"
+timeout 600 python bench.py --full --steps 3 --warmup 1 --cpu-sample 0 --pipe-runs 1 --device-steps 3 --gz-runs 2 > $OUT/bench_gz.log 2> $OUT/bench_gz.err; echo "bench gz rc=$?"
 python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/bench_gz.log").read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.environ["OUT"] + "/bench_gz.log").read().strip().splitlines()[-1])
 print("value", d["value"], "gz", json.dumps(d["file_to_file_gz"]))
 PY
-python tools/e2e_bench.py --pairs 5000000 --gz 2>>gpurun_out/e2e_gz.err | tail -1 | cut -c1-700
-python tools/e2e_bench.py --pairs 2000000 --gz --config5 2>>gpurun_out/e2e_gz.err | tail -1 | cut -c1-700
+python tools/e2e_bench.py --pairs 5000000 --gz 2>>$OUT/e2e_gz.err | tail -1 | cut -c1-700
+python tools/e2e_bench.py --pairs 2000000 --gz --config5 2>>$OUT/e2e_gz.err | tail -1 | cut -c1-700
