@@ -5,9 +5,10 @@ Same 38 options, defaults and post-processing as the reference's CLI (after.py:1
 the same output layout (preprocesser.py:285-371), so `python -m afterqc_amd.after -1 R1.fq -2 R2.fq`
 drops in for `python after.py -1 R1.fq -2 R2.fq`.  Differences by design: Python 3; one GPU context
 per file pair instead of one OS process per file (after.py:168-171) — files of a directory are
-spread round-robin over the visible GPUs; the debubble detector pre-pass (debubble.py, PIL) is out
-of scope: `--debubble` consumes an existing <debubble_dir>/circles.csv exactly like `-1/-2` mode
-does upstream (after.py:207-212, preprocesser.py:235-236).
+spread round-robin over the visible GPUs.  With `-d DIR --debubble` the debubble pre-pass
+(afterqc_amd/debubble.py: the polyX census on the device, then upstream's CSVs and maps) runs first
+unless <debubble_dir>/circles.csv exists (after.py:177-184, 207-212); `-1/-2` mode only consumes an
+existing circles.csv, as upstream (preprocesser.py:235-236).
 """
 import copy
 import os
@@ -190,6 +191,15 @@ def processDir(folder, options, engine_factory=None, n_workers=None):
     return stats
 
 
+def runDebubble(options, engine=None):
+    """after.runDebubble (after.py:177-184): the pre-pass, unless its circles.csv is there already"""
+    from . import debubble
+    if os.path.exists(os.path.join(options.debubble_dir, "circles.csv")):
+        return
+    print("runDebubble")
+    debubble.debubbleDir(options.input_dir, 20, options.debubble_dir, options.draw, engine=engine)
+
+
 def main(argv=None):
     t0 = time.time()
     (options, args) = parseCommand(argv)
@@ -198,6 +208,11 @@ def main(argv=None):
         print('specify current dir as input dir')
         options.input_dir = "."
     if options.input_dir is not None:
+        if options.debubble:
+            try:
+                runDebubble(options)
+            except Exception:
+                print('Error happened with debubble function, just skip it now since it will not affect other features')
         processDir(options.input_dir, options)
     else:
         if options.barcode_flag in options.read1_file and parseBool(options.barcode):

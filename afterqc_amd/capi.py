@@ -51,6 +51,11 @@ RESULT_DTYPE = np.dtype([("flag", "u1"), ("n_edits", "u1"), ("start1", "<u2"), (
                          ("edits", EDIT_DTYPE, (3,)), ("barcode", "u1")])
 assert RESULT_DTYPE.itemsize == 32
 SPAN_EVENT_DTYPE = np.dtype([("in_start", "<u4"), ("in_len", "<u4"), ("out_len", "<u4")])      # struct aqc_span_event
+# struct aqc_census_hit: one polyX read of the debubble census (aqc_poly_census)
+CENSUS_HIT_DTYPE = np.dtype([("index", "<u8"), ("lane", "<i8"), ("tile_no", "<i8"), ("tile", "<i8"), ("x", "<i8"), ("y", "<i8"),
+                             ("name_off", "<u4"), ("name_len", "<u4"), ("count", "<i4"), ("surface", "u1"), ("swath", "u1"),
+                             ("camera", "u1"), ("base", "u1"), ("status", "u1"), ("wide", "u1"), ("pad_", "u1", (6,))])
+CENSUS_OK, CENSUS_NO_NAME, CENSUS_RAISE = 0, 1, 2
 
 
 def assemble_spans(chunk, end, events, stream0):
@@ -351,6 +356,9 @@ def load_library():
     lib.aqc_format_spans.argtypes = [P, C.c_int, C.c_uint64, C.c_int32, P, P]
     lib.aqc_fetch_span_events.argtypes = [P, C.c_int, C.c_int, P, C.c_uint64]
     lib.aqc_span_end.argtypes = [P, C.c_int, C.c_uint64, P]
+    lib.aqc_poly_census.argtypes = [P, C.c_int, C.c_int32, P]
+    lib.aqc_fetch_census.argtypes = [P, C.c_int, P, C.c_uint64]
+    lib.aqc_census_ms.argtypes = [P, C.c_int, P]
     lib.aqc_format_fused.argtypes = [P, C.c_int]
     lib.aqc_fetch_quality_views.argtypes = [P, C.c_int, C.c_int, P, C.c_uint64]
     lib.aqc_error_record.argtypes = [P, C.c_int, C.POINTER(C.c_uint64)]
@@ -422,7 +430,8 @@ def load_library():
                  "aqc_run", "aqc_qc_stat", "aqc_fetch_results", "aqc_sync", "aqc_kernel_ms", "aqc_timing_reset",
                  "aqc_timing_mean", "aqc_get_counters", "aqc_get_histograms", "aqc_get_qc", "aqc_get_kmers",
                  "aqc_overlap", "aqc_read_stats", "aqc_edit_distance", "aqc_frame", "aqc_frame_mixed", "aqc_reframe", "aqc_format", "aqc_format_plain",
-                 "aqc_fetch_text", "aqc_fetch_quality_views", "aqc_error_record", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused"):
+                 "aqc_fetch_text", "aqc_fetch_quality_views", "aqc_error_record", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused",
+                 "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms"):
         getattr(lib, name).restype = C.c_int
     if lib.aqc_abi_version() != 3:
         raise RuntimeError("libafterqc_hip.so ABI version mismatch")
@@ -435,7 +444,7 @@ EXPORTED_SYMBOLS = ["aqc_abi_version", "aqc_device_count", "aqc_device_index", "
                     "aqc_qc_stat", "aqc_fetch_results", "aqc_fetch_quality_views", "aqc_error_record", "aqc_sync", "aqc_last_deferred", "aqc_kernel_ms", "aqc_timing_reset",
                     "aqc_timing_mean", "aqc_get_counters",
                     "aqc_get_histograms", "aqc_get_qc", "aqc_get_kmers", "aqc_overlap", "aqc_read_stats",
-                    "aqc_edit_distance", "aqc_frame", "aqc_frame_mixed", "aqc_reframe", "aqc_format", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused", "aqc_format_plain", "aqc_fetch_text", "aqc_fetch_streams", "aqc_compress", "aqc_fetch_gz", "aqc_gunzip_dev", "aqc_host_alloc",
+                    "aqc_edit_distance", "aqc_frame", "aqc_frame_mixed", "aqc_reframe", "aqc_format", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused", "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms", "aqc_format_plain", "aqc_fetch_text", "aqc_fetch_streams", "aqc_compress", "aqc_fetch_gz", "aqc_gunzip_dev", "aqc_host_alloc",
                     "aqc_host_free",
                     "aqc_pipe_create", "aqc_pipe_destroy", "aqc_pipe_run", "aqc_pipe_last_error",
                     "aqc_host_count_newlines", "aqc_bgzf_compress", "aqc_pipe_split",
@@ -627,6 +636,24 @@ class Engine:
         end = (C.c_uint64 * 2)()
         self._check(self.lib.aqc_span_end(self.h, slot, n, end))
         return [int(x) for x in end]
+
+    def poly_census(self, slot, poly_max):
+        """aqc_poly_census over the records aqc_frame put in the (single-end) slot: the number of polyX reads"""
+        n = C.c_uint64()
+        self._check(self.lib.aqc_poly_census(self.h, slot, int(poly_max), C.byref(n)))
+        return int(n.value)
+
+    def fetch_census(self, slot, n):
+        """the n hits of the slot's last census (CENSUS_HIT_DTYPE), in no particular order"""
+        out = np.zeros(n, dtype=CENSUS_HIT_DTYPE)
+        if n:
+            self._check(self.lib.aqc_fetch_census(self.h, slot, _ptr(out), n))
+        return out
+
+    def census_ms(self, slot):
+        ms = C.c_float()
+        self._check(self.lib.aqc_census_ms(self.h, slot, C.byref(ms)))
+        return float(ms.value)
 
     def format_plain(self, slot, verdict_slot, n, store_overlap=False):
         """index files: whole records of `slot`, routed / renamed by the verdicts of `verdict_slot`"""

@@ -23,6 +23,7 @@
 #include "aqc_kernels.hpp"
 #include "aqc_fast.hpp"
 #include "aqc_text.hpp"
+#include "aqc_census.hpp"
 #include "aqc_gzdev.hpp"
 #include "aqc_gunzip_dev.hpp"
 #include "aqc_gz.hpp"
@@ -88,6 +89,10 @@ struct Slot {
     DevBuf t_scratch;              // FrameMeta[2] + scan totals
     DevBuf f_pos, f_tile, f_plan, f_patch, f_over, f_out[6], f_events[2];
     // AQC_FUSED=1: the verdict kernel placed the slot's records in their streams and copied the whole good ones (aqc_fast.hpp, FUSE)
+    // aqc_poly_census: the hits of the last census of the slot's records, and their counter
+    DevBuf census_hits, census_n;
+    uint64_t n_census = 0;
+    hipEvent_t census_ev[2] = {nullptr, nullptr};   // around the census kernels of the last aqc_poly_census (aqc_census_ms)
     DevBuf fz_state, fz_rec[2], fz_misc;      // look-back words per batch; position words per record; ticket | abort | totals[4]
     bool fused = false;                       // ... for the records the slot holds now (aqc_format checks fz_misc's abort word)
     bool formatted_fused = false;             // the last aqc_format took that placement (aqc_format_fused)
@@ -327,7 +332,8 @@ void aqc_destroy(aqc_ctx* c) {
                           &s.t_name_len[0], &s.t_name_len[1], &s.t_plus_off[0], &s.t_plus_off[1], &s.t_plus_len[0], &s.t_plus_len[1],
                           &s.t_qual_len[0], &s.t_qual_len[1], &s.t_scratch, &s.f_pos, &s.f_tile, &s.f_plan, &s.f_patch, &s.fz_state, &s.fz_rec[0], &s.fz_rec[1], &s.fz_misc, &s.f_over, &s.f_events[0], &s.f_events[1], &s.f_out[0], &s.f_out[1], &s.f_out[2],
                           &s.f_out[3], &s.f_out[4], &s.f_out[5], &s.g_stage, &s.g_sizes, &s.g_offsets, &s.g_total, &s.g_hist, &s.g_code,
-                          &s.g_packed[0], &s.g_packed[1], &s.g_packed[2], &s.g_packed[3], &s.g_packed[4], &s.g_packed[5]};
+                          &s.g_packed[0], &s.g_packed[1], &s.g_packed[2], &s.g_packed[3], &s.g_packed[4], &s.g_packed[5],
+                          &s.census_hits, &s.census_n};
         for (DevBuf* b : bufs) b->release();
         for (int k = 0; k < AQC_N_KERNELS; k++)
             for (int j = 0; j < 2; j++) {
@@ -335,6 +341,7 @@ void aqc_destroy(aqc_ctx* c) {
                 for (hipEvent_t e : s.ring[k][j]) (void)hipEventDestroy(e);
             }
         if (s.status) (void)hipFree(s.status);
+        for (hipEvent_t e : s.census_ev) if (e) (void)hipEventDestroy(e);
         if (s.ev_main) (void)hipEventDestroy(s.ev_main);
         if (s.ev_qc) (void)hipEventDestroy(s.ev_qc);
         if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -1989,6 +1996,69 @@ int aqc_span_end(aqc_ctx* c, int slot, uint64_t n, uint64_t end[2]) {
         HIP_TRY(hipMemcpyAsync(&off, (const uint32_t*)s->t_name_off[f].p + n, sizeof(off), hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(hipStreamSynchronize(s->stream));
         end[f] = off;
+    }
+    return 0;
+}
+
+// ---- debubble pre-pass: polyX census (aqc_census.hpp) ------------------------------------------------------------
+int aqc_poly_census(aqc_ctx* c, int slot, int32_t poly_max, uint64_t* n_hits) {
+    Slot* s;
+    int rc = get_slot(c, slot, &s);
+    if (rc) return rc;
+    if (!n_hits || poly_max < 1) return fail(AQC_ERR_ARG, "aqc_poly_census: null argument or poly_max < 1");
+    if (!s->framed) return fail(AQC_ERR_STATE, "aqc_poly_census needs a slot filled by aqc_frame");
+    if (s->paired) return fail(AQC_ERR_ARG, "aqc_poly_census: the census reads single-end slots (one file per chunk)");
+    *n_hits = 0;
+    s->n_census = 0;
+    const uint64_t n = s->n;
+    if (s->census_hits.reserve(sizeof(aqc_census_hit) * (n ? n : 1)) || s->census_n.reserve(sizeof(unsigned long long)))
+        return fail(AQC_ERR_HIP, "hipMalloc failed");
+    HIP_TRY(hipMemsetAsync(s->census_n.p, 0, sizeof(unsigned long long), s->stream));
+    if (n) {
+        const DevBatch& v = s->view;
+        for (hipEvent_t& e : s->census_ev)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(s->census_ev[0], s->stream));
+        const uint64_t per_block = (uint64_t)TXT_BLOCK * CENSUS_PER_THREAD;
+        hipLaunchKernelGGL(poly_census_kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(TXT_BLOCK), 0, s->stream, v.seq1, v.off1,
+                           v.len1, (const uint32_t*)s->t_name_off[0].p, (const uint32_t*)s->t_name_len[0].p, n, (int)poly_max, v.first_index,
+                           (aqc_census_hit*)s->census_hits.p, (unsigned long long*)s->census_n.p, s->status);
+        // (grid-strided over the hits, whose number only the device knows here: at most 4 workgroups per CU)
+        const uint64_t name_blocks = std::min<uint64_t>((n + TXT_BLOCK - 1) / TXT_BLOCK, (uint64_t)c->n_cu * 4);
+        hipLaunchKernelGGL(census_names_kernel, dim3((unsigned)name_blocks), dim3(TXT_BLOCK), 0, s->stream, v.seq1,
+                           (aqc_census_hit*)s->census_hits.p, (const unsigned long long*)s->census_n.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(s->census_ev[1], s->stream));
+    }
+    unsigned long long h = 0;
+    HIP_TRY(hipMemcpyAsync(&h, s->census_n.p, sizeof(h), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    rc = check_status(*s);
+    if (rc) return rc;
+    s->n_census = h;
+    *n_hits = h;
+    return 0;
+}
+
+int aqc_census_ms(aqc_ctx* c, int slot, float* ms) {
+    Slot* s;
+    int rc = get_slot(c, slot, &s);
+    if (rc) return rc;
+    if (!ms) return fail(AQC_ERR_ARG, "aqc_census_ms: null argument");
+    *ms = 0.f;
+    if (s->census_ev[1]) HIP_TRY(hipEventElapsedTime(ms, s->census_ev[0], s->census_ev[1]));
+    return 0;
+}
+
+int aqc_fetch_census(aqc_ctx* c, int slot, aqc_census_hit* dst, uint64_t cap) {
+    Slot* s;
+    int rc = get_slot(c, slot, &s);
+    if (rc) return rc;
+    if (!dst && cap) return fail(AQC_ERR_ARG, "aqc_fetch_census: null destination");
+    const uint64_t m = std::min(cap, s->n_census);
+    if (m) {
+        HIP_TRY(hipMemcpyAsync(dst, s->census_hits.p, sizeof(aqc_census_hit) * m, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
     }
     return 0;
 }

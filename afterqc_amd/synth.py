@@ -345,3 +345,50 @@ def write_fastq_fixed(path, seq, qual, mate=1, tile=1101):
             f.write(m.reshape(-1))
     finally:
         f.close()
+
+
+def make_census_text(n, L=150, seed=1007, mate=1, poly_frac=0.03, index0=0):
+    """Config-3 shaped FASTQ text for the debubble census (tools/census_bench.py, tests/test_gpu_debubble.py), rendered
+    without a Python loop: fixed-width records "@SIM:1:FC1:<lane>:<tile>:<x:05d>:<y:05d> <mate>:N:0:ACGT" with make_names's
+    lane / tile / x / y, uniform bases, and in `poly_frac` of the reads a run of 20 .. 60 of one of A / C / G / T at a random
+    place (the reads the census reports).  Returns the text as a numpy uint8 array."""
+    rng = np.random.default_rng([seed, index0])
+    lane, tile, x, y = make_names(rng, n)
+    head = b"@SIM:1:FC1:"
+    tail = (" %d:N:0:ACGT\n" % mate).encode()
+    nw = len(head) + 1 + 1 + 4 + 1 + 5 + 1 + 5 + len(tail)
+    W = nw + L + 1 + 2 + L + 1
+    a = np.empty((n, W), dtype=np.uint8)
+    a[:, :len(head)] = np.frombuffer(head, np.uint8)
+    p = len(head)
+    for v, digits in ((lane, 1), (None, 0), (tile, 4), (None, 0), (x, 5), (None, 0), (y, 5)):
+        if v is None:
+            a[:, p] = ord(":")
+            p += 1
+            continue
+        for k in range(digits):
+            a[:, p + k] = 48 + (v // 10 ** (digits - 1 - k)) % 10
+        p += digits
+    a[:, p:nw] = np.frombuffer(tail, np.uint8)
+    seq = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, (n, L), dtype=np.uint8)]
+    hit = np.flatnonzero(rng.random(n) < poly_frac)
+    run = rng.integers(20, 61, len(hit))
+    at = rng.integers(0, L - 60 + 1, len(hit))
+    base = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, len(hit))]
+    cols = np.arange(L)
+    mask = (cols[None, :] >= at[:, None]) & (cols[None, :] < (at + run)[:, None])
+    seq[hit] = np.where(mask, base[:, None], seq[hit])
+    a[:, nw:nw + L] = seq
+    a[:, nw + L] = 10
+    a[:, nw + L + 1] = ord("+")
+    a[:, nw + L + 2] = 10
+    a[:, nw + L + 3:nw + 2 * L + 3] = _quals(rng, (n, L))
+    a[:, W - 1] = 10
+    return a.reshape(-1)
+
+
+def write_census_file(path, n, L=150, seed=1007, mate=1, poly_frac=0.03, chunk=1_000_000):
+    """make_census_text in pieces of `chunk` reads, appended to `path` (plain text)"""
+    with open(path, "wb") as f:
+        for a in range(0, n, chunk):
+            f.write(make_census_text(min(chunk, n - a), L, seed, mate, poly_frac, index0=a).tobytes())

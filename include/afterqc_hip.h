@@ -358,6 +358,34 @@ int aqc_fetch_span_events(aqc_ctx* ctx, int slot, int file, aqc_span_event* dst,
 /* the chunk bytes of each file up to the end of record n - 1 of a framed slot (n == the slot's record count: consumed1 / consumed2):
  * where the last piece of an aqc_format_spans output ends when only the first n records are written */
 int aqc_span_end(aqc_ctx* ctx, int slot, uint64_t n, uint64_t end[2]);
+
+/* ---- debubble pre-pass: the polyX flowcell census (bubbleprocesser.py:348-397) ------------------- */
+/* For every record of a single-end slot filled by aqc_frame: countPoly(seq) with poly_max = K (the first of A, T, C, G with
+ * K of it in a row; count = the length of that base's first run of at least K), and for those reads the name fields of
+ * statFileFastq: re.search(r'\S+\:\d+\:\S+\:\d+\:\d+\:\d+\:\d+', name).group().split(':'), items[3..6] through int().
+ * One aqc_census_hit per polyX read, in NO particular order (sort by index).  A read longer than AQC_MAX_READ_LEN fails the
+ * call with AQC_ERR_READ_TOO_LONG.  poly_max >= 1. */
+#define AQC_CENSUS_OK 0       /* the record of bubbleprocesser.py:381 */
+#define AQC_CENSUS_NO_NAME 1  /* the name does not match: upstream's `continue` (:367-368) */
+#define AQC_CENSUS_RAISE 2    /* int() or tile_no[k] would raise upstream: tile_no shorter than 4 or not all digits, or
+                                 items[3] / [5] / [6] not [+-]?[0-9]+ */
+typedef struct aqc_census_hit {
+    uint64_t index;           /* first_index of the chunk + the record's place in it */
+    int64_t lane, tile_no, tile, x, y;
+    uint32_t name_off;        /* the name line in the chunk text (with its '@'), for fields the host finishes */
+    uint32_t name_len;
+    int32_t count;
+    uint8_t surface, swath, camera;
+    uint8_t base;             /* 'A' 'T' 'C' 'G' */
+    uint8_t status;           /* AQC_CENSUS_* */
+    uint8_t wide;             /* a field has more than 18 digits: its value here is 0, int() of the name bytes decides */
+    uint8_t pad_[6];
+} aqc_census_hit;
+int aqc_poly_census(aqc_ctx* ctx, int slot, int32_t poly_max, uint64_t* n_hits);
+/* copies min(cap, n_hits) hits of the slot's last aqc_poly_census into dst */
+int aqc_fetch_census(aqc_ctx* ctx, int slot, aqc_census_hit* dst, uint64_t cap);
+/* milliseconds of the slot's last census on the device (its two kernels, HIP events; 0 before the first one) */
+int aqc_census_ms(aqc_ctx* ctx, int slot, float* ms);
 /* AQC_FUSED=1 in the environment of aqc_create (opt-in): for 2 x <= 160 pairs framed by aqc_frame, without barcodes,
  * aqc_run's verdict kernel also places every record in its output stream and copies the good
  * records that go out as their own bytes; aqc_format(n = all records, store_overlap = 0) then only rebuilds the rest.  Same bytes
