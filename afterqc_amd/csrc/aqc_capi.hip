@@ -470,8 +470,8 @@ int aqc_reset_stats(aqc_ctx* c) {
         c->qc[k].epoch = 0;
         if (c->qc[k].kt.keys) {
             HIP_TRY(hipMemset(c->qc[k].kt.keys, 0, sizeof(unsigned long long) * KMER_CAP));
-            HIP_TRY(hipMemset(c->qc[k].kt.counts, 0, sizeof(unsigned long long) * KMER_CAP));
-            HIP_TRY(hipMemset(c->qc[k].kt.order, 0xff, sizeof(unsigned long long) * KMER_CAP));
+            HIP_TRY(hipMemset(c->qc[k].kt.counts, 0, sizeof(unsigned long long) * (KMER_CAP + 1)));
+            HIP_TRY(hipMemset(c->qc[k].kt.order, 0xff, sizeof(unsigned long long) * (KMER_CAP + 1)));
             HIP_TRY(hipMemset(c->qc[k].kt.dense_count, 0, sizeof(unsigned int) * DENSE_CAP));
             HIP_TRY(hipMemset(c->qc[k].kt.dense_first, 0xff, sizeof(unsigned long long) * DENSE_CAP));
             HIP_TRY(hipMemset(c->qc[k].kt.complete, 0, sizeof(unsigned int) * (DENSE_ENTRIES / KRED_ENTRIES)));
@@ -706,11 +706,11 @@ int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
 static int ensure_kmer(aqc_ctx* c, QcDev& q) {
     if (q.kt.keys) return 0;
     HIP_TRY(hipMalloc((void**)&q.kt.keys, sizeof(unsigned long long) * KMER_CAP));
-    HIP_TRY(hipMalloc((void**)&q.kt.counts, sizeof(unsigned long long) * KMER_CAP));
-    HIP_TRY(hipMalloc((void**)&q.kt.order, sizeof(unsigned long long) * KMER_CAP));
+    HIP_TRY(hipMalloc((void**)&q.kt.counts, sizeof(unsigned long long) * (KMER_CAP + 1)));      // (+1: the all-NUL k-mer, see kmer_slot)
+    HIP_TRY(hipMalloc((void**)&q.kt.order, sizeof(unsigned long long) * (KMER_CAP + 1)));
     HIP_TRY(hipMemset(q.kt.keys, 0, sizeof(unsigned long long) * KMER_CAP));
-    HIP_TRY(hipMemset(q.kt.counts, 0, sizeof(unsigned long long) * KMER_CAP));
-    HIP_TRY(hipMemset(q.kt.order, 0xff, sizeof(unsigned long long) * KMER_CAP));
+    HIP_TRY(hipMemset(q.kt.counts, 0, sizeof(unsigned long long) * (KMER_CAP + 1)));
+    HIP_TRY(hipMemset(q.kt.order, 0xff, sizeof(unsigned long long) * (KMER_CAP + 1)));
     q.kt.mask = KMER_CAP - 1;
     HIP_TRY(hipMalloc((void**)&q.kt.dense_count, sizeof(unsigned int) * DENSE_CAP));
     HIP_TRY(hipMalloc((void**)&q.kt.dense_first, sizeof(unsigned long long) * DENSE_CAP));
@@ -2356,14 +2356,14 @@ int aqc_get_kmers(aqc_ctx* c, int which, uint64_t* keys, int64_t* counts, uint64
     *n = 0;
     QcDev& q = c->qc[which];
     if (!q.kt.keys) return 0;
-    const uint64_t dcap = cap < KMER_CAP + DENSE_CAP ? cap : KMER_CAP + DENSE_CAP;
+    const uint64_t dcap = cap < KMER_CAP + 1 + DENSE_CAP ? cap : KMER_CAP + 1 + DENSE_CAP;
     unsigned long long *dk = nullptr, *dc = nullptr, *dord = nullptr, *dn = nullptr;
     HIP_TRY(hipMalloc((void**)&dk, 8 * (dcap + 1)));
     HIP_TRY(hipMalloc((void**)&dc, 8 * (dcap + 1)));
     HIP_TRY(hipMalloc((void**)&dord, 8 * (dcap + 1)));
     HIP_TRY(hipMalloc((void**)&dn, 8));
     HIP_TRY(hipMemset(dn, 0, 8));
-    hipLaunchKernelGGL(kmer_compact_kernel, dim3((unsigned)(KMER_CAP / 256)), dim3(256), 0, 0, q.kt, dk, dc, dord,
+    hipLaunchKernelGGL(kmer_compact_kernel, dim3((unsigned)(KMER_CAP / 256 + 1)), dim3(256), 0, 0, q.kt, dk, dc, dord,
                        (unsigned long long)dcap, dn);
     hipLaunchKernelGGL(kmer_compact_dense_kernel, dim3((unsigned)(DENSE_ENTRIES / 256)), dim3(256), 0, 0, q.kt, c->cfg.qc_kmer, dk, dc,
                        dord, (unsigned long long)dcap, dn);

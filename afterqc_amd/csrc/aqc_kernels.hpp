@@ -797,8 +797,8 @@ __global__ __launch_bounds__(BLOCK) void filter_overlap_list_kernel(DevBatch b, 
 struct KmerTable {
     // open-addressing table for k-mers containing anything but A,C,G,T (rare): keyed by the k raw bytes
     unsigned long long* keys;    // 0 = empty
-    unsigned long long* counts;
-    unsigned long long* order;   // min over 2*t (seen) / 2*t+1 (inserted as reverse complement)
+    unsigned long long* counts;  // [capacity + 1]: entry `capacity` belongs to the all-NUL k-mer, whose key is 0 (see kmer_slot)
+    unsigned long long* order;   // [capacity + 1] min over 2*t (seen) / 2*t+1 (inserted as reverse complement)
     uint64_t mask;               // capacity - 1
     // dense tables for pure A/C/G/T k-mers, 4^k entries.  Index = (bit-1 plane << k) | bit-0 plane of the
     // per-base code (c >> 1) & 3 (A=0 C=1 T=2 G=3); base j of the k-mer sits at bit j of each plane.
@@ -834,7 +834,11 @@ __device__ __forceinline__ uint64_t hash64(uint64_t x) {
     return x;
 }
 
+// Key 0 marks an empty slot, and it is also the key of the k-mer of k NUL bytes (a zero-filled block of a damaged
+// file): that k-mer gets the dedicated entry mask + 1 of counts / order, and never claims a slot.  (No spare key
+// value exists to remap it to: for k = 8 every 64-bit value is some k-mer's key.)
 __device__ inline long long kmer_slot(const KmerTable& t, unsigned long long key) {
+    if (key == 0) return (long long)(t.mask + 1);
     uint64_t h = hash64(key) & t.mask;
     for (uint64_t probe = 0; probe <= t.mask; probe++) {
         unsigned long long cur = t.keys[h];
@@ -854,8 +858,8 @@ __device__ __forceinline__ void kmer_slot2(const KmerTable& t, unsigned long lon
                                            long long& h, long long& hr) {
     const uint64_t a = hash64(key) & t.mask, b = hash64(rkey) & t.mask;
     const unsigned long long ka = t.keys[a], kb = t.keys[b];
-    h = ka == key ? (long long)a : kmer_slot(t, key);
-    hr = kb == rkey ? (long long)b : kmer_slot(t, rkey);
+    h = ka == key && key != 0 ? (long long)a : kmer_slot(t, key);
+    hr = kb == rkey && rkey != 0 ? (long long)b : kmer_slot(t, rkey);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1013,8 +1017,10 @@ constexpr uint32_t CODE_TO_BASE = 0x47544341u;   // 2-bit code (c >> 1) & 3 -> '
 // Per-cycle accumulators of statRead (qualitycontrol.py:73-111).  A lane owns FOUR consecutive cycles of the
 // read: one unaligned dword of bases and one of qualities live in registers (no LDS staging), the neighbours'
 // dwords come over the wave for the 5-wide discontinuity window, and a base's count and quality sum travel in
-// ONE LDS atomic (count << 20 | quality sum; at most 4095 reads per workgroup).  total_num / total_qual are
-// column sums of the five rows (A T C G other), formed when the workgroup flushes.
+// ONE LDS atomic (count << 20 | sum of the RAW quality bytes; at most 4095 reads per workgroup, 4095 * 255 < 2^20).
+// The flush subtracts 33 per count: qualNum is ord(q) - 33 for any byte (util.py:39-40), so a control byte or a
+// space inside a quality line is a negative quality upstream, and a per-byte "q - '!'" would borrow from the next
+// field.  total_num / total_qual are column sums of the five rows (A T C G other), formed when the workgroup flushes.
 // ------------------------------------------------------------------------------------------------
 constexpr int QC_BLOCK = 1024;
 constexpr int QC_WPB = QC_BLOCK / WAVE;
@@ -1063,8 +1069,8 @@ __device__ __forceinline__ void qc_accumulate_read(const ReadDesc& cur, uint32_t
         const int tl = len - 3 - base0;                 // cycle len-3 relative to this pass (uniform)
         if (tl >= 0 && tl < 4 * WAVE)
             d_tail = ((unsigned int)__builtin_amdgcn_readlane((int)dpk, tl >> 2) >> (3 * (tl & 3))) & 7u;
-        // the lane's four cycles at once: accumulator row per base (A T C G = 0..3, anything else 4), quality - 33 per
-        // byte, the clamped discontinuity windows patched into the packed fields; then per cycle only two field
+        // the lane's four cycles at once: accumulator row per base (A T C G = 0..3, anything else 4), raw quality byte
+        // per cycle, the clamped discontinuity windows patched into the packed fields; then per cycle only two field
         // extractions, one multiply-add for the address and the atomics remain
         if (base0 == 0 && lane == 0) dpk = (dpk & ~0x3fu) | d_head | (d_head << 3);     // cycles 0, 1: window [0, 5)
         {
@@ -1090,7 +1096,6 @@ __device__ __forceinline__ void qc_accumulate_read(const ReadDesc& cur, uint32_t
         const uint32_t foreign = nz | (nz - (nz >> 7));                                 // 0xff per foreign byte
         // code (A0 C1 T2 G3) -> row (A0 T1 C2 G3); foreign -> 4
         const uint32_t rows4 = (__builtin_amdgcn_perm(0u, 0x03010200u, codes) & ~foreign) | (0x04040404u & foreign);
-        const uint32_t qn4 = wq - 0x21212121u;                                          // (qualities are >= '!' in FASTQ)
         const int nin = min(max(len - x, 0), 4);                                        // cycles of this lane inside the read
         const unsigned int col0 = (unsigned int)lane + (unsigned int)(base0 >> 2);
         // G / C among the lane's cycles inside the read (C = code 1, G = code 3: low code bit), not foreign
@@ -1099,7 +1104,7 @@ __device__ __forceinline__ void qc_accumulate_read(const ReadDesc& cur, uint32_t
         for (int j = 0; j < 4; ++j) {
             if (j < nin) {
                 const unsigned int row = (rows4 >> (8 * j)) & 0xffu;
-                atomicAdd(&accs[row * (unsigned int)cols + (unsigned int)(j * cq) + col0], (1u << 20) + ((qn4 >> (8 * j)) & 0xffu));
+                atomicAdd(&accs[row * (unsigned int)cols + (unsigned int)(j * cq) + col0], (1u << 20) + ((wq >> (8 * j)) & 0xffu));
                 // discontinuity over the 5-wide window clamped to the read (qualitycontrol.py:97-109)
                 const unsigned int d = (dpk >> (3 * j)) & 7u;
                 if (d) atomicAdd(&accs[5u * (unsigned int)cols + (unsigned int)(j * cq) + col0], d);
@@ -1179,7 +1184,7 @@ __global__ __launch_bounds__(QC_BLOCK) void qc_stat_kernel(DevBatch b, int mate,
 #pragma unroll
         for (int row = 0; row < 5; ++row) {
             const unsigned int v = accs[row * cols + ci];
-            const unsigned long long cnt = v >> 20, qs = v & 0xfffffu;
+            const unsigned long long cnt = v >> 20, qs = (v & 0xfffffu) - 33ull * cnt;   // raw byte sum -> sum of qualNum (mod 2^64)
             if (row < 4 && v) {
                 atomicAdd(&qc[(AQC_QC_BASE_COUNT_A + row) * AQC_QC_COLS + i], cnt);
                 atomicAdd(&qc[(AQC_QC_BASE_QUAL_A + row) * AQC_QC_COLS + i], qs);
@@ -1420,7 +1425,7 @@ __global__ __launch_bounds__(KMER_BLOCK) void kmer_count_kernel(DevBatch b, int 
 #pragma unroll
             for (int row = 0; row < 5; ++row) {
                 const unsigned int v = q_accs[row * cols + ci];
-                const unsigned long long cnt = v >> 20, qs = v & 0xfffffu;
+                const unsigned long long cnt = v >> 20, qs = (v & 0xfffffu) - 33ull * cnt;   // raw byte sum -> sum of qualNum (mod 2^64)
                 if (row < 4 && v) {
                     atomicAdd(&qc[(AQC_QC_BASE_COUNT_A + row) * AQC_QC_COLS + i], cnt);
                     atomicAdd(&qc[(AQC_QC_BASE_QUAL_A + row) * AQC_QC_COLS + i], qs);
@@ -1468,13 +1473,13 @@ __global__ __launch_bounds__(KRED_BLOCK) void kmer_reduce_kernel(const uint16_t*
     }
 }
 
-// compact the occupied k-mer slots into dense arrays
+// compact the occupied k-mer slots into dense arrays (i = mask + 1: the all-NUL k-mer's entry, present once its order is set)
 __global__ void kmer_compact_kernel(KmerTable kt, unsigned long long* keys, unsigned long long* counts,
                                     unsigned long long* order, unsigned long long cap, unsigned long long* n_out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > kt.mask) return;
-    const unsigned long long key = kt.keys[i];
-    if (key == 0) return;
+    if (i > kt.mask + 1) return;
+    const unsigned long long key = i > kt.mask ? 0ull : kt.keys[i];
+    if (i > kt.mask ? kt.order[i] == ~0ull : key == 0) return;
     const unsigned long long w = atomicAdd(n_out, 1ull);
     if (w < cap) { keys[w] = key; counts[w] = kt.counts[i]; order[w] = kt.order[i]; }
 }

@@ -556,6 +556,44 @@ int orc_qc_stat_read(orc_qc* qc, const uint8_t* seq, const uint8_t* qual, int se
     return 0;
 }
 
+/* OracleEngine.qc_stat over a range of a batch in one call (the per-read Python loop is what is slow at a million reads): the
+ * same orc_qc_stat_read per read with the same time keys.  results != NULL: the post-filter reads, each the way its result
+ * record leaves it (oracle.py final_read: the GOOD ones only, trim extents, then the edits in order).  Records whose quality line
+ * has a length of its own are not taken here (the batch must have no qlen arrays). */
+int orc_qc_stat_range(orc_qc* qc, const aqc_batch* b, int mate, uint64_t first, uint64_t count, const aqc_result* results,
+                      uint64_t epoch) {
+    if (mate ? b->qlen2 != 0 : b->qlen1 != 0) return AQC_ERR_ARG;
+    uint8_t s[AQC_MAX_READ_LEN], q[AQC_MAX_READ_LEN];
+    const uint64_t* off = mate ? b->off2 : b->off1;
+    const uint64_t* qoff = mate ? (b->qoff2 ? b->qoff2 : b->off2) : (b->qoff1 ? b->qoff1 : b->off1);
+    for (uint64_t i = first; i < first + count && i < b->n; i++) {
+        const uint8_t* seq = (mate ? b->seq2 : b->seq1) + off[i];
+        const uint8_t* qual = (mate ? b->qual2 : b->qual1) + qoff[i];
+        int len = (int)(mate ? b->len2[i] : b->len1[i]);
+        if (results) {
+            const aqc_result* r = &results[i];
+            if (r->flag != AQC_GOOD) continue;
+            const int st = mate ? r->start2 : r->start1;
+            int ln = mate ? r->len2 : r->len1;
+            if (st + ln > len) ln = st < len ? len - st : 0;       /* (a Python slice stops at the end) */
+            if (ln > AQC_MAX_READ_LEN) return AQC_ERR_READ_TOO_LONG;
+            memcpy(s, seq + st, (size_t)ln);
+            memcpy(q, qual + st, (size_t)ln);
+            for (int k = 0; k < r->n_edits; k++) {
+                const aqc_edit* e = &r->edits[k];
+                const int p = mate ? ln - 1 - (int)e->o : ln - (int)r->overlap_len + (int)e->o;
+                if (p < 0 || p >= ln) return AQC_ERR_STATE;
+                if (e->kind == AQC_EDIT_MASK) q[p] = '!';
+                else if ((e->kind == AQC_EDIT_FIX_R1 && !mate) || (e->kind == AQC_EDIT_FIX_R2 && mate)) { s[p] = e->base; q[p] = e->qual; }
+            }
+            seq = s; qual = q; len = ln;
+        }
+        const int rc = orc_qc_stat_read(qc, seq, qual, len, (epoch << 44) | ((b->first_index + i) << 10));
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 void orc_qc_get(const orc_qc* qc, int64_t* out) { memcpy(out, qc->acc, sizeof(qc->acc)); }
 
 uint64_t orc_qc_kmer_count(const orc_qc* qc) { return qc->n; }

@@ -45,6 +45,7 @@ def lib():
         L.orc_qc_free.argtypes = [P]
         L.orc_qc_free.restype = None
         L.orc_qc_stat_read.argtypes = [P, P, P, C.c_int, C.c_uint64]
+        L.orc_qc_stat_range.argtypes = [P, C.POINTER(capi.BatchStruct), C.c_int, C.c_uint64, C.c_uint64, P, C.c_uint64]
         L.orc_qc_get.argtypes = [P, P]
         L.orc_qc_get.restype = None
         L.orc_qc_kmer_count.argtypes = [P]
@@ -207,6 +208,18 @@ class OracleEngine:
         if g0 < self._qc_last_end[which]:
             self._qc_epoch[which] += 1
         self._qc_last_end[which] = g0 + count
+        epoch = self._qc_epoch[which]
+        if (b.qlen2 if r2 else b.qlen1) is None:
+            # the whole range in C (orc_qc_stat_range: the loop below, same reads, same time keys)
+            s = b.as_struct()
+            rp = None
+            if post:
+                res = np.ascontiguousarray(res)
+                rp = res.ctypes.data
+            rc = lib().orc_qc_stat_range(qc.h, C.byref(s), 1 if r2 else 0, first, count, rp, epoch)
+            if rc != 0:
+                raise capi.AqcError(rc, "oracle qc_stat")
+            return
         for i in range(first, min(first + count, b.n)):
             seq, qual = b.read2(i) if r2 else b.read1(i)
             if post:

@@ -193,3 +193,22 @@ def test_fused_contexts_sharing_one_device_through_the_pipe(tmp_path):
     chunks, fused_chunks = b.timing["pipe_chunks"]
     assert chunks >= n // 20000 and fused_chunks == chunks, (chunks, fused_chunks)       # (no pair of this input is deferred)
     assert a.timing["pipe_chunks"][1] == 0
+
+
+@pytest.mark.parametrize("L", [160, 161])
+def test_fused_placement_at_its_length_edge(L, gpu_engine, fused_engine):
+    """the verdict kernel places the records itself up to 2 x 160 bases: at 160 it must, at 161 it must not — same bytes either way"""
+    d = synth.make_pairs(3000, L, seed=7400 + L, short_frac=0.0)      # (no adapter read-through: no pair for the general kernel)
+    t1, t2 = [b"".join(b"@SIM:1:FC:1:1101:%d:%d %d:N:0:ACGT\n" % (1000 + i, 2000 + i, mate) + sq[i].tobytes() + b"\n+\n" + ql[i].tobytes()
+                       + b"\n" for i in range(len(sq)))
+              for mate, (sq, ql) in enumerate(((d["seq1"], d["qual1"]), (d["seq2"], d["qual2"])), 1)]
+    n_a, want, cnt_a, _ = six_streams(gpu_engine, t1, t2, cfg_default())
+    n_b, got, cnt_b, deferred = six_streams(fused_engine, t1, t2, cfg_default())
+    assert n_a == n_b == 3000
+    if L <= 160:
+        assert deferred == 0 and fused_engine.format_fused(0)
+    else:
+        assert not fused_engine.format_fused(0)
+    for q in range(6):
+        assert got[q] == want[q], (L, q, len(got[q]), len(want[q]))
+    assert (cnt_a == cnt_b).all()

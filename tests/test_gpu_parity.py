@@ -404,3 +404,39 @@ def test_qc_stat_from_two_threads(gpu_engine):
             assert np.array_equal(acc_r, acc_g)
             for a, c in zip(km_r, km_g):
                 assert np.array_equal(a, c)
+
+
+# ---- verdict kernel tiers (aqc_capi.hip: <= 160 bases 10 words, <= 256 16 words, <= 288 18 words, else the general kernel) -----
+@pytest.mark.parametrize("barcode", [False, True])
+@pytest.mark.parametrize("paired", [True, False])
+@pytest.mark.parametrize("max_len", [160, 161, 256, 257, 288, 289])
+def test_tier_edges_vs_oracle(gpu_engine, max_len, paired, barcode):
+    """each side of every tier edge, paired / single x barcode off / on, with QC: for barcode on the raw length includes the
+    12 + 5 base prefix"""
+    n = 2000 if max_len <= 200 else 1200
+    L = max_len - 17 if barcode else max_len
+    d = synth.make_pairs(n, L, seed=3300 + max_len + 7 * paired + 3 * barcode, dirty=True)
+    if barcode:
+        d = synth.add_barcodes(d, 3301 + max_len, tail_frac=0.1)
+    assert d["seq1"].shape[1] == max_len
+    if paired:
+        batch = capi.Batch.from_matrices(d["seq1"], d["qual1"], d["len1"], d["seq2"], d["qual2"], d["len2"])
+    else:
+        batch = capi.Batch.from_matrices(d["seq1"], d["qual1"], d["len1"])
+    assert batch.max_len() == max_len
+    g, o = run_both(gpu_engine, default_cfg(paired, barcode=1 if barcode else 0), batch)
+    assert_same(g, o)
+    assert (g["res"]["flag"] == capi.GOOD).sum() > n // 4
+
+
+@pytest.mark.parametrize("long_len", [161, 257, 289])
+def test_one_long_record_decides_the_tier(gpu_engine, long_len):
+    """150-base pairs and ONE record of long_len bases: the batch's max_len moves every record to the wider variant"""
+    d = synth.make_pairs(3000, long_len, seed=3400 + long_len, dirty=True)
+    for m in ("1", "2"):
+        d["len" + m][:] = np.minimum(d["len" + m], 150)
+        d["len" + m][1234] = long_len
+    batch = capi.Batch.from_matrices(d["seq1"], d["qual1"], d["len1"], d["seq2"], d["qual2"], d["len2"])
+    assert batch.max_len() == long_len
+    g, o = run_both(gpu_engine, default_cfg(True), batch)
+    assert_same(g, o)
