@@ -14,7 +14,9 @@ verdict records come back.  This module is I/O and bookkeeping:
               the host (SURVEY.md §8e);
             * serial chunk loop in this file (_run_text / _run_text_indexed): index files, --qc_only, inputs of
               irregular shape (the pipe reports them), injected engines;
-          the host path (_run_host: numpy framing, Python writer) only exists as a cross-check (use_text_path=False)
+          the host path (_run_host: numpy framing, Python writer) only exists as a cross-check (use_text_path=False);
+          the three serial drivers state upstream's loop rules once: lock_step (which reader ends the loop) and
+          seqFilter._judge (the loop body: --qc_only, the post-filter sampling window, death at a record)
   stats   counters -> JSON with the reference's schema  (preprocesser.py:660-778)
 
 There is no CPU compute path: `engine` defaults to the HIP engine, which raises if the library or
@@ -25,6 +27,7 @@ import os
 import sys
 import queue
 import threading
+import time
 
 import numpy as np
 
@@ -51,6 +54,10 @@ COMMAND_KEYS = ("index2_flag", "draw", "barcode", "index1_flag", "seq_len_req", 
                 "unqualified_base_limit", "allow_mismatch_in_poly", "input_dir", "read1_file", "read2_flag",
                 "store_overlap", "debubble", "read1_flag", "trim_front2", "bad_output_folder", "qc_only", "qc_sample",
                 "qc_kmer")
+
+
+def input_files(opt):
+    return [opt.read1_file, opt.read2_file, opt.index1_file, opt.index2_file]
 
 
 def makeDict(opt):
@@ -94,23 +101,13 @@ def build_config(opt, paired, has_index2):
 
 
 class _Outputs:
-    """The good / bad / overlap writers of preprocesser.py:323-371 for up to four input files."""
+    """The good / bad / overlap writers of preprocesser.py:323-371 for up to four input files, opened at the paths
+    seqFilter._layout gives (None: not written; a gzip output carries its .gz in the name, which fastq.Writer goes by)."""
 
-    def __init__(self, opt, files, good_dir, bad_dir, overlap_dir, gzip_out, gzip_comp):
-        self.good, self.bad, self.overlap = [], [], []
-        store = opt.store_overlap and opt.read2_file is not None
-        for f in files:
-            if f is None or opt.qc_only:
-                self.good.append(None); self.bad.append(None); self.overlap.append(None)
-                continue
-            main = getMainName(f)
-            self.good.append(fastq.Writer(os.path.join(good_dir, main + ".good.fq"), gzip_out, gzip_comp))
-            self.bad.append(fastq.Writer(os.path.join(bad_dir, main + ".bad.fq"), gzip_out, gzip_comp))
-            # upstream opens the R1 overlap writer whenever store_overlap is on, the others only when paired
-            if (opt.store_overlap and f == files[0]) or store:
-                self.overlap.append(fastq.Writer(os.path.join(overlap_dir, main + ".overlap.fq"), gzip_out, gzip_comp))
-            else:
-                self.overlap.append(None)
+    def __init__(self, paths, gzip_comp):
+        opened = [[None if p is None else fastq.Writer(p, False, gzip_comp) for p in per_file] for per_file in paths]
+        self.good, self.bad, self.overlap = ([w[q] for w in opened] for q in range(3))
+        self.per_file = [tuple(w) for w in opened]
 
     def close(self):
         for group in (self.good, self.bad, self.overlap):
@@ -233,14 +230,8 @@ class _TextSink:
 
             def fetch_all(sizes):
                 for q, nbytes in enumerate(sizes):
-                    if q // 3 >= len(self.writers) or nbytes == 0 or self.writers[q // 3][q % 3] is None:
-                        continue
-                    buf = self.sets[which][q]
-                    if buf is None or buf.nbytes < nbytes:
-                        if buf is not None:
-                            buf.free()
-                        buf = self.sets[which][q] = self.eng.host_buffer(nbytes + nbytes // 4 + 4096)
-                    self.eng.fetch_text(slot, q // 3, q % 3, buf.array, buf.nbytes)
+                    if q // 3 < len(self.writers) and nbytes and self.writers[q // 3][q % 3] is not None:
+                        fetch_stream(self.eng, slot, q, nbytes, self.sets[which])
 
             try:
                 self.set_free[which].acquire()           # the writer is done with this buffer set
@@ -319,6 +310,52 @@ def death_record(eng, slot, e):
     return None
 
 
+def fetch_stream(eng, slot, q, nbytes, bufs):
+    """stream q (= file * 3 + stream) of the slot's formatted text -> the page-locked buffer bufs[q], which grows to take it"""
+    buf = bufs[q]
+    if buf is None or buf.nbytes < nbytes:
+        if buf is not None:
+            buf.free()
+        buf = bufs[q] = eng.host_buffer(nbytes + nbytes // 4 + 4096)
+    eng.fetch_text(slot, q // 3, q % 3, buf.array, buf.nbytes)
+    return buf
+
+
+def frame_inputs(eng, slot, inputs, fills, cur, first_index, cap=capi.UINT64_MAX):
+    """aqc_frame over buffer `cur` of one or two lock-stepped inputs (fills: per input (bytes in the buffer, the file ends
+    there)) -> (info, per input (records available, an empty line ended the file (fastq.py:44-47), the file ends in this
+    buffer, bytes consumed, bytes in the buffer))"""
+    args = []
+    for inp, (nbytes, final) in zip(inputs, fills):
+        args += [inp.bufs[cur].array, nbytes, final]
+    info = eng.frame(slot, *args, max_records=cap, first_index=first_index)
+    framed = [(int(info.avail1), bool(info.eof1), int(info.consumed1)), (int(info.avail2), bool(info.eof2), int(info.consumed2))]
+    return info, [(avail, eof, final, consumed, nbytes) for (avail, eof, consumed), (nbytes, final) in zip(framed, fills)]
+
+
+def lock_step(state, info):
+    """The reference reads one record of every input per turn, R1 first, and the first reader that returns None ends the
+    loop (preprocesser.py:412-429).  state: per input, R1 first, frame_inputs' (avail, eof_seen, final_fill, ...); info: the
+    reads' frame info — n, the records this chunk gives every input, and next_len1, the length of R1's record n.
+    -> (stop, extra_bases, per input: nothing after this chunk is ever read from it)"""
+    n = int(info.n)
+    done = [(eof or final) and avail == n for avail, eof, final, *_ in state]
+    if done[0]:
+        return True, 0, done
+    if any(done[1:]) and state[0][0] > n:
+        # R1's next record was read (and counted into TOTAL_BASES, :416) before another reader ran dry
+        return True, int(info.next_len1), done
+    return False, 0, [s[1] or (k != 0 and done[k]) for k, s in enumerate(state)]
+
+
+def advance(inputs, cur, n, state, finished):
+    """every input goes on to its next chunk: what framing left of buffer `cur` is carried to the front of the other one"""
+    for inp, (avail, eof, final, consumed, nbytes), fin in zip(inputs, state, finished):
+        if n == 0 and not final and not eof and avail == 0:
+            inp.grow(cur)                                  # not even one record fits the buffer
+        inp.carry(cur, consumed, nbytes, final, fin)
+
+
 class seqFilter:
     """seqFilter(options).run() — preprocesser.py:141-155,234-783."""
 
@@ -377,172 +414,31 @@ class seqFilter:
 
     # ---- the run -----------------------------------------------------------------------------------
     def run(self):
-        import time
         opt = self.options
         t_init = time.perf_counter()
         eng = self._engine()
-        t_init = time.perf_counter() - t_init        # (a fresh process: HIP runtime start + the library's code object)
-        paired = self.paired
+        self.timing = {"init_s": time.perf_counter() - t_init}       # (a fresh process: HIP runtime start + the library's code object)
+        t_run = time.perf_counter()
         if opt.debubble:
             self.bubbleCircles = load_circles(opt.debubble_dir)
         # no front trim if the sequence is barcoded (preprocesser.py:242-243)
         if opt.barcode:
             opt.trim_front = 0
-
-        self.timing = {"init_s": t_init}
-        t_run = time.perf_counter()
-        has_i1 = opt.index1_file is not None
-        has_i2 = opt.index2_file is not None
-        self._last_cfg = (build_config(opt, paired, has_i2), self.bubbleCircles)
-        for e in self._engines():
-            e.set_config(self._last_cfg[0])
-            e.set_circles(self.bubbleCircles)
-            e.reset_stats()
-
-        # ---- pass 1: pre-filter QC on a sample of each file (preprocesser.py:247-251)
-        r1pre = QualityControl(opt.qc_sample, opt.qc_kmer, eng, capi.QC_R1_PRE)
-        r2pre = QualityControl(opt.qc_sample, opt.qc_kmer, eng, capi.QC_R2_PRE)
-        r1post = QualityControl(opt.qc_sample, opt.qc_kmer, eng, capi.QC_R1_POST)
-        r2post = QualityControl(opt.qc_sample, opt.qc_kmer, eng, capi.QC_R2_POST)
-        single = lambda rb: capi.Batch.from_raw(rb)
-        if self.use_text_path and hasattr(eng, "frame"):
-            side, side_err = None, []
-            if paired and isinstance(eng, capi.Engine) and eng.n_slots >= 2:
-                # read 2 is sampled at the same time in slot 1 (a .gz spends most of this pass decoding)
-                def _sample_r2():
-                    try:
-                        r2pre.statFileText(opt.read2_file, self.chunk_bytes, slot=1)
-                    except BaseException as e:       # re-raised on the main thread
-                        side_err.append(e)
-                side = threading.Thread(target=_sample_r2, name="aqc-sample-r2")
-                side.start()
-            try:
-                r1pre.statFileText(opt.read1_file, self.chunk_bytes)
-            finally:
-                if side is not None:
-                    side.join()
-            if side_err:
-                raise side_err[0]
-            if paired and side is None:
-                r2pre.statFileText(opt.read2_file, self.chunk_bytes)
-        else:
-            r1pre.statFile(opt.read1_file, fastq.Reader, single, self.batch_records)
-            if paired:
-                # the R2 file is stat'd through the same single-read path into its own accumulator
-                r2pre.statFile(opt.read2_file, fastq.Reader, single, self.batch_records)
-        readLen = r1pre.readLen
+        self._configure(first=True)
+        r1pre, r2pre = self._sample(eng)
         self.timing["pass1_s"] = time.perf_counter() - t_run
-
-        # ---- auto trim (preprocesser.py:261-280)
-        if opt.trim_front == -1 or opt.trim_tail == -1:
-            tf, tt = r1pre.autoTrim()
-            if opt.trim_front == -1:
-                opt.trim_front = tf
-            if opt.trim_tail == -1:
-                opt.trim_tail = tt
-            if paired:
-                if opt.trim_pair_same:
-                    opt.trim_front2 = opt.trim_front
-                    opt.trim_tail2 = opt.trim_tail
-                else:
-                    tf2, tt2 = r2pre.autoTrim()
-                    if opt.trim_front2 == -1:
-                        opt.trim_front2 = tf2
-                    if opt.trim_tail2 == -1:
-                        opt.trim_tail2 = tt2
+        self._auto_trim(r1pre, r2pre)
         print(opt.read1_file + " options:")
         print(opt)
-
-        # ---- output layout (preprocesser.py:285-321)
-        good_dir = opt.good_output_folder
-        if good_dir is None:
-            good_dir = os.path.dirname(opt.read1_file)
-        parent = os.path.dirname(os.path.dirname(good_dir + "/"))
-        bad_dir = opt.bad_output_folder if opt.bad_output_folder is not None else os.path.join(parent, "bad")
-        overlap_dir = opt.overlap_output_folder if opt.overlap_output_folder is not None else os.path.join(parent, "overlap")
-        qc_dir = opt.report_output_folder if opt.report_output_folder is not None else os.path.join(parent, "QC")
-        for d in (qc_dir, good_dir, bad_dir):
-            os.makedirs(d, exist_ok=True)          # (directory mode runs several files at once)
-        if opt.store_overlap and paired:
-            os.makedirs(overlap_dir, exist_ok=True)
-        gzip_out = bool(opt.gzip) or opt.read1_file.endswith(".gz")
-        files = [opt.read1_file, opt.read2_file, opt.index1_file, opt.index2_file]
-        if opt.store_overlap and not opt.qc_only:
-            os.makedirs(overlap_dir, exist_ok=True)   # single-end + store_overlap: upstream opens the writer without the dir
-        # ---- pass 2: the main loop (preprocesser.py:411-631)
-        # the per-read settings now include the resolved trim values
-        self._last_cfg = (build_config(opt, paired, has_i2), self.bubbleCircles)
-        for e in self._engines():
-            e.set_config(self._last_cfg[0])
-        # text in / text out on the device (aqc_frame / aqc_format); use_text_path=False keeps the host-side framing and
-        # writer below as a cross-check.  An injected engine without the text calls takes the host path.
-        self.text_path = self.use_text_path and hasattr(eng, "frame")
+        qc_dir, gzip_out, paths = self._layout()
+        self._configure()                            # the per-read settings now include the resolved trim values
         t_p2 = time.perf_counter()
         cpu_p2 = sum(os.times()[:2])
-        outs = None
-        extra_bases = None
-        readers = []
-        if self.text_path and self.use_pipe and not (has_i1 or has_i2) and not opt.qc_only and isinstance(eng, capi.Engine):
-            extra_bases = self._run_pipe(opt, files, good_dir, bad_dir, overlap_dir, gzip_out, paired)
-            if extra_bases is None:
-                # not the regular shape (empty line inside, mates of different lengths, ...): start over, chunk by chunk
-                print("afterqc_amd: %s is not of the regular shape the whole-input pipe takes (blank line inside / mates of "
-                      "different lengths); running it again through the serial chunk loop" % opt.read1_file, file=sys.stderr)
-                self.timing["pipe_fallback"] = True
-                for e in self._engines():
-                    e.reset_stats()
-        try:
-            if extra_bases is not None:
-                pass
-            elif self.text_path and (has_i1 or has_i2):
-                outs = _Outputs(opt, files, good_dir, bad_dir, overlap_dir, gzip_out, opt.compression)
-                extra_bases = self._run_text_indexed(eng, opt, outs, paired)
-            elif self.text_path:
-                outs = _Outputs(opt, files, good_dir, bad_dir, overlap_dir, gzip_out, opt.compression)
-                extra_bases = self._run_text(eng, opt, outs, paired)
-            else:
-                outs = _Outputs(opt, files, good_dir, bad_dir, overlap_dir, gzip_out, opt.compression)
-                readers, extra_bases = self._run_host(eng, opt, outs, paired, files)
-        finally:
-            # (also when the run ends in an exception: what was written up to the record upstream dies at stays written)
-            for r in readers:
-                if r is not None:
-                    r.close()
-            if outs is not None:
-                outs.close()
+        extra_bases = self._pass2(eng, paths, gzip_out)
         self.timing["pass2_s"] = time.perf_counter() - t_p2
         self.timing["pass2_cpu_s"] = sum(os.times()[:2]) - cpu_p2          # user + system, all threads: how many cores pass 2 kept busy
-
-        t_stats = time.perf_counter()
         try:
-            # statistics: per-GPU integers summed on the host (only the pipe spreads a run over several engines)
-            stat_eng = capi.MergedEngines(self._engines()) if self.extra_engines else eng
-            r1post.engine = r2post.engine = stat_eng
-            r1post.qc()
-            if paired:
-                r2post.qc()
-
-            self.stat = self._stats(stat_eng, r1pre, r2pre, r1post, r2post, readLen, extra_bases)
-            stat_path = os.path.join(qc_dir, os.path.basename(opt.read1_file) + ".json")
-            with open(stat_path, "w") as f:
-                f.write(json.dumps(self.stat, sort_keys=True, indent=4, separators=(',', ': ')))
-            self.timing["stats_s"] = time.perf_counter() - t_stats
-            t_report = time.perf_counter()
-            # the HTML report next to it (preprocesser.py:780-783, qcreporter.py).  The FASTQ outputs and the statistics are
-            # complete at this point: a problem in the report is reported, it does not fail the run
-            try:
-                from . import qcreporter
-                ovl_hist, _ = stat_eng.histograms(capi.AQC_QC_COLS)
-                figures = qcreporter.build_figures(self.stat, opt, r1pre, r2pre, r1post, r2post, ovl_hist, readLen)
-                with open(os.path.join(qc_dir, os.path.basename(opt.read1_file) + ".html"), "w") as f:
-                    f.write(qcreporter.render(self.stat, figures, getattr(opt, "version", "")))
-            except Exception as e:      # noqa: BLE001 — whatever it is, the run's results stand
-                if os.environ.get("AQC_REPORT_STRICT"):      # the test suites: a broken report must not pass unseen
-                    raise
-                print("afterqc_amd: the HTML report could not be written (%s: %s); outputs and %s are complete"
-                      % (type(e).__name__, e, stat_path), file=sys.stderr)
-                self.timing["report_error"] = "%s: %s" % (type(e).__name__, e)
-            self.timing["report_s"] = time.perf_counter() - t_report
+            self._report(eng, r1pre, r2pre, extra_bases, qc_dir)
             self.timing["total_s"] = time.perf_counter() - t_run
         finally:
             t_close = time.perf_counter()
@@ -555,27 +451,170 @@ class seqFilter:
             self.timing["close_s"] = time.perf_counter() - t_close
         return self.stat
 
+    def _configure(self, first=False):
+        """the options as they stand -> every engine of the run; first: the bubble circles too, and the statistics start at zero"""
+        opt = self.options
+        self._last_cfg = (build_config(opt, self.paired, opt.index2_file is not None), self.bubbleCircles)
+        for e in self._engines():
+            e.set_config(self._last_cfg[0])
+            if first:
+                e.set_circles(self.bubbleCircles)
+                e.reset_stats()
+
+    def _sample(self, eng):
+        """Pass 1: pre-filter QC on a sample of each file (preprocesser.py:247-251) -> the QC objects of R1 and R2."""
+        opt = self.options
+        r1pre = QualityControl(opt.qc_sample, opt.qc_kmer, eng, capi.QC_R1_PRE)
+        r2pre = QualityControl(opt.qc_sample, opt.qc_kmer, eng, capi.QC_R2_PRE)
+        if not (self.use_text_path and hasattr(eng, "frame")):
+            r1pre.statFile(opt.read1_file, fastq.Reader, capi.Batch.from_raw, self.batch_records)
+            if self.paired:
+                # the R2 file is stat'd through the same single-read path into its own accumulator
+                r2pre.statFile(opt.read2_file, fastq.Reader, capi.Batch.from_raw, self.batch_records)
+            return r1pre, r2pre
+        side, side_err = None, []
+        if self.paired and isinstance(eng, capi.Engine) and eng.n_slots >= 2:
+            # read 2 is sampled at the same time in slot 1 (a .gz spends most of this pass decoding)
+            def _sample_r2():
+                try:
+                    r2pre.statFileText(opt.read2_file, self.chunk_bytes, slot=1)
+                except BaseException as e:       # re-raised on the main thread
+                    side_err.append(e)
+            side = threading.Thread(target=_sample_r2, name="aqc-sample-r2")
+            side.start()
+        try:
+            r1pre.statFileText(opt.read1_file, self.chunk_bytes)
+        finally:
+            if side is not None:
+                side.join()
+        if side_err:
+            raise side_err[0]
+        if self.paired and side is None:
+            r2pre.statFileText(opt.read2_file, self.chunk_bytes)
+        return r1pre, r2pre
+
+    def _auto_trim(self, r1pre, r2pre):
+        """Every trim option left at -1 is resolved from the pass-1 sample (preprocesser.py:261-280)."""
+        opt = self.options
+        if opt.trim_front != -1 and opt.trim_tail != -1:
+            return
+        tf, tt = r1pre.autoTrim()
+        if opt.trim_front == -1:
+            opt.trim_front = tf
+        if opt.trim_tail == -1:
+            opt.trim_tail = tt
+        if self.paired and opt.trim_pair_same:
+            opt.trim_front2 = opt.trim_front
+            opt.trim_tail2 = opt.trim_tail
+        elif self.paired:
+            tf2, tt2 = r2pre.autoTrim()
+            if opt.trim_front2 == -1:
+                opt.trim_front2 = tf2
+            if opt.trim_tail2 == -1:
+                opt.trim_tail2 = tt2
+
+    def _layout(self):
+        """Output layout (preprocesser.py:285-371): makes the folders -> (report folder, gzip the outputs?, per input file
+        (read 1, read 2, index 1, index 2) the paths of its good / bad / overlap output; None: not written)."""
+        opt = self.options
+        good_dir = opt.good_output_folder
+        if good_dir is None:
+            good_dir = os.path.dirname(opt.read1_file)
+        parent = os.path.dirname(os.path.dirname(good_dir + "/"))
+        bad_dir = opt.bad_output_folder if opt.bad_output_folder is not None else os.path.join(parent, "bad")
+        overlap_dir = opt.overlap_output_folder if opt.overlap_output_folder is not None else os.path.join(parent, "overlap")
+        qc_dir = opt.report_output_folder if opt.report_output_folder is not None else os.path.join(parent, "QC")
+        for d in (qc_dir, good_dir, bad_dir):
+            os.makedirs(d, exist_ok=True)          # (directory mode runs several files at once)
+        if opt.store_overlap and (self.paired or not opt.qc_only):
+            os.makedirs(overlap_dir, exist_ok=True)   # (single-end + store_overlap: upstream opens the writer without the dir)
+        gzip_out = bool(opt.gzip) or opt.read1_file.endswith(".gz")
+        ext = ".gz" if gzip_out else ""
+        paths = []
+        for k, f in enumerate(input_files(opt)):
+            if f is None or opt.qc_only:
+                paths.append((None, None, None))
+                continue
+            main = getMainName(f)
+            # upstream opens the R1 overlap writer whenever store_overlap is on, the others only when paired
+            ovl = opt.store_overlap and (k == 0 or self.paired)
+            paths.append((os.path.join(good_dir, main + ".good.fq" + ext), os.path.join(bad_dir, main + ".bad.fq" + ext),
+                          os.path.join(overlap_dir, main + ".overlap.fq" + ext) if ovl else None))
+        return qc_dir, gzip_out, paths
+
+    def _pass2(self, eng, paths, gzip_out):
+        """Pass 2, the main loop (preprocesser.py:411-631), through the driver the run calls for -> the extra-bases quirk value.
+        Text in / text out on the device (aqc_frame / aqc_format); use_text_path=False keeps the host-side framing and writer
+        as a cross-check, and an injected engine without the text calls takes that path too."""
+        opt = self.options
+        indexed = opt.index1_file is not None or opt.index2_file is not None
+        self.text_path = self.use_text_path and hasattr(eng, "frame")
+        if self.text_path and self.use_pipe and not indexed and not opt.qc_only and isinstance(eng, capi.Engine):
+            extra_bases = self._run_pipe(opt, paths, gzip_out)
+            if extra_bases is not None:
+                return extra_bases
+            # not the regular shape (empty line inside, mates of different lengths, ...): start over, chunk by chunk
+            print("afterqc_amd: %s is not of the regular shape the whole-input pipe takes (blank line inside / mates of "
+                  "different lengths); running it again through the serial chunk loop" % opt.read1_file, file=sys.stderr)
+            self.timing["pipe_fallback"] = True
+            for e in self._engines():
+                e.reset_stats()
+        outs = _Outputs(paths, opt.compression)
+        try:
+            if not self.text_path:
+                return self._run_host(eng, opt, outs)
+            return self._run_text_indexed(eng, opt, outs) if indexed else self._run_text(eng, opt, outs)
+        finally:
+            # (also when the run ends in an exception: what was written up to the record upstream dies at stays written)
+            outs.close()
+
+    def _report(self, eng, r1pre, r2pre, extra_bases, qc_dir):
+        """Post-filter QC and the counters -> self.stat, QC/<R1 basename>.json and the HTML report next to it."""
+        opt = self.options
+        t_stats = time.perf_counter()
+        # statistics: per-GPU integers summed on the host (only the pipe spreads a run over several engines)
+        stat_eng = capi.MergedEngines(self._engines()) if self.extra_engines else eng
+        r1post = QualityControl(opt.qc_sample, opt.qc_kmer, stat_eng, capi.QC_R1_POST)
+        r2post = QualityControl(opt.qc_sample, opt.qc_kmer, stat_eng, capi.QC_R2_POST)
+        r1post.qc()
+        if self.paired:
+            r2post.qc()
+        readLen = r1pre.readLen
+        self.stat = self._stats(stat_eng, r1pre, r2pre, r1post, r2post, readLen, extra_bases)
+        stat_path = os.path.join(qc_dir, os.path.basename(opt.read1_file) + ".json")
+        with open(stat_path, "w") as f:
+            f.write(json.dumps(self.stat, sort_keys=True, indent=4, separators=(',', ': ')))
+        self.timing["stats_s"] = time.perf_counter() - t_stats
+        t_report = time.perf_counter()
+        # the HTML report next to it (preprocesser.py:780-783, qcreporter.py).  The FASTQ outputs and the statistics are
+        # complete at this point: a problem in the report is reported, it does not fail the run
+        try:
+            from . import qcreporter
+            ovl_hist, _ = stat_eng.histograms(capi.AQC_QC_COLS)
+            figures = qcreporter.build_figures(self.stat, opt, r1pre, r2pre, r1post, r2post, ovl_hist, readLen)
+            with open(os.path.join(qc_dir, os.path.basename(opt.read1_file) + ".html"), "w") as f:
+                f.write(qcreporter.render(self.stat, figures, getattr(opt, "version", "")))
+        except Exception as e:      # noqa: BLE001 — whatever it is, the run's results stand
+            if os.environ.get("AQC_REPORT_STRICT"):      # the test suites: a broken report must not pass unseen
+                raise
+            print("afterqc_amd: the HTML report could not be written (%s: %s); outputs and %s are complete"
+                  % (type(e).__name__, e, stat_path), file=sys.stderr)
+            self.timing["report_error"] = "%s: %s" % (type(e).__name__, e)
+        self.timing["report_s"] = time.perf_counter() - t_report
+
     # ---- pass 2 through the whole-input pipe (aqc_pipe_run) ---------------------------------------------------------------
-    def _run_pipe(self, opt, files, good_dir, bad_dir, overlap_dir, gzip_out, paired):
+    def _run_pipe(self, opt, paths, gzip_out):
         """Hands the read file(s) to the C++ pipe: chunks of `chunk_records` records dealt over every engine, outputs written
         in chunk order by its writer thread.  Returns the extra-bases quirk value (preprocesser.py:416-421) or None when the
         pipe met an input it cannot chunk (the caller falls back to the serial chunk loop)."""
-        nfiles = 2 if paired else 1
-        outputs = []
-        for k in range(nfiles):
-            main = getMainName(files[k])
-            ext = ".gz" if gzip_out else ""
-            # upstream opens the R1 overlap writer whenever store_overlap is on, the others only when paired (_Outputs)
-            want_ovl = (opt.store_overlap and k == 0) or (opt.store_overlap and paired)
-            outputs.append((os.path.join(good_dir, main + ".good.fq" + ext), os.path.join(bad_dir, main + ".bad.fq" + ext),
-                            os.path.join(overlap_dir, main + ".overlap.fq" + ext) if want_ovl else None))
+        files = [opt.read1_file] + ([opt.read2_file] if self.paired else [])
         engines = self._engines(all_devices=True)
         pipe = capi.Pipe(engines, slots=min([self.pipe_slots] + [e.n_slots for e in engines]), io_threads=self.io_threads)
         try:
             # (fastq.py:23-26: .gz through gzip.open, .bz2 through bz2.BZ2File upstream — here the pipe's own decoders: 1 gzip, 2 bzip2)
-            res = pipe.run(files[:nfiles], outputs, gzip_in=[1 if f.endswith(".gz") else 2 if f.endswith(".bz2") else 0 for f in files[:nfiles]], gzip_out=gzip_out,
-                           gzip_level=opt.compression, chunk_records=self.chunk_records, qc_sample=opt.qc_sample,
-                           store_overlap=bool(opt.store_overlap) and paired)
+            res = pipe.run(files, paths[:len(files)], gzip_in=[1 if f.endswith(".gz") else 2 if f.endswith(".bz2") else 0 for f in files],
+                           gzip_out=gzip_out, gzip_level=opt.compression, chunk_records=self.chunk_records, qc_sample=opt.qc_sample,
+                           store_overlap=bool(opt.store_overlap) and self.paired)
         except capi.AqcError as e:
             # (an exception inside upstream's loop — capi.RECORD_ERRORS — ends the run at that record: the pipe has written
             #  everything before it and says so; there is nothing to rerun)
@@ -593,149 +632,23 @@ class seqFilter:
         #  applies fastq.Reader's end-of-file rules itself since round 6)
         return int(res.extra_bases)
 
-    # ---- pass 2, text path with index files (-7 / -5): four lock-stepped inputs, two device slots ---------------------
-    def _run_text_indexed(self, eng, opt, outs, paired):
-        """Like _run_text, for runs with index files: the reads are framed into slot 0, the index reads into slot 1 (capped
-        at the reads' record count), the index records are formatted whole under the reads' verdicts
-        (aqc_format_plain).  Rare in practice, so this variant is kept simple: one chunk at a time, fetch and write inline."""
-        files = [opt.read1_file, opt.read2_file, opt.index1_file, opt.index2_file]
-        present = [k for k in range(4) if files[k] is not None]
-        groups = [[k for k in present if k < 2], [k for k in present if k >= 2]]
-        inputs = dict((k, _TextInput(eng, files[k], self.chunk_bytes)) for k in present)
-        writers = dict((k, (outs.good[k], outs.bad[k], outs.overlap[k])) for k in present)
-        hold = {}
-        total = 0
-        extra_bases = 0
-        cur = 0
-        UNLIMITED = capi.UINT64_MAX
-
-        def frame_group(slot, g, fills, cap):
-            a = g[0]
-            if len(g) > 1:
-                b = g[1]
-                return eng.frame(slot, inputs[a].bufs[cur].array, fills[a][0], fills[a][1], inputs[b].bufs[cur].array, fills[b][0],
-                                 fills[b][1], max_records=cap, first_index=total)
-            return eng.frame(slot, inputs[a].bufs[cur].array, fills[a][0], fills[a][1], max_records=cap, first_index=total)
-
-        def per_file(info, g):
-            d = {g[0]: (int(info.avail1), bool(info.eof1), int(info.consumed1))}
-            if len(g) > 1:
-                d[g[1]] = (int(info.avail2), bool(info.eof2), int(info.consumed2))
-            return d
-
-        def write_streams(slot, g, sizes):
-            for q, nbytes in enumerate(sizes):
-                if nbytes == 0 or q // 3 >= len(g):
-                    continue
-                w = writers[g[q // 3]][q % 3]
-                if w is None:
-                    continue
-                buf = hold.get(q)
-                if buf is None or buf.nbytes < nbytes:
-                    if buf is not None:
-                        buf.free()
-                    buf = hold[q] = eng.host_buffer(nbytes + nbytes // 4 + 4096)
-                eng.fetch_text(slot, q // 3, q % 3, buf.array, buf.nbytes)
-                w.write_bytes(buf.view[:nbytes])
-
+    # ---- the body of upstream's loop for one chunk: every serial driver calls this -------------------------------------
+    def _judge(self, eng, slot, n, total, wait=True):
+        """Verdicts and statistics of the `n` records framed or uploaded into `slot`, `total` records (TOTAL_READS) into the
+        run -> (n, stop, death): the records of the chunk that count, whether the loop ends with them, and the AqcError to
+        raise once they are written — an exception inside upstream's loop ends its run AT that record (death_record).
+        wait=False (the pipelined loop, whose fetch thread meets a death of its own): no host-blocking call but the one
+        the sampling kernels need."""
+        opt = self.options
+        stop, death = False, None
         try:
-            for k in present:
-                inputs[k].start_fill(cur, 0)
-            while True:
-                fills = dict((k, inputs[k].wait_fill()) for k in present)
-                info_a = frame_group(0, groups[0], fills, UNLIMITED)
-                info_b = frame_group(1, groups[1], fills, int(info_a.n))
-                if int(info_b.n) < int(info_a.n):
-                    info_a = frame_group(0, groups[0], fills, int(info_b.n))     # the index chunk holds fewer records
-                n = int(info_b.n)
-                state = per_file(info_a, groups[0])
-                state.update(per_file(info_b, groups[1]))
-                done = dict((k, (state[k][1] or fills[k][1]) and state[k][0] == n) for k in present)
-                stop = False
-                if done[0]:
-                    stop = True
-                elif any(done[k] for k in present if k != 0) and state[0][0] > n:
-                    # R1's next record was read (and counted into TOTAL_BASES) before another reader ran dry (:416-429)
-                    extra_bases = int(info_a.next_len1)
-                    stop = True
-                if not stop:
-                    for k in present:
-                        if n == 0 and not fills[k][1] and not state[k][1] and state[k][0] == 0:
-                            inputs[k].grow(cur)
-                        inputs[k].carry(cur, state[k][2], fills[k][0], fills[k][1], state[k][1] or (k != 0 and done[k]))
-                if n:
-                    death = None
-                    try:
-                        limit = UNLIMITED
-                        if opt.qc_only:
-                            eng.run(0, 0)
-                            flags = eng.fetch_results(0)[:n]["flag"]
-                            hit = np.flatnonzero((flags == capi.GOOD) & (total + 1 + np.arange(n) >= opt.qc_sample))
-                            if len(hit):
-                                n = int(hit[0]) + 1
-                                stop = True
-                            limit = n
-                        eng.run(0, limit)
-                        n_qc = n if opt.qc_sample <= 0 else max(0, min(n, opt.qc_sample - 1 - total))
-                        if n_qc > 0:
-                            eng.qc_stat(0, capi.QC_R1_POST, 0, 0, n_qc, 1)
-                            if paired:
-                                eng.qc_stat(0, capi.QC_R2_POST, 1, 0, n_qc, 1)
-                        eng.sync(0)
-                    except capi.AqcError as e:
-                        k = death_record(eng, 0, e)          # upstream's run ends at that record, what came before is written
-                        if k is None or k >= n:
-                            raise
-                        n, death = k, e
-                    if not opt.qc_only:
-                        write_streams(0, groups[0], eng.format(0, n, bool(opt.store_overlap)))
-                        write_streams(1, groups[1], eng.format_plain(1, 0, n, bool(opt.store_overlap)))
-                    if death is not None:
-                        raise death
-                    total += n
-                if stop:
-                    break
-                cur = 1 - cur
-        finally:
-            for k in present:
-                inputs[k].close()
-            for b in hold.values():
-                b.free()
-        return extra_bases
-
-    # ---- pass 2 with host-side framing / formatting (general: barcodes, index files, overlap store, bubbles) ------
-    def _run_host(self, eng, opt, outs, paired, files):
-        readers = [fastq.Reader(f) if f is not None else None for f in files]
-        total = 0          # TOTAL_READS so far
-        extra_bases = 0    # R1 bases read for a record that a shorter mate file then cut off (:416-421)
-        stop = False
-        slot = 0
-        while not stop:
-            rbs = [r.next_batch(self.batch_records) if r is not None else None for r in readers]
-            if rbs[0] is None:
-                break
-            # lock-step reading: the first file to run dry ends the loop (preprocesser.py:412-429); R1's
-            # record was already counted into TOTAL_BASES by then (:416)
-            n = min(rbs[k].n if rbs[k] is not None else 0 for k in range(4) if readers[k] is not None)
-            if n < rbs[0].n:
-                extra_bases = int(rbs[0].seq_len[n])
-                stop = True
-            if n == 0:
-                break
-            batch = capi.Batch.from_raw(rbs[0], rbs[1] if paired else None, first_index=total)
-            if n < batch.n:
-                batch.n = n
-            if opt.debubble:
-                self._aux(batch, rbs[0])
-            eng.upload(slot, batch)
-            # --qc_only stops at the first good record whose 1-based index reaches qc_sample (:630-631)
             limit = capi.UINT64_MAX
-            results = None
             if opt.qc_only:
+                # --qc_only stops at the first good record whose 1-based index reaches qc_sample (:630-631):
+                # verdicts first (nothing accumulated), then the accumulating run up to that record
                 eng.run(slot, 0)
-                results = eng.fetch_results(slot)[:n]
-                idx1 = total + 1 + np.arange(n)
-                hit = np.flatnonzero((results["flag"] == capi.GOOD) & (idx1 >= opt.qc_sample))
+                flags = eng.fetch_results(slot)[:n]["flag"]
+                hit = np.flatnonzero((flags == capi.GOOD) & (total + 1 + np.arange(n) >= opt.qc_sample))
                 if len(hit):
                     n = int(hit[0]) + 1
                     stop = True
@@ -745,39 +658,121 @@ class seqFilter:
             n_qc = n if opt.qc_sample <= 0 else max(0, min(n, opt.qc_sample - 1 - total))
             if n_qc > 0:
                 eng.qc_stat(slot, capi.QC_R1_POST, 0, 0, n_qc, 1)
-                if paired:
+                if self.paired:
                     eng.qc_stat(slot, capi.QC_R2_POST, 1, 0, n_qc, 1)
-            death = None
-            try:
-                results = eng.fetch_results(slot)[:n]
-            except capi.AqcError as e:
-                k = death_record(eng, slot, e)               # upstream's run ends at that record, what came before is written
-                if k is None or k >= n:
-                    raise
-                n, death = k, e
-                results = eng.fetch_results(slot)[:n]
-            if not opt.qc_only:
-                qviews = None
-                if batch.qlen1 is not None:
-                    qviews = [eng.fetch_quality_views(slot, 0), eng.fetch_quality_views(slot, 1) if paired else None]
-                self._write(outs, rbs, results, n, qviews)
-            if death is not None:
-                raise death
-            total += n
-        return readers, extra_bases
+            # the sampling kernels share per-context scratch: never two chunks at once; and a death surfaces at a host-blocking
+            # call: with `wait` here, where it is cut at its record, not in the caller's fetches
+            if wait or n_qc > 0 or opt.qc_only:
+                eng.sync(slot)
+        except capi.AqcError as e:
+            k = death_record(eng, slot, e)
+            if k is None or k >= n:
+                raise
+            n, stop, death = k, True, e
+        return n, stop, death
+
+    # ---- pass 2, text path with index files (-7 / -5): four lock-stepped inputs, two device slots ---------------------
+    def _run_text_indexed(self, eng, opt, outs):
+        """Like _run_text, for runs with index files: the reads are framed into slot 0, the index reads into slot 1 (capped
+        at the reads' record count), the index records are formatted whole under the reads' verdicts
+        (aqc_format_plain).  Rare in practice, so this variant is kept simple: one chunk at a time, fetch and write inline."""
+        inputs = [_TextInput(eng, f, self.chunk_bytes) for f in input_files(opt) if f is not None]
+        writers = [w for w, f in zip(outs.per_file, input_files(opt)) if f is not None]
+        nr = 2 if self.paired else 1                  # inputs[:nr] are the reads, inputs[nr:] the index reads
+        hold = [None] * 6
+        total = 0
+        cur = 0
+
+        def write_streams(slot, group, sizes):
+            for q, nbytes in enumerate(sizes):
+                if nbytes and q // 3 < len(group) and group[q // 3][q % 3] is not None:
+                    group[q // 3][q % 3].write_bytes(fetch_stream(eng, slot, q, nbytes, hold).view[:nbytes])
+
+        try:
+            for inp in inputs:
+                inp.start_fill(cur, 0)
+            while True:
+                fills = [inp.wait_fill() for inp in inputs]
+                info, reads = frame_inputs(eng, 0, inputs[:nr], fills[:nr], cur, total)
+                info_b, index = frame_inputs(eng, 1, inputs[nr:], fills[nr:], cur, total, int(info.n))
+                n = int(info_b.n)
+                if n < int(info.n):
+                    info, reads = frame_inputs(eng, 0, inputs[:nr], fills[:nr], cur, total, n)    # the index chunk holds fewer records
+                stop, extra_bases, finished = lock_step(reads + index, info)
+                if not stop:
+                    advance(inputs, cur, n, reads + index, finished)
+                if n:
+                    n, cut, death = self._judge(eng, 0, n, total)
+                    if not opt.qc_only:
+                        write_streams(0, writers[:nr], eng.format(0, n, bool(opt.store_overlap)))
+                        write_streams(1, writers[nr:], eng.format_plain(1, 0, n, bool(opt.store_overlap)))
+                    if death is not None:
+                        raise death
+                    total += n
+                    stop = stop or cut
+                if stop:
+                    return extra_bases
+                cur = 1 - cur
+        finally:
+            for inp in inputs:
+                inp.close()
+            for b in hold:
+                if b is not None:
+                    b.free()
+
+    # ---- pass 2 with host-side framing / formatting (general: barcodes, index files, overlap store, bubbles) ------
+    def _run_host(self, eng, opt, outs):
+        readers = [fastq.Reader(f) if f is not None else None for f in input_files(opt)]
+        total = 0          # TOTAL_READS so far
+        extra_bases = 0    # R1 bases read for a record that a shorter mate file then cut off (:416-421)
+        stop = False
+        slot = 0
+        try:
+            while not stop:
+                rbs = [r.next_batch(self.batch_records) if r is not None else None for r in readers]
+                if rbs[0] is None:
+                    break
+                # lock step over whole batches (the rule is stated by lock_step): the first file to run dry ends the loop, and
+                # R1's record was already counted into TOTAL_BASES by then
+                n = min(rbs[k].n if rbs[k] is not None else 0 for k in range(4) if readers[k] is not None)
+                if n < rbs[0].n:
+                    extra_bases = int(rbs[0].seq_len[n])
+                    stop = True
+                if n == 0:
+                    break
+                batch = capi.Batch.from_raw(rbs[0], rbs[1] if self.paired else None, first_index=total)
+                if n < batch.n:
+                    batch.n = n
+                if opt.debubble:
+                    self._aux(batch, rbs[0])
+                eng.upload(slot, batch)
+                n, cut, death = self._judge(eng, slot, n, total)
+                stop = stop or cut
+                if not opt.qc_only:
+                    qviews = None
+                    if batch.qlen1 is not None:
+                        qviews = [eng.fetch_quality_views(slot, 0), eng.fetch_quality_views(slot, 1) if self.paired else None]
+                    self._write(outs, rbs, eng.fetch_results(slot)[:n], n, qviews)
+                if death is not None:
+                    raise death
+                total += n
+        finally:
+            for r in readers:
+                if r is not None:
+                    r.close()
+        return extra_bases
 
     # ---- pass 2, text in / text out: framing and formatting on the device (SURVEY.md §8(f)1) -------------------
-    def _run_text(self, eng, opt, outs, paired):
+    def _run_text(self, eng, opt, outs):
         """The loop of preprocesser.py:411-631 over raw text chunks.  Per chunk the host only moves bytes: file ->
         page-locked buffer -> aqc_frame (records found on the device) -> aqc_run / aqc_qc_stat -> aqc_format
         (good / bad text built on the device) -> page-locked buffer -> file.  File reads and writes run on side
         threads while the main thread sits in the (GIL-free) C-ABI calls."""
-        files = [opt.read1_file] + ([opt.read2_file] if paired else [])
+        files = [opt.read1_file] + ([opt.read2_file] if self.paired else [])
         inputs = [_TextInput(eng, f, self.chunk_bytes) for f in files]
         n_slots = min(2, getattr(eng, "n_slots", 1))
-        sink = _TextSink(eng, [(outs.good[k], outs.bad[k], outs.overlap[k]) for k in range(len(files))], n_slots, bool(opt.store_overlap))
+        sink = _TextSink(eng, outs.per_file[:len(files)], n_slots, bool(opt.store_overlap))
         total = 0
-        extra_bases = 0
         slot = 0
         cur = 0
         try:
@@ -786,78 +781,31 @@ class seqFilter:
             while True:
                 fills = [inp.wait_fill() for inp in inputs]          # (bytes in buffer `cur`, final)
                 sink.acquire_slot(slot)                               # its previous chunk has left the device
-                a1, n1, f1 = inputs[0].bufs[cur].array, fills[0][0], fills[0][1]
-                if paired:
-                    info = eng.frame(slot, a1, n1, f1, inputs[1].bufs[cur].array, fills[1][0], fills[1][1], first_index=total)
-                else:
-                    info = eng.frame(slot, a1, n1, f1, first_index=total)
+                info, state = frame_inputs(eng, slot, inputs, fills, cur, total)
                 n = int(info.n)
-                # lock step (preprocesser.py:412-429): R1 is read first; the first reader to return None ends the loop,
-                # and an R1 record read just before R2 ran dry has already been counted into TOTAL_BASES (:416)
-                done1 = (info.eof1 or f1) and info.avail1 == n
-                done2 = paired and (info.eof2 or fills[1][1]) and info.avail2 == n
-                stop = False
-                if done1:
-                    stop = True
-                elif done2 and info.avail1 > n:
-                    extra_bases = int(info.next_len1)
-                    stop = True
+                stop, extra_bases, finished = lock_step(state, info)
                 if not stop:
-                    consumed = [int(info.consumed1), int(info.consumed2)]
-                    eofs = [bool(info.eof1), bool(info.eof2)]
-                    for k, inp in enumerate(inputs):
-                        if n == 0 and not fills[k][1] and not eofs[k] and (info.avail1, info.avail2)[k] == 0:
-                            inp.grow(cur)                                  # not even one record fits the buffer
-                        inp.carry(cur, consumed[k], fills[k][0], fills[k][1], eofs[k] or (k == 1 and done2))
+                    advance(inputs, cur, n, state, finished)
                 if n:
-                    death = None
-                    try:
-                        limit = capi.UINT64_MAX
-                        if opt.qc_only:
-                            # --qc_only stops at the first good record whose 1-based index reaches qc_sample (:630-631):
-                            # verdicts first (nothing accumulated), then the accumulating run up to that record
-                            eng.run(slot, 0)
-                            flags = eng.fetch_results(slot)[:n]["flag"]
-                            hit = np.flatnonzero((flags == capi.GOOD) & (total + 1 + np.arange(n) >= opt.qc_sample))
-                            if len(hit):
-                                n = int(hit[0]) + 1
-                                stop = True
-                            limit = n
-                        eng.run(slot, limit)
-                        # post-filter QC on good records while TOTAL_READS < qc_sample (preprocesser.py:624-627)
-                        n_qc = n if opt.qc_sample <= 0 else max(0, min(n, opt.qc_sample - 1 - total))
-                        if n_qc > 0:
-                            eng.qc_stat(slot, capi.QC_R1_POST, 0, 0, n_qc, 1)
-                            if paired:
-                                eng.qc_stat(slot, capi.QC_R2_POST, 1, 0, n_qc, 1)
-                            eng.sync(slot)       # the sampling kernels share per-context scratch: never two chunks at once
-                        if opt.qc_only:
-                            eng.sync(slot)
-                    except capi.AqcError as e:
-                        # an exception inside upstream's loop ends its run AT that record: what came before is written
-                        k = death_record(eng, slot, e)
-                        if k is None or k >= n:
-                            raise
-                        n, death, stop = k, e, True
+                    n, cut, death = self._judge(eng, slot, n, total, wait=False)
+                    stop = stop or cut
                     if opt.qc_only:
                         sink.release_slot(slot)
                         if death is not None:
                             raise death
                     else:
-                        sizes = eng.format(slot, n, bool(opt.store_overlap))
-                        sink.emit(slot, sizes, death)   # (the fetch thread releases the slot)
+                        sink.emit(slot, eng.format(slot, n, bool(opt.store_overlap)), death)   # (the fetch thread releases the slot)
                     total += n
                 else:
                     sink.release_slot(slot)
                 if stop:
-                    break
+                    return extra_bases
                 cur = 1 - cur
                 slot = (slot + 1) % n_slots
         finally:
             sink.close()
             for inp in inputs:
                 inp.close()
-        return extra_bases
 
     # ---- output formatting (writeReads, preprocesser.py:206-232; fastq.Writer.writeLines) ------------
     def _write(self, outs, rbs, results, n, qviews=None):

@@ -173,6 +173,35 @@ class QualityControl:
         return [[k, c] for k, c in self.topKmerCount[:top]]
 
     # ---- sampling policy ----------------------------------------------------------------------------
+    def _window(self):
+        """statFile's policy (qualitycontrol.py:331-357) as 0-based bounds: reads #1..999 are skipped and the next
+        `sampleLimit` reads stat'd -> (lo, hi, stop): reads [lo, hi) are stat'd (hi None: to the end of the file) and reading
+        ends after `stop` reads — the read whose arrival triggers the break is still consumed"""
+        lo = READ_TO_SKIP - 1
+        hi = lo + self.sampleLimit if self.sampleLimit > 0 else None
+        return lo, hi, None if hi is None else hi + 1
+
+    def _stat(self, slot, first, count):
+        self.engine.qc_stat(slot, self.which, 0, first, count, 0)
+        self.engine.sync(slot)
+
+    def _clip(self, seen, n):
+        """a chunk holds reads [seen, seen + n) of the file -> (first, count) of those inside the window, chunk-relative"""
+        lo, hi, _ = self._window()
+        a = max(lo, seen)
+        b = seen + n if hi is None else min(hi, seen + n)
+        return a - seen, max(0, b - a)
+
+    def _skipped_to_stat(self, seen, head_n, too_few):
+        """when fewer than 1000 reads followed the skipped ones, the skipped reads are stat'd as well — afterwards, which
+        fixes the k-mer dictionary's insertion order -> how many of the file's first reads that is (0: none); head_n: the
+        reads the caller kept of the first chunk"""
+        lo = self._window()[0]
+        k = min(lo, seen) if max(0, seen - lo) < READ_TO_SKIP else 0
+        if head_n < k:
+            raise RuntimeError(too_few % lo)
+        return k
+
     def statFileText(self, filename, chunk_bytes, slot=0):
         """statFile (qualitycontrol.py:331-357) with the records framed on the device (aqc_frame): the host only reads
         the file into a page-locked buffer.  Same policy as statFile below.  `slot`: the engine slot to work in (the two
@@ -182,9 +211,7 @@ class QualityControl:
         cap = max(int(chunk_bytes), 4 << 20)          # the first chunk must hold the 999 skipped reads (fallback below)
         f = fastq.open_binary(filename, sample=self.sampleLimit > 0)
         buf = eng.host_buffer(cap)
-        lo = READ_TO_SKIP - 1
-        hi = lo + self.sampleLimit if self.sampleLimit > 0 else None    # stat 0-based [lo, hi)
-        stop = None if hi is None else hi + 1      # the read whose arrival triggers the break is still consumed
+        stop = self._window()[2]
         head, head_n = None, 0
         seen = 0
         left = 0
@@ -204,11 +231,9 @@ class QualityControl:
                 n = int(info.n)
                 if head is None:
                     head, head_n = buf.array[:int(info.consumed1)].copy(), n
-                a = max(lo, seen)
-                b = seen + n if hi is None else min(hi, seen + n)
-                if b > a:
-                    eng.qc_stat(slot, self.which, 0, a - seen, b - a, 0)
-                    eng.sync(slot)
+                first, count = self._clip(seen, n)
+                if count:
+                    self._stat(slot, first, count)
                 seen += n
                 if info.eof1 or (file_eof and int(info.avail1) == n):
                     break
@@ -228,27 +253,21 @@ class QualityControl:
                     # decoded for every byte asked for), not for another buffer-full
                     fill = min(cap, left + int(int(info.consumed1) / n * (stop - seen) * 1.1) + (256 << 10))
             self.readCount = seen
-            if max(0, seen - lo) < READ_TO_SKIP and head is not None and min(lo, seen) > 0:
-                if head_n < min(lo, seen):
-                    raise RuntimeError("the first chunk must hold at least %d records" % lo)
+            k = self._skipped_to_stat(seen, head_n, "the first chunk must hold at least %d records")
+            if k:
                 pad = np.zeros(len(head) + 64, dtype=np.uint8)
                 pad[:len(head)] = head
-                eng.frame(slot, pad, len(head), True, max_records=min(lo, seen), first_index=0)
-                eng.qc_stat(slot, self.which, 0, 0, min(lo, seen), 0)
-                eng.sync(slot)
+                eng.frame(slot, pad, len(head), True, max_records=k, first_index=0)
+                self._stat(slot, 0, k)
         finally:
             f.close()
             buf.free()
         self.qc()
 
     def statFile(self, filename, open_reader, to_batch, batch_records):
-        """statFile (qualitycontrol.py:331-357): reads #1..999 are skipped, the next `sampleLimit`
-        reads are stat'd; when fewer than 1000 reads followed the skipped ones, the skipped reads are
-        stat'd as well — afterwards, which fixes the k-mer dictionary's insertion order."""
+        """statFile (qualitycontrol.py:331-357, the policy of _window / _skipped_to_stat) over batches framed on the host."""
         reader = open_reader(filename)
-        lo = READ_TO_SKIP - 1
-        hi = lo + self.sampleLimit if self.sampleLimit > 0 else None    # stat 0-based [lo, hi)
-        stop = None if hi is None else hi + 1      # the read whose arrival triggers the break is still consumed
+        stop = self._window()[2]
         head = None
         seen = 0
         while stop is None or seen < stop:
@@ -257,19 +276,15 @@ class QualityControl:
                 break
             if head is None:
                 head = rb
-            a = max(lo, seen)
-            b = seen + rb.n if hi is None else min(hi, seen + rb.n)
-            if b > a:
+            first, count = self._clip(seen, rb.n)
+            if count:
                 self.engine.upload(0, to_batch(rb))
-                self.engine.qc_stat(0, self.which, 0, a - seen, b - a, 0)
-                self.engine.sync(0)
+                self._stat(0, first, count)
             seen += rb.n
         reader.close()
         self.readCount = seen
-        if max(0, seen - lo) < READ_TO_SKIP and head is not None and min(lo, seen) > 0:
-            if head.n < min(lo, seen):
-                raise RuntimeError("batch_records must be at least %d" % lo)
+        k = self._skipped_to_stat(seen, head.n if head is not None else 0, "batch_records must be at least %d")
+        if k:
             self.engine.upload(0, to_batch(head))
-            self.engine.qc_stat(0, self.which, 0, 0, min(lo, seen), 0)
-            self.engine.sync(0)
+            self._stat(0, 0, k)
         self.qc()
