@@ -89,7 +89,7 @@ void inflate_raw2(const uint8_t* const src[2], const size_t n[2], uint8_t* const
 uint32_t crc32_fast(uint32_t crc, const uint8_t* p, size_t n);
 uint32_t crc32_combine_fast(uint32_t crc1, uint32_t crc2, uint64_t len2);
 
-// Sections decoded somewhere else than on the pool: the GPU (aqc_capi.hip: DeviceInflate, kernels in aqc_gunzip_dev.hpp).  A
+// Sections decoded somewhere else than on the pool: the GPU (aqc_gunzip_offload.hip: DeviceInflate, kernels in aqc_gunzip_dev.hpp).  A
 // GROUP of consecutive sections is handed over at once; each comes back as what a pool thread would have produced — the block
 // boundary it starts at, the one it ends at, its symbols — or as "nothing found".  The consumer's commit rule does not care who
 // decoded a section, so exactness does not depend on the device being right, only speed does.
@@ -153,7 +153,7 @@ public:
     virtual bool fetch(void* token, size_t off, size_t len, uint8_t* dst) { (void)token; (void)off; (void)len; (void)dst; return false; }
     virtual bool fetch_wait() { return false; }
 };
-// the device decoder of GPU `device` (aqc_capi.hip); nullptr when it cannot be set up
+// the device decoder of GPU `device` (aqc_gunzip_offload.hip); nullptr when it cannot be set up
 SectionOffload* make_device_offload(int device, size_t group_bytes);
 // kernel / copy microseconds of every device decoder of the process so far: scan, decode, chain + gather, H2D, D2H, groups, sections given, sections found
 void device_offload_stats(uint64_t out[8]);

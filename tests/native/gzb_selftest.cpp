@@ -3,7 +3,7 @@
 // The header's GZB_HD functions are what the kernels' lanes execute: the block-start tests, the table builder, the block
 // decoder, the chain walk, the marker re-basing.  CpuOffload below deals them out with plain loops in the kernels' order
 // (scan -> compact -> decode -> chain -> gather, same buffers, same GzbJob) and plugs into the real ParallelGunzip through
-// the SectionOffload interface the GPU uses (aqc_capi.hip: DeviceInflate).  So this checks, without a GPU:
+// the SectionOffload interface the GPU uses (aqc_gunzip_offload.hip: DeviceInflate).  So this checks, without a GPU:
 //   * every zlib stream below comes out byte-identical (ParallelGunzip also verifies CRC-32 / ISIZE itself);
 //   * the offloaded sections really are committed (the chain rule accepts them) for dynamic-Huffman streams;
 //   * stored blocks inside a chain, concatenated members, fixed-Huffman and stored-only streams, false section starts,
