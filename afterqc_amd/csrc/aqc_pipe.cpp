@@ -21,12 +21,14 @@
 // empty line inside.  Anything else (fastq.py:44-47's "empty line ends the file", mates of different lengths, ...)
 // is detected from the frame info and reported as `anomaly`; the caller then reruns the input through the serial
 // chunk loop, which reproduces the reference's reader semantics case by case.
-#include <dlfcn.h>
-#include <fcntl.h>
-#include <sys/mman.h>
+//
+// One translation unit, in four files:
+//   aqc_pipe_prim.hpp     clocks, the bounded queue, on / off environment knobs
+//   aqc_pipe_source.hpp   newline counting and the byte sources (file, bzip2, gzip)
+//   aqc_pipe_out.hpp      the output file, the BGZF member, the host buffer
+//   aqc_pipe.cpp          this file: the chunks, `struct Run` (one run's queues, locks and thread bodies) and the C ABI
 #include <sys/stat.h>
 #include <sys/uio.h>
-#include <unistd.h>
 #include <zlib.h>
 
 #include <atomic>
@@ -36,8 +38,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
-#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -45,13 +45,12 @@
 #include <thread>
 #include <vector>
 
-#if defined(__x86_64__)
-#include <immintrin.h>
-#endif
-
 #include "../../include/afterqc_hip.h"
 #include "aqc_gz.hpp"
 #include "aqc_pool.hpp"
+#include "aqc_pipe_prim.hpp"
+#include "aqc_pipe_source.hpp"
+#include "aqc_pipe_out.hpp"
 
 #ifdef AQC_GZ_PROFILE
 namespace aqcgz { extern std::atomic<long> gz_prof[6]; }
@@ -61,731 +60,6 @@ namespace {
 
 char g_pipe_err[512] = "";
 std::mutex g_pipe_err_mu;
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-double thread_cpu_s() {
-    timespec ts;
-    return clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts) == 0 ? (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec : 0.0;
-}
-double process_cpu_s() {
-    timespec ts;
-    return clock_gettime(CLOCK_PROCESS_CPUTIME_ID, &ts) == 0 ? (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec : 0.0;
-}
-uint64_t now_ns() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-using aqc_host::Pool;      // aqc_pool.hpp: parallel_for (front lane) + submit (background lane for speculative work)
-
-template <class T>
-class BQueue {
-public:
-    explicit BQueue(size_t cap = 0) : cap_(cap) {}
-    bool push(T v) {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_space_.wait(lk, [&] { return closed_ || cap_ == 0 || q_.size() < cap_; });
-        if (closed_) return false;
-        q_.push_back(std::move(v));
-        cv_item_.notify_one();
-        return true;
-    }
-    bool pop(T& out) {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_item_.wait(lk, [&] { return closed_ || !q_.empty(); });
-        if (q_.empty()) return false;
-        out = std::move(q_.front());
-        q_.pop_front();
-        cv_space_.notify_one();
-        return true;
-    }
-    void close() {
-        std::lock_guard<std::mutex> g(mu_);
-        closed_ = true;
-        cv_item_.notify_all();
-        cv_space_.notify_all();
-    }
-
-private:
-    size_t cap_;
-    std::deque<T> q_;
-    std::mutex mu_;
-    std::condition_variable cv_item_, cv_space_;
-    bool closed_ = false;
-};
-
-// ---------------------------------------------------------------------------------------------------------------
-// newline counting (the chunk boundary is "the 4K-th newline"): 8 bytes per step, portable; an AVX2 twin where the CPU has it
-// ---------------------------------------------------------------------------------------------------------------
-uint64_t count_nl_generic(const uint8_t* p, size_t n) {
-    uint64_t c = 0;
-    size_t i = 0;
-    for (; i < n && ((uintptr_t)(p + i) & 7); ++i) c += p[i] == '\n';
-    const uint64_t k = 0x0a0a0a0a0a0a0a0aull, lo7 = 0x7f7f7f7f7f7f7f7full;
-    for (; i + 8 <= n; i += 8) {
-        uint64_t x;
-        memcpy(&x, p + i, 8);
-        x ^= k;
-        const uint64_t z = ~(((x & lo7) + lo7) | x | lo7);      // 0x80 in every zero byte
-        c += (uint64_t)__builtin_popcountll(z);
-    }
-    for (; i < n; ++i) c += p[i] == '\n';
-    return c;
-}
-
-#if defined(__x86_64__)
-__attribute__((target("avx2"))) uint64_t count_nl_avx2(const uint8_t* p, size_t n) {
-    uint64_t c = 0;
-    size_t i = 0;
-    const __m256i nl = _mm256_set1_epi8('\n');
-    for (; i + 128 <= n; i += 128) {
-        const unsigned m0 = (unsigned)_mm256_movemask_epi8(_mm256_cmpeq_epi8(_mm256_loadu_si256((const __m256i*)(p + i)), nl));
-        const unsigned m1 = (unsigned)_mm256_movemask_epi8(_mm256_cmpeq_epi8(_mm256_loadu_si256((const __m256i*)(p + i + 32)), nl));
-        const unsigned m2 = (unsigned)_mm256_movemask_epi8(_mm256_cmpeq_epi8(_mm256_loadu_si256((const __m256i*)(p + i + 64)), nl));
-        const unsigned m3 = (unsigned)_mm256_movemask_epi8(_mm256_cmpeq_epi8(_mm256_loadu_si256((const __m256i*)(p + i + 96)), nl));
-        c += (uint64_t)__builtin_popcountll(((uint64_t)m1 << 32) | m0) + (uint64_t)__builtin_popcountll(((uint64_t)m3 << 32) | m2);
-    }
-    return c + count_nl_generic(p + i, n - i);
-}
-#endif
-
-uint64_t count_nl(const uint8_t* p, size_t n) {
-#if defined(__x86_64__)
-    static const bool have_avx2 = __builtin_cpu_supports("avx2");
-    if (have_avx2) return count_nl_avx2(p, n);
-#endif
-    return count_nl_generic(p, n);
-}
-
-constexpr size_t SUB = 256 << 10;        // newline counts are kept per 256 KiB block
-
-// position just behind the `want`-th newline of p[0, n) (want >= 1) given the per-block counts; n if there are fewer
-size_t locate_nl(const uint8_t* p, size_t n, const std::vector<uint32_t>& cnt, uint64_t want) {
-    uint64_t seen = 0;
-    for (size_t b = 0; b < cnt.size(); ++b) {
-        if (seen + cnt[b] >= want) {
-            size_t i = b * SUB;
-            const size_t end = std::min(n, i + SUB);
-            while (i < end) {
-                const uint8_t* q = (const uint8_t*)memchr(p + i, '\n', end - i);
-                if (!q) break;
-                i = (size_t)(q - p) + 1;
-                if (++seen == want) return i;
-            }
-            return n;      // (counts and bytes disagree: cannot happen)
-        }
-        seen += cnt[b];
-    }
-    return n;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// byte sources: a plain file (parallel pread), a gzip stream (zlib; BGZF / multi-member inputs are inflated
-// member-parallel), or host memory
-// ---------------------------------------------------------------------------------------------------------------
-struct Source {
-    virtual ~Source() {}
-    // fill dst[0, want) with the next bytes of the stream; returns the bytes delivered (< want only at the end)
-    virtual size_t read(uint8_t* dst, size_t want) = 0;
-    // the same, into base[fill, fill + want), ALSO counting the newlines of every SUB-sized block of `base` the new bytes
-    // touch (cnt[b] = newlines in base[b * SUB, min((b + 1) * SUB, fill + got)); the block the old bytes end in is recounted)
-    virtual size_t read_counted(uint8_t* base, size_t fill, size_t want, std::vector<uint32_t>& cnt, Pool* pool) {
-        const size_t got = want ? read(base + fill, want) : 0;
-        count_blocks(base, fill, fill + got, cnt, pool);
-        return got;
-    }
-    virtual bool failed() const { return false; }
-    virtual const char* why() const { return "read error"; }
-    static void count_blocks(const uint8_t* base, size_t from, size_t to, std::vector<uint32_t>& cnt, Pool* pool) {
-        const size_t nb = (to + SUB - 1) / SUB, b0 = std::min(nb, from / SUB);
-        cnt.resize(nb);
-        pool->parallel_for(nb - b0, [&](size_t i) {
-            const size_t o = (b0 + i) * SUB;
-            cnt[b0 + i] = (uint32_t)count_nl(base + o, std::min(SUB, to - o));
-        });
-    }
-};
-
-struct FileSource : Source {
-    int fd = -1;
-    uint64_t pos = 0, size = 0;
-    Pool* pool;
-    bool bad = false;            // sticky: a failed pread is an error, never "end of file"
-    FileSource(const char* path, Pool* p) : pool(p) {
-        fd = open(path, O_RDONLY);
-        if (fd >= 0) {
-            struct stat st;
-            if (fstat(fd, &st) == 0) size = (uint64_t)st.st_size;
-            (void)posix_fadvise(fd, 0, 0, POSIX_FADV_SEQUENTIAL);
-        }
-    }
-    ~FileSource() override { if (fd >= 0) close(fd); }
-    bool failed() const override { return fd < 0 || bad; }
-    size_t read(uint8_t* dst, size_t want) override {
-        std::vector<uint32_t> none;
-        return read_impl(dst, 0, want, nullptr);
-    }
-    // the pieces are cut at multiples of 4 * SUB of `base`, so the thread that pread a piece counts its newlines while
-    // the bytes are still in its cache: one pass, one parallel_for
-    size_t read_counted(uint8_t* base, size_t fill, size_t want, std::vector<uint32_t>& cnt, Pool*) override {
-        return read_impl(base, fill, want, &cnt);
-    }
-    size_t read_impl(uint8_t* base, size_t fill, size_t want, std::vector<uint32_t>* cnt) {
-        const uint64_t left = size > pos ? size - pos : 0;
-        const size_t take = (size_t)std::min<uint64_t>(want, left);
-        const size_t end = fill + take;
-        const size_t PIECE = 4 * SUB;
-        const size_t p0 = fill / PIECE, p1 = (end + PIECE - 1) / PIECE;
-        if (cnt) cnt->resize((end + SUB - 1) / SUB);
-        std::atomic<bool> err{false};
-        pool->parallel_for(p1 > p0 ? p1 - p0 : 0, [&](size_t k) {
-            const size_t lo = std::max(fill, (p0 + k) * PIECE), hi = std::min(end, (p0 + k + 1) * PIECE);
-            size_t off = lo;
-            while (off < hi) {
-                const ssize_t got = pread(fd, base + off, hi - off, (off_t)(pos + (off - fill)));
-                if (got <= 0) { err = true; return; }
-                off += (size_t)got;
-            }
-            if (cnt)
-                for (size_t b = lo / SUB; b * SUB < hi; ++b) (*cnt)[b] = (uint32_t)count_nl(base + b * SUB, std::min(SUB, end - b * SUB));
-        });
-        if (err) { bad = true; return 0; }
-        pos += take;
-        return take;
-    }
-};
-
-// A bzip2 file (fastq.py:25-26: bz2.BZ2File upstream).  libbz2 does the decoding — loaded at run time (dlopen: the image carries the
-// library Python's bz2 module links, not its header) — on threads of its own, so that the pipe's readers, GPUs and writers work
-// while it does: the file is mapped and cut at its STREAM starts ("BZh1".."BZh9" + the block magic, byte aligned: pbzip2 and
-// concatenated files have many, plain bzip2 one); a producer thread decodes windows of streams in parallel on the pool and queues
-// their text in order.  A file that ends inside a stream, or that libbz2 rejects, is an error.  (Every stream is decoded, as
-// python 3's BZ2File does — the path the serial loop takes for .bz2; python 2's reads only the first, qualitycontrol.py:77-78
-// warns about pbzip2 files.)
-struct Bz2Api {
-    struct Stream {
-        char* next_in; unsigned int avail_in, total_in_lo32, total_in_hi32;
-        char* next_out; unsigned int avail_out, total_out_lo32, total_out_hi32;
-        void* state; void* (*bzalloc)(void*, int, int); void (*bzfree)(void*, void*); void* opaque;
-    };
-    int (*init)(Stream*, int, int) = nullptr;
-    int (*step)(Stream*) = nullptr;
-    int (*end)(Stream*) = nullptr;
-    bool ok = false;
-    Bz2Api() {
-        void* h = nullptr;
-        for (const char* name : {"libbz2.so.1.0", "libbz2.so.1", "libbz2.so"})
-            if ((h = dlopen(name, RTLD_NOW | RTLD_GLOBAL))) break;
-        if (!h) return;
-        init = (int (*)(Stream*, int, int))dlsym(h, "BZ2_bzDecompressInit");
-        step = (int (*)(Stream*))dlsym(h, "BZ2_bzDecompress");
-        end = (int (*)(Stream*))dlsym(h, "BZ2_bzDecompressEnd");
-        ok = init && step && end;
-    }
-    static const Bz2Api& get() { static Bz2Api api; return api; }
-};
-
-struct Bz2Source : Source {
-    int fd = -1;
-    Pool* pool;
-    const uint8_t* map = nullptr;
-    size_t size = 0;
-    std::atomic<bool> bad{false}, stop{false};
-    char err[200] = "";
-    std::mutex err_mu;
-    std::vector<size_t> starts;                 // stream starts + the file's size
-    std::thread producer;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<std::vector<uint8_t>> q;         // decoded text, in order
-    size_t q_bytes = 0, front_off = 0;
-    bool done = false;
-
-    void fail(const char* msg) {
-        {
-            std::lock_guard<std::mutex> g(err_mu);
-            if (!bad) snprintf(err, sizeof(err), "%s", msg);
-        }
-        {
-            std::lock_guard<std::mutex> g(mu);
-            bad = true;
-        }
-        cv.notify_all();
-    }
-    Bz2Source(const char* path, Pool* p) : pool(p) {
-        fd = open(path, O_RDONLY);
-        if (fd < 0) { fail("cannot open the file"); return; }
-        struct stat st;
-        if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { fail("not a regular file"); return; }
-        size = (size_t)st.st_size;
-        if (!Bz2Api::get().ok) { fail("libbz2 could not be loaded (dlopen libbz2.so.1.0)"); return; }
-        if (size) {
-            void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m == MAP_FAILED) { fail("cannot map the file"); return; }
-            map = (const uint8_t*)m;
-            (void)madvise(m, size, MADV_SEQUENTIAL);
-            if (size < 10 || memcmp(map, "BZh", 3) != 0) { fail("not a bzip2 file"); return; }
-        }
-        producer = std::thread([this] { produce(); });
-    }
-    ~Bz2Source() override {
-        {
-            std::lock_guard<std::mutex> g(mu);          // (under the lock the producer evaluates its wait predicate with: no lost wake-up)
-            stop = true;
-        }
-        cv.notify_all();
-        if (producer.joinable()) producer.join();
-        if (map) munmap((void*)map, size);
-        if (fd >= 0) close(fd);
-    }
-    bool failed() const override { return bad; }
-    const char* why() const override { return err; }
-
-    static bool stream_start(const uint8_t* p) {
-        static const uint8_t blk[6] = {0x31, 0x41, 0x59, 0x26, 0x53, 0x59}, eos[6] = {0x17, 0x72, 0x45, 0x38, 0x50, 0x90};
-        return p[0] == 'B' && p[1] == 'Z' && p[2] == 'h' && p[3] >= '1' && p[3] <= '9' && (memcmp(p + 4, blk, 6) == 0 || memcmp(p + 4, eos, 6) == 0);
-    }
-    // one stream -> text; false: libbz2 rejected it or it ends early.  *garbage: bytes follow the stream's end inside [a, b) that
-    // are not a stream — python's BZ2File reads up to there and ignores the rest of the FILE (its _compression.DecompressReader
-    // treats data that does not decompress as trailing garbage), so the caller stops behind this stream.
-    // sink != nullptr: the text is handed over in pieces of PIECE bytes as they fill (a big stream never sits in memory whole:
-    // round-5 advisory — a plain `bzip2` file is ONE stream, and the queue's 1 GiB bound only counted whole streams)
-    static constexpr size_t PIECE = 16u << 20;
-    bool decode(size_t a, size_t b, std::vector<uint8_t>& out, bool* garbage, const std::function<bool(std::vector<uint8_t>&&)>* sink = nullptr) {
-        const Bz2Api& api = Bz2Api::get();
-        Bz2Api::Stream z{};
-        if (api.init(&z, 0, 0) != 0) return false;
-        out.resize(sink ? PIECE : std::max<size_t>(1u << 20, (b - a) * 5));
-        size_t produced = 0;
-        z.next_in = (char*)(map + a);
-        size_t in_left = b - a;
-        bool ok = false;
-        for (;;) {
-            if (z.avail_in == 0 && in_left) { z.avail_in = (unsigned)std::min<size_t>(in_left, 1u << 30); in_left -= z.avail_in; }
-            if (out.size() - produced < (1u << 16)) {
-                if (sink) {
-                    out.resize(produced);
-                    if (!(*sink)(std::move(out))) break;                       // (stopped)
-                    out = std::vector<uint8_t>(PIECE);
-                    produced = 0;
-                } else out.resize(out.size() + out.size() / 2);
-            }
-            z.next_out = (char*)out.data() + produced;
-            const size_t room = std::min<size_t>(out.size() - produced, 1u << 30);
-            z.avail_out = (unsigned)room;
-            const int rc = api.step(&z);
-            produced += room - z.avail_out;
-            if (rc == 4) {                                                      // BZ_STREAM_END
-                ok = true;
-                if (garbage) *garbage = z.avail_in != 0 || in_left != 0;
-                break;
-            }
-            if (rc != 0 || (z.avail_in == 0 && in_left == 0 && z.avail_out != 0)) break;   // error, or the stream ends early
-            if (stop) break;
-        }
-        api.end(&z);
-        out.resize(produced);
-        if (ok && sink && produced) ok = (*sink)(std::move(out));
-        return ok;
-    }
-    // decoded text into the queue, in order; false: the reader has gone
-    bool enqueue(std::vector<uint8_t>&& text) {
-        if (text.empty()) return true;
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return stop.load() || q_bytes < (1u << 30); });
-        if (stop) return false;
-        q_bytes += text.size();
-        q.push_back(std::move(text));
-        lk.unlock();
-        cv.notify_all();
-        return true;
-    }
-    void produce() {
-        // stream starts: byte aligned (a stream is padded to a whole byte); ten fixed bytes make a chance hit a 2^-80 event
-        if (size) {
-            const size_t nb = (size + (4u << 20) - 1) / (4u << 20);
-            std::vector<std::vector<size_t>> hits(nb);
-            pool->parallel_for(nb, [&](size_t i) {
-                const size_t lo = i * (4u << 20), hi = std::min(size, lo + (4u << 20));
-                for (size_t o = lo; o < hi && o + 10 <= size; ++o) {
-                    const uint8_t* hit = (const uint8_t*)memchr(map + o, 'B', hi - o);
-                    if (!hit) break;
-                    o = (size_t)(hit - map);
-                    if (o + 10 <= size && stream_start(map + o)) hits[i].push_back(o);
-                }
-            });
-            for (auto& h : hits) starts.insert(starts.end(), h.begin(), h.end());
-            if (starts.empty() || starts[0] != 0) { fail("not a bzip2 file"); starts.clear(); }
-            starts.push_back(size);
-        }
-        // small streams (pbzip2's blocks: <= 900 KB of text each) are decoded whole, a window of them in parallel on the pool; a
-        // big one — the single stream of a plain `bzip2` file — is decoded here, piece by piece, straight into the queue
-        const size_t window = (size_t)std::max(2, pool->size());
-        const size_t BIG = 8u << 20;
-        bool cut = false;                         // garbage behind a stream: python's reader ends the file there
-        for (size_t k = 0; k + 1 < starts.size() && !stop && !bad && !cut;) {
-            if (starts[k + 1] - starts[k] > BIG) {
-                std::vector<uint8_t> out;
-                bool garbage = false;
-                const std::function<bool(std::vector<uint8_t>&&)> sink = [this](std::vector<uint8_t>&& t) { return enqueue(std::move(t)); };
-                if (!decode(starts[k], starts[k + 1], out, &garbage, &sink)) { if (!stop) fail("corrupt or truncated bzip2 stream"); break; }
-                cut = garbage;
-                ++k;
-                continue;
-            }
-            size_t n = 0;
-            while (n < window && k + n + 1 < starts.size() && starts[k + n + 1] - starts[k + n] <= BIG) ++n;
-            std::vector<std::vector<uint8_t>> outs(n);
-            std::vector<char> good(n, 0), junk(n, 0);
-            pool->parallel_for(n, [&](size_t i) { bool g = false; good[i] = decode(starts[k + i], starts[k + i + 1], outs[i], &g) ? 1 : 0; junk[i] = g ? 1 : 0; });
-            for (size_t i = 0; i < n && !bad; ++i) {
-                if (!good[i]) { fail("corrupt or truncated bzip2 stream"); break; }
-                if (!enqueue(std::move(outs[i]))) break;
-                if (junk[i]) { cut = true; break; }
-            }
-            k += n;
-        }
-        {
-            std::lock_guard<std::mutex> g(mu);
-            done = true;
-        }
-        cv.notify_all();
-    }
-    size_t read(uint8_t* dst, size_t want) override {
-        size_t got = 0;
-        while (got < want) {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return !q.empty() || done || bad; });
-            if (bad) return 0;
-            if (q.empty()) break;                                  // done
-            std::vector<uint8_t>& f = q.front();
-            const size_t take = std::min(want - got, f.size() - front_off);
-            lk.unlock();
-            memcpy(dst + got, f.data() + front_off, take);         // (the front buffer is only ever popped by this thread)
-            got += take;
-            lk.lock();
-            front_off += take;
-            if (front_off == f.size()) { q_bytes -= f.size(); q.pop_front(); front_off = 0; lk.unlock(); cv.notify_all(); }
-        }
-        return bad ? 0 : got;
-    }
-};
-
-// A gzip file (fastq.py:23-24 opens it with gzip.open upstream).  The file is mapped; then
-//   * members that carry the BGZF extra field ("BC": the member's compressed size) are located by walking the headers and
-//     inflated independently, in parallel;
-//   * anything else — one big member as gzip / pigz / Python write it, or members without sizes — goes through
-//     aqcgz::ParallelGunzip: speculative sections from block boundaries found in the middle of the stream, committed in order.
-// Every member's CRC-32 and length are checked; a file that ends inside a member is an error (gzip.open raises EOFError).
-std::atomic<uint64_t> g_gz_in_stats[4];      // sections committed / of them from the device / text bytes / of them from the device (process-wide)
-
-struct GzSource : Source {
-    int fd = -1;
-    Pool* pool;
-    const uint8_t* map = nullptr;
-    size_t size = 0;
-    bool bgzf = false, bad = false, mapped = false;
-    char err[200] = "";
-    std::unique_ptr<aqcgz::ParallelGunzip> pg;
-    // BGZF walk
-    size_t pos = 0;
-    std::vector<uint8_t> spill;
-    size_t spill_lo = 0;
-    // fallback for files that cannot be mapped (pipes): one zlib stream
-    std::vector<uint8_t> in;
-    size_t in_lo = 0, in_hi = 0;
-    bool file_eof = false, stream_end = true, any_in_member = false;
-    z_stream zs{};
-    bool zs_init = false;
-
-    GzSource(const char* path, Pool* p, size_t section_bytes = 0, aqcgz::SectionOffload* offload = nullptr) : pool(p) {
-        fd = open(path, O_RDONLY);
-        if (fd < 0) return;
-        struct stat st;
-        if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode)) {
-            size = (size_t)st.st_size;
-            if (size == 0) { mapped = true; return; }
-            void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m != MAP_FAILED) {
-                map = (const uint8_t*)m;
-                mapped = true;
-                (void)madvise(m, size, MADV_SEQUENTIAL);
-                bgzf = is_bgzf_header(map, size);
-                if (!bgzf) {
-                    const int threads = std::max(1, pool->size());
-                    // sections in flight: two per pool thread (a thread decodes two sections alternately, aqc_gunzip.cpp; a single-end
-                    // run has only this stream to keep the pool busy); more only means more symbol buffers touched for the first
-                    // time (tools/gpu_gzrate.sh, GZ_MATRIX)
-                    const int inflight = std::max(4, std::min(2 * threads, 64));
-                    size_t sec = section_bytes;
-                    if (!sec) {
-                        if (const char* e = getenv("AQC_GZ_SECTION")) sec = (size_t)atoll(e);
-                    }
-                    if (!sec) sec = std::min<size_t>(offload ? (1u << 20) : (2u << 20), std::max<size_t>(256u << 10, size / (size_t)(4 * inflight)));
-                    pg.reset(new aqcgz::ParallelGunzip(map, size, pool, inflight, sec, offload));
-                }
-                return;
-            }
-        }
-        in.resize(8 << 20);
-    }
-    ~GzSource() override {
-        if (pg) {
-            g_gz_in_stats[0] += pg->sections_accepted; g_gz_in_stats[1] += pg->offloaded_accepted;
-            g_gz_in_stats[2] += pg->total_out; g_gz_in_stats[3] += pg->offloaded_bytes;
-            if (getenv("AQC_PIPE_DEBUG"))
-                fprintf(stderr, "pipe: gunzip — %llu sections committed (%llu from the device of %llu handed to it), %llu discarded, %.1f MB of %.1f MB decoded sequentially\n",
-                        (unsigned long long)pg->sections_accepted, (unsigned long long)pg->offloaded_accepted, (unsigned long long)pg->sections_offloaded,
-                        (unsigned long long)pg->sections_discarded, 1e-6 * (double)pg->bridged_bytes, 1e-6 * (double)pg->total_out);
-            if (getenv("AQC_PIPE_DEBUG"))
-                fprintf(stderr, "pipe: gunzip consumer, ms inside read() — waiting for a pool section %.1f, for a device section %.1f, for the device to resolve a run %.1f (%.1f MB of text resolved there), for the translation of what it committed + the copies from the device %.1f, handing out work %.1f, committing %.1f, decoding sequentially %.1f\n",
-                        pg->us_wait_pool / 1e3, pg->us_wait_device / 1e3, pg->us_resolve / 1e3, 1e-6 * (double)pg->resident_bytes, pg->us_drain / 1e3, pg->us_top_up / 1e3, pg->us_accept / 1e3, pg->us_bridge / 1e3);
-        }
-        pg.reset();
-        if (map) munmap((void*)map, size);
-        if (zs_init) inflateEnd(&zs);
-        if (fd >= 0) close(fd);
-    }
-    bool failed() const override { return fd < 0 || bad; }
-    const char* why() const override { return err[0] ? err : "read error"; }
-    void fail(const char* what) { if (!bad) snprintf(err, sizeof(err), "%s", what); bad = true; }
-    static bool is_bgzf_header(const uint8_t* h, size_t n) {
-        return n >= 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[10] == 6 && h[11] == 0 && h[12] == 'B' && h[13] == 'C' &&
-               h[14] == 2 && h[15] == 0;
-    }
-    size_t read(uint8_t* dst, size_t want) override {
-        if (bad) return 0;
-        if (!mapped) return read_stream(dst, want);
-        if (size == 0) return 0;
-        if (bgzf) return read_bgzf(dst, want);
-        const size_t got = pg->read(dst, want);
-        if (pg->failed()) { fail(pg->error()); return 0; }
-        return got;
-    }
-
-    // read(), but text that is in device memory stays there and is listed in *segs (one-member files with a device decoder only)
-    bool takes_segments() const { return mapped && !bgzf && pg != nullptr && size != 0; }
-    size_t read_segments(uint8_t* dst, size_t want, std::vector<aqcgz::DevSegment>* segs) {
-        if (bad) return 0;
-        if (!takes_segments()) return read(dst, want);
-        const size_t got = pg->read(dst, want, segs);
-        if (pg->failed()) { fail(pg->error()); return 0; }
-        return got;
-    }
-
-    size_t read_bgzf(uint8_t* dst, size_t want) {
-        size_t out = 0;
-        if (spill_lo < spill.size()) {
-            const size_t k = std::min(want, spill.size() - spill_lo);
-            memcpy(dst, spill.data() + spill_lo, k);
-            spill_lo += k;
-            out = k;
-            if (spill_lo == spill.size()) { spill.clear(); spill_lo = 0; }
-        }
-        struct Blk { size_t coff, clen, isize, ooff; uint32_t crc; };
-        while (out < want && !bad && pos < size) {
-            // walk the members until they cover what is asked for
-            std::vector<Blk> blks;
-            size_t p = pos, total = 0;
-            bool foreign = false;
-            while (p < size && total < (want - out) + (1u << 20)) {
-                // zero bytes between / behind members are padding (Python's gzip module, which upstream reads through, skips them)
-                while (p < size && map[p] == 0) ++p;
-                if (p == size) break;
-                if (!is_bgzf_header(map + p, size - p)) { foreign = true; break; }
-                const size_t bsize = (size_t)(map[p + 16] | (map[p + 17] << 8)) + 1;
-                if (bsize < 26 || p + bsize > size) { fail("truncated BGZF member"); break; }
-                const uint8_t* t = map + p + bsize - 8;
-                uint32_t crc, isz;
-                memcpy(&crc, t, 4); memcpy(&isz, t + 4, 4);
-                // (a BGZF member holds at most 64 KiB of data: a larger ISIZE is a damaged trailer, not a reason to allocate gigabytes)
-                if (isz > 65536u) { fail("corrupt BGZF member (ISIZE beyond 64 KiB)"); break; }
-                blks.push_back(Blk{p + 18, bsize - 18 - 8, (size_t)isz, total, crc});
-                total += isz;
-                p += bsize;
-            }
-            if (bad) break;
-            if (blks.empty()) {
-                if (foreign) {
-                    // a member without the size field behind BGZF ones (cat of different writers): the general decoder takes over
-                    pg.reset(new aqcgz::ParallelGunzip(map + pos, size - pos, pool, std::max(4, pool->size()), 1u << 20));
-                    bgzf = false;
-                    const size_t got = pg->read(dst + out, want - out);
-                    if (pg->failed()) { fail(pg->error()); return 0; }
-                    return out + got;
-                }
-                pos = p;
-                break;
-            }
-            const size_t room = want - out;
-            size_t fit_total = 0;
-            for (auto& b : blks) if (b.ooff + b.isize <= room) fit_total = b.ooff + b.isize;
-            spill.assign(total - fit_total, 0);
-            spill_lo = 0;
-            std::atomic<bool> e{false};
-            uint8_t* const d0 = dst + out;
-            // two members per task, decoded alternately (aqcgz::decode_pair: two dependency chains share one core's issue slots)
-            pool->parallel_for((blks.size() + 1) / 2, [&](size_t t) {
-                const size_t i0 = 2 * t, i1 = std::min(2 * t + 1, blks.size() - 1);
-                uint8_t* o[2];
-                const uint8_t* src[2];
-                size_t n[2], cap[2];
-                int64_t got[2];
-                for (int k = 0; k < 2; ++k) {
-                    const Blk& b = blks[k ? i1 : i0];
-                    o[k] = b.ooff + b.isize <= room ? d0 + b.ooff : spill.data() + (b.ooff - fit_total);
-                    src[k] = map + b.coff; n[k] = b.clen; cap[k] = b.isize;
-                }
-                if (i1 != i0) aqcgz::inflate_raw2(src, n, o, cap, got);
-                else got[0] = got[1] = aqcgz::inflate_raw(src[0], n[0], o[0], cap[0]);
-                for (int k = 0; k < 2; ++k) {
-                    const Blk& b = blks[k ? i1 : i0];
-                    if (got[k] != (int64_t)b.isize || aqcgz::crc32_fast(0u, o[k], b.isize) != b.crc) e = true;
-                }
-            });
-            if (e) { fail("corrupt BGZF member (inflate / CRC-32 / length)"); break; }
-            pos = p;
-            out += fit_total;
-            if (!spill.empty()) {
-                const size_t k = std::min(want - out, spill.size());
-                memcpy(dst + out, spill.data(), k);
-                spill_lo = k;
-                out += k;
-                if (spill_lo == spill.size()) { spill.clear(); spill_lo = 0; }
-            }
-        }
-        return bad ? 0 : out;
-    }
-
-    void refill() {
-        if (in_lo > 0 && in_lo < in_hi) memmove(in.data(), in.data() + in_lo, in_hi - in_lo);
-        in_hi -= in_lo;
-        in_lo = 0;
-        while (!file_eof && in_hi < in.size()) {
-            const ssize_t got = ::read(fd, in.data() + in_hi, in.size() - in_hi);
-            if (got < 0) { fail("read error"); file_eof = true; break; }
-            if (got == 0) { file_eof = true; break; }
-            in_hi += (size_t)got;
-        }
-    }
-    size_t read_stream(uint8_t* dst, size_t want) {
-        size_t out = 0;
-        while (out < want && !bad) {
-            if (in_lo == in_hi) {
-                refill();
-                if (in_lo == in_hi) break;          // end of the file
-            }
-            if (stream_end) {
-                // next member (concatenated members are one gzip file); zero padding behind the last one is ignored
-                while (in_lo < in_hi && in[in_lo] == 0) ++in_lo;
-                if (in_lo == in_hi) continue;
-                if (zs_init) inflateEnd(&zs);
-                memset(&zs, 0, sizeof(zs));
-                if (inflateInit2(&zs, 15 + 16) != Z_OK) { fail("inflateInit2 failed"); break; }
-                zs_init = true;
-                stream_end = false;
-            }
-            zs.next_in = in.data() + in_lo;
-            zs.avail_in = (uInt)std::min<size_t>(in_hi - in_lo, 1u << 30);
-            zs.next_out = dst + out;
-            zs.avail_out = (uInt)std::min<size_t>(want - out, 1u << 30);
-            const uInt ai = zs.avail_in, ao = zs.avail_out;
-            const int rc = inflate(&zs, Z_NO_FLUSH);      // (zlib checks the member's CRC-32 / length itself)
-            in_lo += ai - zs.avail_in;
-            out += ao - zs.avail_out;
-            if (rc == Z_STREAM_END) stream_end = true;
-            else if (rc != Z_OK && rc != Z_BUF_ERROR) { fail("corrupt gzip data"); break; }
-            else if (rc == Z_BUF_ERROR && ai == zs.avail_in && ao == zs.avail_out) {
-                if (file_eof && in_lo == in_hi) break;
-                refill();
-                if (in_lo == in_hi) break;
-            }
-        }
-        // the file ended inside a member: gzip.open raises EOFError there, so do we
-        if (out < want && !bad && !stream_end && file_eof && in_lo == in_hi) fail("gzip stream ends before its trailer (truncated file)");
-        return bad ? 0 : out;
-    }
-};
-
-// An output file.  Measured on the MI355X host (tools/ubench/file_write_rate.cpp): ONE thread issuing large sequential
-// write()s fills a file at 6 GB/s (tmpfs) .. 11 GB/s (page cache); several threads pwrite()-ing disjoint ranges of the same
-// file, or storing into a shared mapping of it, are 2-5x SLOWER (they fight over the file's page-cache lock).  So every
-// output file gets its own writer thread and sees nothing but big sequential writes.
-//
-// Round 6 (tools/ubench/dma_write_rate.hip, profiles/r06_dma_write_rate.txt: what the round-5 review's "26 % the writers lose" is):
-// two files at once take 9.7 - 10.7 GB/s each whatever the source buffer is — lying still or just filled by a D2H copy, on either
-// socket, in pieces of 1 / 4 / 16 / 45 MiB — and 12.0 - 13.0 GB/s once the file's blocks exist: write() into a fresh file spends a
-// fifth of its time allocating them.  So the writer keeps the file's blocks reserved 1 GiB ahead of its position
-// (fallocate(FALLOC_FL_KEEP_SIZE): the size stays what has been written) and gives back what is left over when it closes.
-// AQC_FALLOC=0 switches that off; a filesystem without fallocate does so by itself.
-struct OutFile {
-    int fd = -1;
-    uint64_t pos = 0;
-    uint64_t reserved = 0;       // blocks exist up to here
-    int prealloc = 1;            // 0 off, 1 keep-size, 2 size-extending (the file is cut to `pos` when it closes)
-    bool open_(const char* path) {
-        fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (const char* e = getenv("AQC_FALLOC")) prealloc = e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1;
-        reserved = 0;
-        return fd >= 0;
-    }
-    void reserve_ahead(size_t n) {
-        const uint64_t STEP = 1ull << 30;
-        if (!prealloc || pos + n + (STEP >> 2) <= reserved) return;
-        const uint64_t want = std::max<uint64_t>(reserved, pos) , len = std::max<uint64_t>(STEP, pos + n + (STEP >> 2) - want);
-        if (fallocate(fd, prealloc == 1 ? FALLOC_FL_KEEP_SIZE : 0, (off_t)want, (off_t)len) == 0) reserved = want + len;
-        else prealloc = 0;       // (not supported here / no space for the reservation: plain writes will say what is wrong, if anything)
-    }
-    bool append(const uint8_t* p, size_t n) {
-        reserve_ahead(n);
-        while (n) {
-            const ssize_t w = ::write(fd, p, std::min<size_t>(n, 1u << 30));
-            if (w <= 0) return false;
-            p += w; n -= (size_t)w; pos += (uint64_t)w;
-        }
-        return true;
-    }
-    // the same for a list of pieces (writev, IOV_MAX at a time; pieces of length 0 are the caller's business)
-    bool appendv(std::vector<struct iovec>& iov) {
-        size_t total = 0;
-        for (const struct iovec& v : iov) total += v.iov_len;
-        reserve_ahead(total);
-        size_t i = 0;
-        while (i < iov.size()) {
-            const int cnt = (int)std::min<size_t>(iov.size() - i, 1024);
-            ssize_t w = ::writev(fd, iov.data() + i, cnt);
-            if (w <= 0) return false;
-            pos += (uint64_t)w;
-            while (w > 0 && i < iov.size()) {
-                if ((size_t)w >= iov[i].iov_len) { w -= (ssize_t)iov[i].iov_len; ++i; }
-                else { iov[i].iov_base = (uint8_t*)iov[i].iov_base + w; iov[i].iov_len -= (size_t)w; w = 0; }
-            }
-        }
-        return true;
-    }
-    void close_() {
-        if (fd >= 0) {
-            if (reserved > pos && ftruncate(fd, (off_t)pos) != 0) {}   // (gives the unused reservation back; a size-extending one is cut)
-            close(fd);
-        }
-        fd = -1;
-    }
-};
-
-struct HostBuf {
-    uint8_t* p = nullptr;
-    size_t cap = 0;
-    bool pageable = false;       // (aqc_pipe_split only: plain memory, no GPU runtime involved)
-    void ensure(size_t n) {
-        if (n <= cap) return;
-        release();
-        cap = n + n / 8 + (1 << 20);
-        p = pageable ? (uint8_t*)malloc(cap) : (uint8_t*)aqc_host_alloc(cap);
-        if (!p) cap = 0;
-    }
-    void release() {
-        if (p) { if (pageable) free(p); else aqc_host_free(p); }
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 struct InChunk {
     uint64_t idx = 0;
@@ -821,22 +95,35 @@ struct OutChunk {
     };
     std::shared_ptr<Spans> spans;
     int in_buf[2] = {-1, -1};    // input ring buffers this chunk still holds (spans mode), -1: none
-    // the good output of file f, put together on the host by the slot worker (spans mode "assemble", the default for plain-text
-    // outputs since round 6): the file writer issues ONE write() of it, as for a stream the device formatted
+    // the good output of file f, put together on the host by the slot worker (spans mode "assemble"): the file writer issues
+    // ONE write() of it, as for a stream the device formatted
     const uint8_t* good_ptr[2] = {nullptr, nullptr};
     uint64_t good_bytes[2] = {0, 0};
 };
 
-}  // namespace
+// The good output of one file of a chunk formatted by aqc_format_spans, in order: the chunk's own bytes from the end of one
+// event's record to the start of the next (`own(offset in the chunk, length)`, never of length 0), `out_len` rebuilt bytes at
+// every event (`patch(length)`, once per event, 0 for a bad record), and the chunk's own bytes behind the last event up to `end`.
+// Events [e0, e1) are walked; a walk that does not reach the chunk's tail passes end = 0.
+template <class Own, class Patch>
+inline void walk_spans(const aqc_span_event* ev, size_t e0, size_t e1, uint64_t end, Own&& own, Patch&& patch) {
+    uint64_t cursor = e0 ? (uint64_t)ev[e0 - 1].in_start + ev[e0 - 1].in_len : 0;
+    for (size_t i = e0; i < e1; ++i) {
+        if (ev[i].in_start > cursor) own(cursor, (uint64_t)ev[i].in_start - cursor);
+        patch((uint64_t)ev[i].out_len);
+        cursor = (uint64_t)ev[i].in_start + ev[i].in_len;
+    }
+    if (end > cursor) own(cursor, end - cursor);
+}
 
-// Device decoders of .gz inputs outlive the pipe that made them (round 6): a decoder that has worked holds gigabytes of device
+// Device decoders of .gz inputs outlive the pipe that made them: a decoder that has worked holds gigabytes of device
 // buffers and page-locked stages — freeing them took a one-shot CLI run 34 ms of its pass 2 (two decoders, one after the other),
 // and a folder of inputs (after.py -d: a pipe per file) would set them up again for every file.  A pipe that is destroyed hands
 // its decoders back, the next pipe on that device takes them over warm; they are freed when the process ends.
-namespace {
 struct PooledOffload { int device; size_t group; bool warm; std::unique_ptr<aqcgz::SectionOffload> dec; };
 std::mutex g_offload_mu;
 std::vector<PooledOffload> g_offload_pool;
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -846,11 +133,6 @@ struct aqc_pipe {
     int slots = 2;
     int io_threads = 8;
     std::unique_ptr<Pool> pool;
-    // per input file: ring of page-locked chunk buffers
-    std::vector<HostBuf> in_buf[2];
-    // per worker (ctx, slot): two sets of six output buffers
-    struct WorkerBufs { HostBuf out[2][6]; HostBuf good[2][2]; };       // good[set][file]: assembled good output (plain memory)
-    std::vector<WorkerBufs> wbufs;
     // per input file: the device decoder of its gzip stream (created with the first .gz input, kept: its device buffers and
     // page-locked arenas are as expensive to set up as a whole run)
     std::unique_ptr<aqcgz::SectionOffload> gz_offload[2];
@@ -858,17 +140,32 @@ struct aqc_pipe {
     size_t gz_offload_group[2] = {0, 0};
     bool gz_offload_tried[2] = {false, false};
     bool gz_offload_warm[2] = {false, false};       // the decoder of this file slot has run before: its device buffers and page-locked arenas exist
+    // The buffers come last: they are the first thing `delete` frees (aqc_pipe_destroy), ahead of the decoders and the pool.
+    // per input file: ring of page-locked chunk buffers
+    std::vector<HostBuf> in_buf[2];
+    // per worker (ctx, slot): two sets of six output buffers
+    struct WorkerBufs { HostBuf out[2][6]; HostBuf good[2][2]; };       // good[set][file]: assembled good output (plain memory)
+    std::vector<WorkerBufs> wbufs;
 };
 
 namespace {
 
 struct Run {
+    // ---- what the run is given ------------------------------------------------------------------------------------------------
     aqc_pipe* P;
     const aqc_pipe_io* io;
     const aqc_pipe_opts* opt;
     aqc_pipe_result* res;
     int nf = 1;
     uint64_t K = 0;
+    // ---- what it reads from the environment when it starts (Run::Run; the knobs of a .gz input: open_source) --------------------
+    bool dbg = false;                  // AQC_PIPE_DEBUG
+    bool spans_on = false;             // plain-text output: good records that go out as their own bytes are not copied on the device (aqc_format_spans) ...
+    bool spans_assemble = false;       // ... and the slot worker puts each good file's chunk together on the host (else: the file writers writev the pieces)
+    bool gz_on_device = false;
+    int io_node = -1;                  // the NUMA node every context's GPU hangs off (-1: they differ, or unknown): readers, the dispatcher, the
+                                       // commit thread and the file writers run there too, next to the rings they fill and drain
+    // ---- how it ends --------------------------------------------------------------------------------------------------------
     std::atomic<bool> abort{false}, anomaly{false};
     std::mutex err_mu;
     std::string err;
@@ -878,17 +175,15 @@ struct Run {
     std::string fatal_err;
     int fatal_code = 0;
 
-    // reader -> dispatcher
+    // ---- readers -> dispatcher: chunks in input buffer rings ------------------------------------------------------------------------
     std::unique_ptr<BQueue<InChunk>> inq[2];
-    // input buffer rings
     std::mutex ring_mu[2];
     std::condition_variable ring_cv[2];
     std::vector<char> ring_free[2];
-    // dispatcher -> workers (one queue per context)
+
+    // ---- dispatcher -> slot workers (one queue per context) -------------------------------------------------------------------------
     struct Job { InChunk c[2]; uint64_t idx; bool last; uint64_t ticket; };
     std::vector<std::unique_ptr<BQueue<Job>>> jobq;
-    // workers -> writer
-    BQueue<OutChunk> outq{0};
     // DMA gates, one pair per physical device: the uploads (and the downloads) of the chunks dealt to ONE device start in
     // chunk order and at most `slots` of them run at a time.  With one context per GPU that never blocks; with several
     // contexts on one device it keeps a dozen transfers from sharing the link equally and all finishing late, which
@@ -901,34 +196,8 @@ struct Run {
     std::vector<std::unique_ptr<Gate>> up_gate, down_gate;
     std::vector<int> group_of_ctx;
     std::vector<uint64_t> group_tickets;
-    bool gate_enter(Gate& g, uint64_t ticket, uint64_t width) {
-        std::unique_lock<std::mutex> lk(g.mu);
-        g.cv.wait(lk, [&] { return abort.load() || (g.started == ticket && ticket < g.finished + width); });
-        if (abort) return false;
-        g.started++;
-        return true;
-    }
-    void gate_leave(Gate& g) {
-        {
-            std::lock_guard<std::mutex> lk(g.mu);
-            g.finished++;
-        }
-        g.cv.notify_all();
-    }
-    // output set ownership
-    std::mutex set_mu;
-    std::condition_variable set_cv;
-    std::vector<char> set_free;        // [worker * 2 + set]
-    bool gz_on_device = false;
-    int io_node = -1;                  // the NUMA node every context's GPU hangs off (-1: they differ, or unknown): readers, the dispatcher, the
-                                       // commit thread and the file writers run there too, next to the rings they fill and drain
-    void bind_io_thread(const char* what) {
-        const int bound = aqc_bind_thread_to_node(io_node);
-        if (getenv("AQC_PIPE_DEBUG"))
-            fprintf(stderr, "pipe: %s thread — NUMA node %d, %s\n", what, io_node, bound ? "bound to that node's CPUs" : "not bound (contexts on several nodes, single node, unknown, or AQC_PIPE_NUMA=0)");
-    }
-    bool spans_on = false;             // plain-text output: good records that go out as their own bytes are not copied on the device (aqc_format_spans) ...
-    bool spans_assemble = false;       // ... and the slot worker puts each good file's chunk together on the host (else: the file writers writev the pieces)
+
+    // ---- among the slot workers, in chunk order: the end of the input, the QC turn ------------------------------------------------------
     // End of input inside the pipe (fastq.py:37-49, preprocesser.py:412-429).  A chunk is RUN only once every chunk before it has been
     // framed and found to continue the input: the chunk in which the input ends (an empty line, a partial last record, a mate file
     // that is shorter) becomes the run's last, chunks behind it are dropped before anything of them reaches a counter.
@@ -937,22 +206,107 @@ struct Run {
     uint64_t framed_next = 0, end_chunk = UINT64_MAX;
     std::atomic<bool> ended{false};        // the input has ended in a chunk: readers and the dispatcher stop feeding
     uint64_t extra_bases = 0;
-    void end_input() {
-        ended = true;
-        for (int f = 0; f < 2; ++f) {
-            if (inq[f]) inq[f]->close();
-            ring_cv[f].notify_all();
-        }
-    }
     // QC turn taking (post-filter sampling must be issued in chunk order, see aqc_qc_stat's time keys)
     std::mutex qc_mu;
     std::condition_variable qc_cv;
     uint64_t qc_next = 0;
-    // outputs
+
+    // ---- slot workers -> commit thread: chunks in output buffer sets --------------------------------------------------------------------
+    BQueue<OutChunk> outq{0};
+    std::mutex set_mu;
+    std::condition_variable set_cv;
+    std::vector<char> set_free;        // [worker * 2 + set]
+
+    // ---- commit thread -> file writers ----------------------------------------------------------------------------------------------
+    // a committed chunk on its way through the per-file writer threads; the last one to finish hands the buffer set back
+    struct Commit {
+        OutChunk oc;
+        std::atomic<int> remaining{0};
+    };
+    std::unique_ptr<BQueue<std::shared_ptr<Commit>>> fileq[6];
     OutFile out[6];
+    // (file, chunk) writes handed to the file writers / finished by them: the run that dies at a record stops the pipe only once
+    // EVERY chunk committed before it has reached its files (waiting for the fatal chunk's own files alone let stop_all() cancel
+    // earlier chunks still queued on a file the fatal chunk does not write to)
+    std::atomic<uint64_t> writes_queued{0}, writes_done{0};
+    std::shared_ptr<Commit> fatal_commit;
+
+    // ---- what it reports ------------------------------------------------------------------------------------------------------------
     std::atomic<uint64_t> records{0};
     std::atomic<uint64_t> ns_read{0}, ns_count{0}, ns_frame{0}, ns_kernels{0}, ns_fetch{0}, ns_write{0}, ns_wait_set{0}, ns_wait_ring{0};
+    // (AQC_PIPE_DEBUG: CPU seconds per kind of thread, printed at the end — who uses the host's cores)
+    std::atomic<long> cpu_us[5] = {{0}, {0}, {0}, {0}, {0}};       // file writers, readers, dispatcher, slot workers, commit thread
+    double cpu_proc0 = 0, cpu_pool0 = 0;
 
+    // ---- set-up: queues, ring occupancy, gates by physical device, the I/O threads' node, the modes of the output -----------------------
+    // only_file >= 0: the run of ONE reader and nothing else (aqc_pipe_split: a pipe without contexts, `opt` without output)
+    Run(aqc_pipe* pipe, const aqc_pipe_io* io_, const aqc_pipe_opts* opt_, aqc_pipe_result* res_, int only_file = -1)
+        : P(pipe), io(io_), opt(opt_), res(res_) {
+        nf = (only_file < 0 && (io->in_path[1] || io->in_mem[1])) ? 2 : 1;
+        K = opt->chunk_records ? opt->chunk_records : (1u << 17);
+        dbg = getenv("AQC_PIPE_DEBUG") != nullptr;
+        {
+            // Plain-text outputs, OPT-IN: the good records that go out as their own bytes never leave the host (aqc_format_spans): no copy
+            // on the device (the device step of 10 M reads 4.7 -> 3.2 ms, 17.3 -> 10.7 GB of HBM traffic), no download (3.1 of the
+            // 3.44 GB per 10 M reads stay off PCIe: pinned -> pinned 105 -> 122 - 160 Mreads/s).  Two ways to get them into the good files:
+            //   AQC_SPANS=1  writev: the file writers writev the pieces straight from the input buffers — no host copy, but a
+            //                run of whole records is 3 - 4 KB in the bench workload and an iovec costs the kernel ~60 ns: 9.2 - 9.9 GB/s
+            //                against write()'s 11 - 12 on a path bound by exactly those two writers (file -> file 0.18 -> 0.23 s,
+            //                profiles/r05_spans_ab.txt);
+            //   AQC_SPANS=2  assemble: the slot worker puts each good file's chunk together in host memory — the chunk's own
+            //                bytes between the events, the rebuilt records at them, copied on the pool in ~1 MiB tasks — and the file
+            //                writer issues one big write() as it always did.  Tried as the DEFAULT and taken back: interleaved on one
+            //                box the text step gives 50.2 - 51.4 Mreads/s, this 39.6 - 48.2 (two inputs at once: 72 - 76 against 55 - 68;
+            //                the 100 M-read input 19 against 44 - 52; profiles/r06_spans_assemble_ab.txt) — the host copies every
+            //                output byte once more, on the 16 granted CPUs that the readers' and the writers' own copies already
+            //                share, and the writers then read buffers that pool threads of either socket have just written.
+            // So the DEFAULT stays the text step (aqc_format: everything formatted on the device and downloaded): a run is bound by its
+            // two file writers, and the text step is what leaves them alone.  Both spans modes pay where PCIe or the device is the
+            // bound and the host has cycles to spare.  (.gz output needs the whole text on the device, where its members are built; a
+            // .gz input decoded on the device keeps its text in HBM and has no host copy to assemble from.)
+            const char* e = getenv("AQC_SPANS");
+            spans_on = !io->gzip_out && !opt->no_output && e && (e[0] == '1' || e[0] == '2');
+            spans_assemble = spans_on && e[0] == '2';
+        }
+        // .gz output: the members are made on the device (aqc_gzdev.hpp) and come back compressed — no host CPU for
+        // deflate, a third of the bytes over PCIe.  --compression 0 (stored) and AQC_GZ_DEVICE=0 keep the host codec.
+        gz_on_device = io->gzip_out && io->gzip_level >= 1 && !opt->no_output && env_on("AQC_GZ_DEVICE");
+        for (int f = 0; f < 2; ++f) {
+            if (only_file < 0 ? f >= nf : f != only_file) continue;
+            inq[f].reset(new BQueue<InChunk>(2));
+            // (the whole ring only when chunks keep their input buffers until they are written — spans mode; else one buffer per slot + two:
+            //  every buffer used is a buffer page-locked, which a one-shot run pays for)
+            const size_t use = (spans_on && !spans_assemble) ? P->in_buf[f].size() : std::min(P->in_buf[f].size(), (size_t)(P->n_ctx * P->slots + 2));
+            ring_free[f].assign(P->in_buf[f].size(), 0);
+            for (size_t i = 0; i < use; ++i) ring_free[f][i] = 1;
+        }
+        for (int i = 0; i < P->n_ctx; ++i) jobq.emplace_back(new BQueue<Job>((size_t)P->slots));
+        set_free.assign(P->wbufs.size() * 2, 1);
+        for (int q = 0; q < 6; ++q) fileq[q].reset(new BQueue<std::shared_ptr<Commit>>(0));
+        // contexts on the same physical device share one pair of DMA gates
+        std::vector<int> devs;
+        for (int i = 0; i < P->n_ctx; ++i) {
+            const int dv = aqc_device_index(P->ctx[i]);
+            int g = -1;
+            for (size_t k = 0; k < devs.size(); ++k) if (devs[k] == dv) g = (int)k;
+            if (g < 0) { g = (int)devs.size(); devs.push_back(dv); }
+            group_of_ctx.push_back(g);
+        }
+        for (size_t k = 0; k < devs.size(); ++k) { up_gate.emplace_back(new Gate()); down_gate.emplace_back(new Gate()); }
+        group_tickets.assign(devs.size(), 0);
+        // one node for the I/O threads when every context's GPU hangs off the same one
+        io_node = P->n_ctx > 0 ? aqc_device_numa_node(P->ctx[0]) : -1;
+        for (int i = 1; i < P->n_ctx; ++i)
+            if (aqc_device_numa_node(P->ctx[i]) != io_node) io_node = -1;
+    }
+
+    void bind_io_thread(const char* what) {
+        const int bound = aqc_bind_thread_to_node(io_node);
+        if (dbg)
+            fprintf(stderr, "pipe: %s thread — NUMA node %d, %s\n", what, io_node, bound ? "bound to that node's CPUs" : "not bound (contexts on several nodes, single node, unknown, or AQC_PIPE_NUMA=0)");
+    }
+
+    // ---- ending the run ---------------------------------------------------------------------------------------------------------
     void fail(int code, const char* fmt, ...) {
         char buf[400];
         va_list ap;
@@ -965,12 +319,22 @@ struct Run {
         }
         stop_all();
     }
-    void stop_all() {
-        abort = true;
+    // the failures several stages share (false: so that a stage can `return no_memory(n);`)
+    bool no_memory(size_t n) { fail(AQC_ERR_HIP, "page-locked allocation of %zu bytes failed", n); return false; }
+    bool device_copy_failed(int f) { fail(AQC_ERR_HIP, "%s: copying decoded text from the device failed", io->in_path[f]); return false; }
+    void close_input() {
         for (int f = 0; f < 2; ++f) {
             if (inq[f]) inq[f]->close();
             ring_cv[f].notify_all();
         }
+    }
+    void end_input() {
+        ended = true;
+        close_input();
+    }
+    void stop_all() {
+        abort = true;
+        close_input();
         for (auto& q : jobq) q->close();
         outq.close();
         for (int q = 0; q < 6; ++q) if (fileq[q]) fileq[q]->close();
@@ -981,6 +345,7 @@ struct Run {
         for (auto& g : down_gate) { std::lock_guard<std::mutex> lk(g->mu); g->cv.notify_all(); }
     }
 
+    // ---- input buffer rings -----------------------------------------------------------------------------------------------------
     int acquire_ring(int f) {
         std::unique_lock<std::mutex> lk(ring_mu[f]);
         int got = -1;
@@ -1002,167 +367,252 @@ struct Run {
         }
         ring_cv[f].notify_all();
     }
+    // A ring buffer in one owner's hands: it goes back to the ring when the owner is done with it — on every way out — unless it
+    // has been handed on (to the chunk that travels on with it).  i < 0: none (a zero-copy chunk of a memory source).
+    struct RingHold {
+        Run& r;
+        const int f;
+        int i;
+        RingHold(Run& run, int file, int index = -1) : r(run), f(file), i(index) {}
+        RingHold(const RingHold&) = delete;
+        RingHold& operator=(const RingHold&) = delete;
+        ~RingHold() { release(); }
+        void release() { r.release_ring(f, i); i = -1; }
+        int hand_on() { const int k = i; i = -1; return k; }
+        explicit operator bool() const { return i >= 0; }
+        HostBuf& buf() const { return r.P->in_buf[f][(size_t)i]; }
+    };
 
-    // ---- reader: chunks of exactly K records -------------------------------------------------------------------------
+    // ---- DMA gates ----------------------------------------------------------------------------------------------------------------
+    // A turn at a gate: entered in ticket order, left when the pass goes out of scope (or earlier: leave()).
+    struct GatePass {
+        Run& r;
+        Gate* g = nullptr;
+        explicit GatePass(Run& run) : r(run) {}
+        GatePass(const GatePass&) = delete;
+        GatePass& operator=(const GatePass&) = delete;
+        ~GatePass() { leave(); }
+        bool held() const { return g != nullptr; }
+        bool enter(Gate& gate, uint64_t ticket) {      // false: the run is stopping
+            std::unique_lock<std::mutex> lk(gate.mu);
+            gate.cv.wait(lk, [&] { return r.abort.load() || (gate.started == ticket && ticket < gate.finished + (uint64_t)r.P->slots); });
+            if (r.abort) return false;
+            gate.started++;
+            g = &gate;
+            return true;
+        }
+        void leave() {
+            if (!g) return;
+            {
+                std::lock_guard<std::mutex> lk(g->mu);
+                g->finished++;
+            }
+            g->cv.notify_all();
+            g = nullptr;
+        }
+    };
+
+    // ---- output buffer sets: a slot worker fills one while the files drain its other ------------------------------------------------------
+    bool acquire_set(int wid, int set) {      // waits for the writers to hand the set back; false: the run is stopping
+        std::unique_lock<std::mutex> lk(set_mu);
+        set_cv.wait(lk, [&] { return abort || set_free[wid * 2 + set]; });
+        if (abort) return false;
+        set_free[wid * 2 + set] = 0;
+        return true;
+    }
+    void release_set(const OutChunk& oc) {
+        for (int f = 0; f < 2; ++f) release_ring(f, oc.in_buf[f]);       // (spans mode: the chunk's input buffers were its good records)
+        if (oc.set < 0) return;
+        {
+            std::lock_guard<std::mutex> g(set_mu);
+            set_free[oc.worker * 2 + oc.set] = 1;
+        }
+        set_cv.notify_all();
+    }
+
+    // ---- readers: chunks of exactly K records ---------------------------------------------------------------------------------------
+    // Three of them — over memory, over a byte source into ring buffers, over a .gz whose device-decoded text stays in HBM — which
+    // differ in how they count line feeds.  What a chunk's buffer holds at first, how it grows and how a chunk is closed is the same.
+    size_t estimate(double est, size_t slack) const { return (size_t)(est * 1.02 * (double)K) + slack; }      // bytes of K records of `est` bytes
+    // the next ring buffer of file f, with room for the estimate (and for what the last chunk left behind its cut); false: the reader ends
+    bool open_chunk(RingHold& rb, double est, size_t carried, size_t& cap) {
+        const uint64_t tw = now_ns();
+        rb.i = acquire_ring(rb.f);
+        ns_wait_ring += now_ns() - tw;
+        if (!rb) return false;
+        cap = estimate(est, 256 << 10);
+        if (cap < carried + (1 << 20)) cap = carried + (1 << 20);
+        rb.buf().ensure(cap);
+        return rb.buf().p ? true : no_memory(cap);
+    }
+    // the records are longer than estimated: a bigger buffer, keep what is there
+    bool grow_chunk(HostBuf& hb, size_t& cap, size_t fill) {
+        const size_t ncap = cap + cap / 2 + (4 << 20);
+        if (!hb.grow(ncap, fill)) return no_memory(ncap);
+        cap = ncap;
+        return true;
+    }
+    // The chunk is cut (idx, data, bytes are set): `lines` line feeds were seen up to the cut or the end, `final` says that nothing
+    // of the input is left.  Counts the unterminated last line, refines the estimate, passes the chunk — and its ring buffer — on.
+    // false: the reader's loop ends (this was the last chunk, or nobody takes chunks any more).
+    bool close_chunk(InChunk& c, RingHold& rb, uint64_t lines, bool final, uint8_t last_byte, double& est) {
+        const uint64_t want_lines = 4 * K;
+        c.lines = std::min<uint64_t>(lines, want_lines);
+        c.final = final;
+        if (final && c.bytes > 0 && last_byte != '\n' && lines < want_lines) c.lines += 1;     // unterminated last line
+        if (c.lines >= 4 && c.bytes) est = (double)c.bytes / (double)(c.lines / 4);
+        c.buf = rb.i;
+        if (!inq[rb.f]->push(c)) return false;
+        rb.hand_on();
+        return !final;
+    }
+
     void reader(int f) {
         bind_io_thread(f == 0 ? "reader (file 1)" : "reader (file 2)");     // (the ring buffers it allocates are first touched here)
-        const bool mem = io->in_mem[f] != nullptr;
+        if (io->in_mem[f]) { read_memory(f); return; }
+        GzSource* stretches = nullptr;
+        std::unique_ptr<Source> src = open_source(f, &stretches);
+        if (!src) return;
+        if (stretches) read_stretches(f, stretches, aqc_device_index(P->ctx[(size_t)f % P->ctx.size()]));
+        else read_source(f, *src);
+    }
+
+    // The byte source of input file f (nullptr: there is none — the run has been stopped).  *stretches: it is a .gz the device decodes
+    // and whose text is to stay there (read_stretches).
+    std::unique_ptr<Source> open_source(int f, GzSource** stretches) {
         std::unique_ptr<Source> src;
-        if (!mem) {
-            if (io->gzip_in[f] == 2 && !Bz2Api::get().ok) {
+        if (io->gzip_in[f] == 2) {
+            if (!Bz2Api::get().ok) {
                 // no libbz2 to load: not an error of the input — the caller's serial loop reads .bz2 through python's own module
                 anomaly = true;
                 stop_all();
-                return;
+                return nullptr;
             }
-            if (io->gzip_in[f] == 2) src.reset(new Bz2Source(io->in_path[f], P->pool.get()));
-            else if (io->gzip_in[f]) {
-                // gzip input: the GPUs take groups of sections off the pool's hands (file f -> the device of context f % n)
-                const char* e = getenv("AQC_GZ_DEVICE_IN");
-                if (!(e && e[0] == '0') && !P->gz_offload_tried[f] && !P->ctx.empty()) {      // (set up with the first .gz input of this file slot)
-                    P->gz_offload_tried[f] = true;
-                    size_t group = 96u << 20;       // (measured, warm pipe, 0.59 GB inputs: groups of 16 / 32 / 96 MiB = 34 / 38 / 42.5 Mreads/s — profiles/r06_gz_hbm_ab.txt)
-                    if (const char* g = getenv("AQC_GZ_GROUP")) group = (size_t)std::max(1ll, atoll(g));
-                    const int dev = aqc_device_index(P->ctx[(size_t)f % P->ctx.size()]);
-                    {
-                        std::lock_guard<std::mutex> g(g_offload_mu);
-                        for (size_t i = 0; i < g_offload_pool.size(); ++i)
-                            if (g_offload_pool[i].device == dev && g_offload_pool[i].group == group) {
-                                P->gz_offload[f] = std::move(g_offload_pool[i].dec);
-                                P->gz_offload_warm[f] = g_offload_pool[i].warm;
-                                g_offload_pool.erase(g_offload_pool.begin() + (long)i);
-                                break;
-                            }
-                    }
-                    if (!P->gz_offload[f]) P->gz_offload[f].reset(aqcgz::make_device_offload(dev, group));
-                    P->gz_offload_device[f] = dev;
-                    P->gz_offload_group[f] = group;
+            src.reset(new Bz2Source(io->in_path[f], P->pool.get()));
+        } else if (io->gzip_in[f]) {
+            // gzip input: the GPUs take groups of sections off the pool's hands (file f -> the device of context f % n)
+            const bool device_in = env_on("AQC_GZ_DEVICE_IN");
+            if (device_in && !P->gz_offload_tried[f] && !P->ctx.empty()) take_offload(f);      // (set up with the first .gz input of this file slot)
+            // Which files the device is asked for.  A cold decoder — buffers by need (2 - 3 GB for groups of 62 MiB), set up in the
+            // background while the pool keeps every section (SectionOffload::prepare), markers + CRC-32 resolved on the device — is
+            // started for every input of >= 448 MiB compressed (about 8 M reads).  Measured through the CLI, a fresh process per
+            // run (profiles/r06_gz_cold_cli.txt): 10 M reads in two files of 0.59 GB — pass 2 0.37 - 0.41 s with the device,
+            // 0.40 - 0.47 s with the pool alone; 4 M reads of the config-5 flavour in two files of 0.36 GB — 0.41 against 0.33 s:
+            // a run of a quarter of a second is over before the decoder has paid for its set-up.  A warm one — the pipe object has
+            // decoded a .gz input of this slot with it before: a service, a folder of files, bench.py — for everything the pool
+            // would need longer for than a group takes the device (48 MiB).  AQC_GZ_DEVICE_MIN=<bytes> sets the limit for both.
+            // (How the limit came down from 4 GiB: DESIGN.md §4, profiles/r05_gz_cold_decoder.txt.)
+            size_t dev_min = P->gz_offload_warm[f] ? (size_t)(48u << 20) : (size_t)(448u << 20);
+            if (const char* m = getenv("AQC_GZ_DEVICE_MIN")) dev_min = (size_t)std::max(0ll, atoll(m));
+            struct stat gst;
+            const bool use_dev = device_in && P->gz_offload[f] && stat(io->in_path[f], &gst) == 0 && (size_t)gst.st_size >= dev_min;
+            if (use_dev) P->gz_offload_warm[f] = true;
+            GzSource* gs = new GzSource(io->in_path[f], P->pool.get(), 0, use_dev ? P->gz_offload[f].get() : nullptr);
+            src.reset(gs);
+            // the text of the sections the device decodes stays in HBM and is framed from there — for the chunks that are dealt
+            // to the decoder's own device, with plain chunk buffers (the spans mode writes good records FROM them)
+            if (use_dev && !gs->failed() && gs->takes_segments() && !spans_on && env_on("AQC_GZ_HBM")) { *stretches = gs; return src; }
+        } else src.reset(new FileSource(io->in_path[f], P->pool.get()));
+        if (src->failed()) { fail(AQC_ERR_ARG, "cannot open %s", io->in_path[f]); return nullptr; }
+        return src;
+    }
+    // the device decoder of file slot f: a warm one from the pool of decoders earlier pipes left, or a new one
+    void take_offload(int f) {
+        P->gz_offload_tried[f] = true;
+        size_t group = 96u << 20;       // (measured, warm pipe, 0.59 GB inputs: groups of 16 / 32 / 96 MiB = 34 / 38 / 42.5 Mreads/s — profiles/r06_gz_hbm_ab.txt)
+        if (const char* g = getenv("AQC_GZ_GROUP")) group = (size_t)std::max(1ll, atoll(g));
+        const int dev = aqc_device_index(P->ctx[(size_t)f % P->ctx.size()]);
+        {
+            std::lock_guard<std::mutex> g(g_offload_mu);
+            for (size_t i = 0; i < g_offload_pool.size(); ++i)
+                if (g_offload_pool[i].device == dev && g_offload_pool[i].group == group) {
+                    P->gz_offload[f] = std::move(g_offload_pool[i].dec);
+                    P->gz_offload_warm[f] = g_offload_pool[i].warm;
+                    g_offload_pool.erase(g_offload_pool.begin() + (long)i);
+                    break;
                 }
-                // Which files the device is asked for.  Until round 5 its first use in a process cost more than a run of 10 M reads
-                // takes (~40 GB of device buffers sized for the worst case, hipMalloc at 16 ms per GB, with the consumer waiting for
-                // the groups the allocating lanes had been handed: profiles/r05_gz_cold_decoder.txt), so a cold decoder was kept for
-                // inputs of >= 4 GiB.  Round 6: buffers by need (2 - 3 GB for groups of 62 MiB), set up in the background while the
-                // pool keeps every section (SectionOffload::prepare), markers + CRC-32 resolved on the device — a cold decoder is
-                // started for every input of >= 448 MiB compressed (about 8 M reads).  Measured through the CLI, a fresh process per
-                // run (profiles/r06_gz_cold_cli.txt): 10 M reads in two files of 0.59 GB — pass 2 0.37 - 0.41 s with the device,
-                // 0.40 - 0.47 s with the pool alone; 4 M reads of the config-5 flavour in two files of 0.36 GB — 0.41 against 0.33 s:
-                // a run of a quarter of a second is over before the decoder has paid for its set-up.  A warm one — the pipe object has decoded a .gz input of this slot with it before: a service, a folder of
-                // files, bench.py — for everything the pool would need longer for than a group takes the device (48 MiB).
-                // AQC_GZ_DEVICE_MIN=<bytes> sets the limit for both.
-                size_t dev_min = P->gz_offload_warm[f] ? (size_t)(48u << 20) : (size_t)(448u << 20);
-                if (const char* m = getenv("AQC_GZ_DEVICE_MIN")) dev_min = (size_t)std::max(0ll, atoll(m));
-                struct stat gst;
-                const bool big = P->gz_offload[f] && stat(io->in_path[f], &gst) == 0 && (size_t)gst.st_size >= dev_min;
-                if (big && !(e && e[0] == '0')) P->gz_offload_warm[f] = true;
-                const bool use_dev = big && !(e && e[0] == '0');
-                GzSource* gs = new GzSource(io->in_path[f], P->pool.get(), 0, use_dev ? P->gz_offload[f].get() : nullptr);
-                src.reset(gs);
-                // the text of the sections the device decodes stays in HBM and is framed from there (round 6) — for the chunks
-                // that are dealt to the decoder's own device, with plain chunk buffers (the spans mode writes good records FROM them)
-                const char* h = getenv("AQC_GZ_HBM");
-                if (use_dev && !gs->failed() && gs->takes_segments() && !spans_on && !(h && h[0] == '0')) {
-                    reader_gz(f, gs, aqc_device_index(P->ctx[(size_t)f % P->ctx.size()]));
-                    return;
-                }
-            }
-            else src.reset(new FileSource(io->in_path[f], P->pool.get()));
-            if (src->failed()) { fail(AQC_ERR_ARG, "cannot open %s", io->in_path[f]); return; }
         }
-        const uint64_t want_lines = 4 * K;
+        if (!P->gz_offload[f]) P->gz_offload[f].reset(aqcgz::make_device_offload(dev, group));
+        P->gz_offload_device[f] = dev;
+        P->gz_offload_group[f] = group;
+    }
+
+    // host memory: zero-copy chunks, counted over a span that grows until it holds K records
+    void read_memory(int f) {
+        const uint64_t want_lines = 4 * K, total = io->in_mem_bytes[f];
         double est = 360.0;                 // bytes per record, refined after the first chunk
         uint64_t mpos = 0;
+        for (uint64_t idx = 0; !abort; ++idx) {
+            const uint8_t* base = io->in_mem[f] + mpos;
+            const uint64_t left = total - mpos;
+            uint64_t span = std::min<uint64_t>(left, estimate(est, 64 << 10));
+            std::vector<uint32_t> cnt;
+            uint64_t lines = 0;
+            for (;;) {
+                const size_t b0 = cnt.size(), b1 = (size_t)((span + SUB - 1) / SUB);
+                cnt.resize(b1);
+                P->pool->parallel_for(b1 - b0, [&](size_t i) {
+                    const size_t o = (b0 + i) * SUB;
+                    cnt[b0 + i] = (uint32_t)count_nl(base + o, (size_t)std::min<uint64_t>(SUB, span - o));
+                });
+                lines = 0;
+                for (auto v : cnt) lines += v;
+                if (lines >= want_lines || span == left) break;
+                const uint64_t nspan = std::min<uint64_t>(left, span + span / 2 + (1 << 20));
+                // recount the (partial) last block of the old span together with the new bytes
+                if (!cnt.empty()) cnt.pop_back();
+                span = nspan;
+            }
+            InChunk c;
+            c.idx = idx;
+            c.data = base;
+            c.bytes = lines >= want_lines ? locate_nl(base, (size_t)span, cnt, want_lines) : span;
+            mpos += c.bytes;
+            RingHold none(*this, f);
+            if (!close_chunk(c, none, lines, mpos == total, c.bytes ? base[c.bytes - 1] : (uint8_t)'\n', est)) break;
+        }
+        inq[f]->close();
+    }
+
+    // a byte source: into ring buffers, counted per block by the thread that fetched the piece (Source::read_counted)
+    void read_source(int f, Source& src) {
+        const uint64_t want_lines = 4 * K;
+        double est = 360.0;                 // bytes per record, refined after the first chunk
         std::vector<uint8_t> carry;
         bool eof = false;
         for (uint64_t idx = 0; !abort; ++idx) {
+            RingHold rb(*this, f);
+            size_t cap = 0;
+            if (!open_chunk(rb, est, carry.size(), cap)) return;
+            HostBuf& hb = rb.buf();
+            size_t fill = carry.size();
+            if (fill) memcpy(hb.p, carry.data(), fill);
+            carry.clear();
+            std::vector<uint32_t> cnt;
+            uint64_t lines = 0;
+            if (fill) Source::count_blocks(hb.p, 0, fill, cnt, P->pool.get());      // the carried-over bytes
+            for (;;) {
+                if (!eof && fill < hb.cap) {
+                    const size_t want = std::min(hb.cap, cap) - fill;
+                    const uint64_t tr = now_ns();
+                    // (bytes and their per-block newline counts in one go: the thread that fetched a piece counts it)
+                    const size_t got = want ? src.read_counted(hb.p, fill, want, cnt, P->pool.get()) : 0;
+                    ns_read += now_ns() - tr;
+                    if (src.failed()) { fail(AQC_ERR_ARG, "%s: %s", io->in_path[f], src.why()); return; }
+                    if (got < want) eof = true;
+                    fill += got;
+                }
+                lines = 0;
+                for (auto v : cnt) lines += v;
+                if (lines >= want_lines || eof) break;
+                if (!grow_chunk(hb, cap, fill)) return;
+            }
             InChunk c;
             c.idx = idx;
-            if (mem) {
-                const uint8_t* base = io->in_mem[f] + mpos;
-                const uint64_t left = io->in_mem_bytes[f] - mpos;
-                uint64_t span = std::min<uint64_t>(left, (uint64_t)(est * 1.02 * (double)K) + (64 << 10));
-                std::vector<uint32_t> cnt;
-                uint64_t lines = 0;
-                for (;;) {
-                    const size_t b0 = cnt.size(), b1 = (size_t)((span + SUB - 1) / SUB);
-                    cnt.resize(b1);
-                    P->pool->parallel_for(b1 - b0, [&](size_t i) {
-                        const size_t o = (b0 + i) * SUB;
-                        cnt[b0 + i] = (uint32_t)count_nl(base + o, (size_t)std::min<uint64_t>(SUB, span - o));
-                    });
-                    lines = 0;
-                    for (auto v : cnt) lines += v;
-                    if (lines >= want_lines || span == left) break;
-                    const uint64_t nspan = std::min<uint64_t>(left, span + span / 2 + (1 << 20));
-                    // recount the (partial) last block of the old span together with the new bytes
-                    if (!cnt.empty()) cnt.pop_back();
-                    span = nspan;
-                }
-                uint64_t bytes = span;
-                if (lines >= want_lines) bytes = locate_nl(base, (size_t)span, cnt, want_lines);
-                c.data = base;
-                c.bytes = bytes;
-                c.lines = std::min<uint64_t>(lines, want_lines);
-                mpos += bytes;
-                c.final = mpos == io->in_mem_bytes[f];
-                if (c.final && bytes > 0 && base[bytes - 1] != '\n' && lines < want_lines) c.lines += 1;     // unterminated last line
-                c.buf = -1;
-            } else {
-                const uint64_t tw = now_ns();
-                const int bi = acquire_ring(f);
-                ns_wait_ring += now_ns() - tw;
-                if (bi < 0) return;
-                HostBuf& hb = P->in_buf[f][bi];
-                size_t cap = (size_t)(est * 1.02 * (double)K) + (256 << 10);
-                if (cap < carry.size() + (1 << 20)) cap = carry.size() + (1 << 20);
-                hb.ensure(cap);
-                if (!hb.p) { fail(AQC_ERR_HIP, "page-locked allocation of %zu bytes failed", cap); return; }
-                size_t fill = carry.size();
-                if (fill) memcpy(hb.p, carry.data(), fill);
-                carry.clear();
-                std::vector<uint32_t> cnt;
-                uint64_t lines = 0;
-                if (fill) Source::count_blocks(hb.p, 0, fill, cnt, P->pool.get());      // the carried-over bytes
-                for (;;) {
-                    if (!eof && fill < hb.cap) {
-                        const size_t want = std::min(hb.cap, cap) - fill;
-                        const uint64_t tr = now_ns();
-                        // (bytes and their per-block newline counts in one go: the thread that fetched a piece counts it)
-                        const size_t got = want ? src->read_counted(hb.p, fill, want, cnt, P->pool.get()) : 0;
-                        ns_read += now_ns() - tr;
-                        if (src->failed()) { fail(AQC_ERR_ARG, "%s: %s", io->in_path[f], src->why()); return; }
-                        if (got < want) eof = true;
-                        fill += got;
-                    }
-                    lines = 0;
-                    for (auto v : cnt) lines += v;
-                    if (lines >= want_lines || eof) break;
-                    // the records are longer than estimated: a bigger buffer, keep what is there
-                    const size_t ncap = cap + cap / 2 + (4 << 20);
-                    if (ncap > hb.cap) {
-                        HostBuf nbuf;
-                        nbuf.pageable = hb.pageable;
-                        nbuf.ensure(ncap);
-                        if (!nbuf.p) { fail(AQC_ERR_HIP, "page-locked allocation of %zu bytes failed", ncap); return; }
-                        memcpy(nbuf.p, hb.p, fill);
-                        hb.release();
-                        hb = nbuf;
-                    }
-                    cap = ncap;
-                }
-                size_t bytes = fill;
-                if (lines >= want_lines) bytes = locate_nl(hb.p, fill, cnt, want_lines);
-                if (bytes < fill) carry.assign(hb.p + bytes, hb.p + fill);
-                c.data = hb.p;
-                c.bytes = bytes;
-                c.lines = std::min<uint64_t>(lines, want_lines);
-                c.final = eof && carry.empty();
-                if (c.final && bytes > 0 && hb.p[bytes - 1] != '\n' && lines < want_lines) c.lines += 1;
-                c.buf = bi;
-            }
-            if (c.lines >= 4 && c.bytes) est = (double)c.bytes / (double)(c.lines / 4);
-            const bool fin = c.final;
-            if (!inq[f]->push(c)) { if (c.buf >= 0) release_ring(f, c.buf); return; }
-            if (fin) break;
+            c.data = hb.p;
+            c.bytes = lines >= want_lines ? locate_nl(hb.p, fill, cnt, want_lines) : fill;
+            if (c.bytes < fill) carry.assign(hb.p + c.bytes, hb.p + fill);
+            if (!close_chunk(c, rb, lines, eof && carry.empty(), c.bytes ? hb.p[c.bytes - 1] : (uint8_t)'\n', est)) break;
         }
         inq[f]->close();
     }
@@ -1173,7 +623,7 @@ struct Run {
     // buffer stays unwritten).  Line feeds: host stretches are counted here, device stretches come with a count per 64 KiB piece
     // from the kernel that checksummed them (gzb_crc_kernel); the <= 2 pieces a stretch covers only partly, and the piece the
     // chunk is cut in, are copied down (64 KiB each) and looked at here.  The text itself crosses PCIe only for chunks that go to
-    // ANOTHER device than the decoder's (fetched into the ring buffer, as in rounds 4 - 5).
+    // ANOTHER device than the decoder's (fetched into the ring buffer).
     struct Stretch {
         size_t off = 0, len = 0;          // in the chunk buffer
         uint64_t nl = 0;
@@ -1243,165 +693,162 @@ struct Run {
         return false;       // (counts and bytes disagree: cannot happen)
     }
 
-    void reader_gz(int f, GzSource* src, int dec_device) {
-        const uint64_t want_lines = 4 * K;
-        double est = 360.0;
+    // the chunk this reader is putting together, and what the one before left behind its cut
+    struct StretchChunk {
+        int f = 0;
+        std::vector<Stretch> st;               // the chunk so far
+        size_t fill = 0;                       // bytes of the ring buffer they cover
+        uint64_t lines = 0;                    // line feeds in them
         std::vector<Stretch> carry;            // what the previous chunk left behind its cut (offsets from 0)
         std::vector<uint8_t> carry_host, tmp;  // ... the host bytes of it (carry_host.size() = its whole length; device stretches' places unwritten)
+    };
+    // the chunk starts with what the last one left behind its cut
+    bool take_carry(StretchChunk& k, HostBuf& hb, bool same_dev) {
+        k.st.clear();
+        k.fill = k.carry_host.size();
+        k.lines = 0;
+        if (k.fill) memcpy(hb.p, k.carry_host.data(), k.fill);
+        for (Stretch& c : k.carry) {
+            if (c.dev && !same_dev) {
+                // (this chunk goes to another device: its device text comes down after all)
+                if (!fetch_now(c.d, c.d.sec_off, c.d.sec_off + c.d.len, hb.p + c.off)) return device_copy_failed(k.f);
+                c.dev = false;
+                c.d = aqcgz::DevSegment();
+            }
+            k.lines += c.nl;
+            k.st.push_back(std::move(c));
+        }
+        k.carry.clear();
+        k.carry_host.clear();
+        return true;
+    }
+    // `got` new bytes behind k.fill as stretches: the device segments among them, host bytes between them
+    bool add_stretches(StretchChunk& k, HostBuf& hb, size_t got, std::vector<aqcgz::DevSegment>& segs) {
+        const uint64_t tc = now_ns();
+        size_t cur = 0;
+        auto host_part = [&](size_t a, size_t b) {
+            if (b <= a) return;
+            Stretch h;
+            h.off = k.fill + a; h.len = b - a;
+            h.nl = count_host(hb.p + h.off, h.len);
+            k.lines += h.nl;
+            k.st.push_back(std::move(h));
+        };
+        for (aqcgz::DevSegment& g : segs) {
+            host_part(cur, g.dst_off);
+            Stretch d;
+            d.off = k.fill + g.dst_off; d.len = g.len; d.dev = true;
+            cur = g.dst_off + g.len;
+            d.d = std::move(g);
+            if (!count_dev(d.d, d.nl, k.tmp)) return device_copy_failed(k.f);
+            k.lines += d.nl;
+            k.st.push_back(std::move(d));
+        }
+        host_part(cur, got);
+        ns_count += now_ns() - tc;
+        k.fill += got;
+        return true;
+    }
+    // the cut, just behind the 4K-th line feed (k.lines >= 4K): *bytes is where; what lies behind it becomes the carry
+    bool cut_stretches(StretchChunk& k, HostBuf& hb, size_t& bytes) {
+        const uint64_t want_lines = 4 * K;
+        uint64_t seen = 0;
+        for (size_t i = 0; i < k.st.size(); ++i) {
+            Stretch& x = k.st[i];
+            if (seen + x.nl < want_lines) { seen += x.nl; continue; }
+            size_t pos = 0;      // inside the stretch, behind the line feed
+            const uint64_t n = want_lines - seen;
+            if (x.dev) {
+                if (!locate_dev(x.d, n, pos, k.tmp)) return device_copy_failed(k.f);
+            } else {
+                uint64_t c = 0;
+                const uint8_t* p = hb.p + x.off;
+                size_t o = 0;
+                while (o < x.len) {
+                    const uint8_t* q = (const uint8_t*)memchr(p + o, '\n', x.len - o);
+                    if (!q) break;
+                    o = (size_t)(q - p) + 1;
+                    if (++c == n) break;
+                }
+                pos = o;
+            }
+            bytes = x.off + pos;
+            // what lies behind the cut is the head of the next chunk
+            if (pos < x.len) {
+                Stretch t = x;             // (a copy: its DevSegment holds the section too)
+                t.off = 0; t.len = x.len - pos; t.nl = x.nl - n;
+                if (t.dev) { t.d.sec_off += pos; t.d.len = t.len; t.d.dev += pos; t.d.dst_off = 0; }
+                k.carry.push_back(std::move(t));
+                x.len = pos; x.nl = n;
+                if (x.dev) x.d.len = pos;
+            }
+            for (size_t j = i + 1; j < k.st.size(); ++j) {
+                Stretch t = std::move(k.st[j]);
+                t.off -= bytes;
+                k.carry.push_back(std::move(t));
+            }
+            k.st.resize(i + 1);
+            break;
+        }
+        if (bytes < k.fill) k.carry_host.assign(hb.p + bytes, hb.p + k.fill);
+        return true;
+    }
+
+    void read_stretches(int f, GzSource* src, int dec_device) {
+        const uint64_t want_lines = 4 * K;
+        double est = 360.0;
+        StretchChunk k;
+        k.f = f;
         bool eof = false;
         for (uint64_t idx = 0; !abort; ++idx) {
             // chunk idx goes to context idx % n: only there may its device text stay where it is
             const bool same_dev = aqc_device_index(P->ctx[(size_t)(idx % jobq.size())]) == dec_device;
-            const uint64_t tw = now_ns();
-            const int bi = acquire_ring(f);
-            ns_wait_ring += now_ns() - tw;
-            if (bi < 0) return;
-            HostBuf& hb = P->in_buf[f][bi];
-            size_t cap = (size_t)(est * 1.02 * (double)K) + (256 << 10);
-            if (cap < carry_host.size() + (1 << 20)) cap = carry_host.size() + (1 << 20);
-            hb.ensure(cap);
-            if (!hb.p) { fail(AQC_ERR_HIP, "page-locked allocation of %zu bytes failed", cap); release_ring(f, bi); return; }
-            std::vector<Stretch> st;
-            size_t fill = carry_host.size();
-            uint64_t lines = 0;
-            if (fill) memcpy(hb.p, carry_host.data(), fill);
-            for (Stretch& c : carry) {
-                if (c.dev && !same_dev) {
-                    // (this chunk goes to another device: its device text comes down after all)
-                    if (!fetch_now(c.d, c.d.sec_off, c.d.sec_off + c.d.len, hb.p + c.off)) { fail(AQC_ERR_HIP, "%s: copying decoded text from the device failed", io->in_path[f]); release_ring(f, bi); return; }
-                    c.dev = false;
-                    c.d = aqcgz::DevSegment();
-                }
-                lines += c.nl;
-                st.push_back(std::move(c));
-            }
-            carry.clear();
-            carry_host.clear();
-            for (;;) {
-                if (lines >= want_lines || eof) break;
-                if (fill >= cap) {
-                    // the records are longer than estimated: a bigger buffer, keep what is there
-                    const size_t ncap = cap + cap / 2 + (4 << 20);
-                    if (ncap > hb.cap) {
-                        HostBuf nbuf;
-                        nbuf.pageable = hb.pageable;
-                        nbuf.ensure(ncap);
-                        if (!nbuf.p) { fail(AQC_ERR_HIP, "page-locked allocation of %zu bytes failed", ncap); release_ring(f, bi); return; }
-                        memcpy(nbuf.p, hb.p, fill);
-                        hb.release();
-                        hb = nbuf;
-                    }
-                    cap = ncap;
-                }
-                const size_t want = std::min(hb.cap, cap) - fill;
+            RingHold rb(*this, f);
+            size_t cap = 0;
+            if (!open_chunk(rb, est, k.carry_host.size(), cap)) return;
+            HostBuf& hb = rb.buf();
+            if (!take_carry(k, hb, same_dev)) return;
+            while (k.lines < want_lines && !eof) {
+                if (k.fill >= cap && !grow_chunk(hb, cap, k.fill)) return;
+                const size_t want = std::min(hb.cap, cap) - k.fill;
                 std::vector<aqcgz::DevSegment> segs;
                 const uint64_t tr = now_ns();
-                const size_t got = src->read_segments(hb.p + fill, want, same_dev ? &segs : nullptr);
+                const size_t got = src->read_segments(hb.p + k.fill, want, same_dev ? &segs : nullptr);
                 ns_read += now_ns() - tr;
-                if (src->failed()) { fail(AQC_ERR_ARG, "%s: %s", io->in_path[f], src->why()); release_ring(f, bi); return; }
+                if (src->failed()) { fail(AQC_ERR_ARG, "%s: %s", io->in_path[f], src->why()); return; }
                 if (got < want) eof = true;
-                // the new bytes as stretches: device segments, host bytes between them
-                const uint64_t tc = now_ns();
-                size_t cur = 0;
-                auto host_part = [&](size_t a, size_t b) {
-                    if (b <= a) return;
-                    Stretch h;
-                    h.off = fill + a; h.len = b - a;
-                    h.nl = count_host(hb.p + h.off, h.len);
-                    lines += h.nl;
-                    st.push_back(std::move(h));
-                };
-                for (aqcgz::DevSegment& g : segs) {
-                    host_part(cur, g.dst_off);
-                    Stretch d;
-                    d.off = fill + g.dst_off; d.len = g.len; d.dev = true;
-                    cur = g.dst_off + g.len;
-                    d.d = std::move(g);
-                    if (!count_dev(d.d, d.nl, tmp)) { fail(AQC_ERR_HIP, "%s: copying decoded text from the device failed", io->in_path[f]); release_ring(f, bi); return; }
-                    lines += d.nl;
-                    st.push_back(std::move(d));
-                }
-                host_part(cur, got);
-                ns_count += now_ns() - tc;
-                fill += got;
+                if (!add_stretches(k, hb, got, segs)) return;
             }
-            // the cut: just behind the 4K-th line feed
-            size_t bytes = fill;
-            if (lines >= want_lines) {
-                uint64_t seen = 0;
-                for (size_t i = 0; i < st.size(); ++i) {
-                    Stretch& x = st[i];
-                    if (seen + x.nl < want_lines) { seen += x.nl; continue; }
-                    size_t pos = 0;      // inside the stretch, behind the line feed
-                    const uint64_t k = want_lines - seen;
-                    if (x.dev) {
-                        if (!locate_dev(x.d, k, pos, tmp)) { fail(AQC_ERR_HIP, "%s: copying decoded text from the device failed", io->in_path[f]); release_ring(f, bi); return; }
-                    } else {
-                        uint64_t c = 0;
-                        const uint8_t* p = hb.p + x.off;
-                        size_t o = 0;
-                        while (o < x.len) {
-                            const uint8_t* q = (const uint8_t*)memchr(p + o, '\n', x.len - o);
-                            if (!q) break;
-                            o = (size_t)(q - p) + 1;
-                            if (++c == k) break;
-                        }
-                        pos = o;
-                    }
-                    bytes = x.off + pos;
-                    // what lies behind the cut is the head of the next chunk
-                    if (pos < x.len) {
-                        Stretch t = x;             // (a copy: its DevSegment holds the section too)
-                        t.off = 0; t.len = x.len - pos; t.nl = x.nl - k;
-                        if (t.dev) { t.d.sec_off += pos; t.d.len = t.len; t.d.dev += pos; t.d.dst_off = 0; }
-                        carry.push_back(std::move(t));
-                        x.len = pos; x.nl = k;
-                        if (x.dev) x.d.len = pos;
-                    }
-                    for (size_t j = i + 1; j < st.size(); ++j) {
-                        Stretch t = std::move(st[j]);
-                        t.off -= bytes;
-                        carry.push_back(std::move(t));
-                    }
-                    st.resize(i + 1);
-                    break;
-                }
-                if (bytes < fill) carry_host.assign(hb.p + bytes, hb.p + fill);
-            }
+            size_t bytes = k.fill;
+            if (k.lines >= want_lines && !cut_stretches(k, hb, bytes)) return;
             InChunk c;
             c.idx = idx;
             c.data = hb.p;
             c.bytes = bytes;
-            c.lines = std::min<uint64_t>(lines, want_lines);
-            c.final = eof && carry.empty() && carry_host.empty();
-            c.buf = bi;
             // the chunk's last byte (the framing wants it on the host), and its device stretches for aqc_frame_mixed
-            c.last_byte = '\n';
+            uint8_t last_byte = '\n';
             if (bytes) {
-                const Stretch& z = st.back();
-                if (!z.dev) c.last_byte = hb.p[bytes - 1];
-                else if (lines < want_lines) {          // (cut behind a line feed otherwise)
-                    uint8_t b1 = '\n';
-                    if (!fetch_now(z.d, z.d.sec_off + z.d.len - 1, z.d.sec_off + z.d.len, &b1)) { fail(AQC_ERR_HIP, "%s: copying decoded text from the device failed", io->in_path[f]); release_ring(f, bi); return; }
-                    c.last_byte = b1;
+                const Stretch& z = k.st.back();
+                if (!z.dev) last_byte = hb.p[bytes - 1];
+                else if (k.lines < want_lines && !fetch_now(z.d, z.d.sec_off + z.d.len - 1, z.d.sec_off + z.d.len, &last_byte)) {      // (cut behind a line feed otherwise)
+                    device_copy_failed(f);
+                    return;
                 }
             }
-            if (c.final && bytes > 0 && c.last_byte != '\n' && lines < want_lines) c.lines += 1;     // unterminated last line
-            for (Stretch& x : st)
+            c.last_byte = last_byte;
+            for (Stretch& x : k.st)
                 if (x.dev && x.len) {
                     if (!c.ext) c.ext = std::make_shared<std::vector<aqcgz::DevSegment>>();
                     x.d.dst_off = x.off;
                     c.ext->push_back(std::move(x.d));
                 }
-            if (c.lines >= 4 && c.bytes) est = (double)c.bytes / (double)(c.lines / 4);
-            const bool fin = c.final;
-            if (!inq[f]->push(c)) { release_ring(f, bi); return; }
-            if (fin) break;
+            if (!close_chunk(c, rb, k.lines, eof && k.carry.empty() && k.carry_host.empty(), last_byte, est)) break;
         }
         inq[f]->close();
     }
 
     // ---- dispatcher: pair the chunks, deal them round robin ---------------------------------------------------------------
+    void release_inputs(const Job& j) { for (int f = 0; f < nf; ++f) release_ring(f, j.c[f].buf); }
     void dispatcher() {
         bind_io_thread("dispatcher");
         static const uint8_t nothing[1] = {0};
@@ -1420,263 +867,295 @@ struct Run {
                 } else if (j.c[f].final) over[f] = true;
             }
             if (!got[0] && !(nf == 2 && got[1])) break;            // both ran dry (or the pipe is stopping)
-            if (abort || ended) { for (int f = 0; f < nf; ++f) release_ring(f, j.c[f].buf); break; }
+            if (abort || ended) { release_inputs(j); break; }
             // (R1's final chunk ends the loop whatever R2 holds: preprocesser.py:412-415)
             j.last = j.c[0].final;
             j.ticket = group_tickets[group_of_ctx[idx % jobq.size()]]++;
-            if (!jobq[idx % jobq.size()]->push(j)) {
-                for (int f = 0; f < nf; ++f) release_ring(f, j.c[f].buf);
-                break;
-            }
+            if (!jobq[idx % jobq.size()]->push(j)) { release_inputs(j); break; }
             if (j.last) break;
         }
         for (auto& q : jobq) q->close();
     }
 
     // ---- slot worker ------------------------------------------------------------------------------------------------------
+    // One chunk pair in a slot worker's hands.  It owns the chunk's input buffers: they go back to their rings when the text has
+    // left them, or when the worker lets go of the chunk on any other way — unless the chunk's good records are going to be
+    // written from them (spans mode), in which case they are handed on to its OutChunk.
+    struct Turn {
+        aqc_ctx* c;
+        int ci, slot, wid;
+        Job& j;
+        RingHold in[2];
+        aqc_text_chunk ch{};
+        aqc_frame_info info{};
+        uint64_t n = 0;           // records of the chunk that are run and written (info.n, fewer when upstream dies at one)
+        bool fatal = false;       // upstream's run ends inside this chunk (an exception in its loop): records [0, n) are written, then the pipe stops
+        uint64_t tt = 0;          // since when the stage being timed runs
+        Turn(Run& r, aqc_ctx* ctx, int ci_, int slot_, Job& job)
+            : c(ctx), ci(ci_), slot(slot_), wid(ci_ * r.P->slots + slot_), j(job), in{{r, 0, job.c[0].buf}, {r, 1, job.c[1].buf}} {}
+        void drop_input() { in[0].release(); in[1].release(); }
+    };
+    enum class Step { go, skip, quit };      // on with this chunk / on with the next one / the worker ends
+
     void worker(int ci, int slot) {
         aqc_ctx* c = P->ctx[ci];
-        const int wid = ci * P->slots + slot;
         // this thread drives one GPU: it runs on the CPUs next to that GPU, and the page-locked output sets it touches first
         // (P->wbufs[wid]) come from that node's memory.  Readers and file writers serve every context: they float.
         {
             const int node = aqc_device_numa_node(c), bound = aqc_bind_thread_to_node(node);
-            if (slot == 0 && getenv("AQC_PIPE_DEBUG"))
+            if (slot == 0 && dbg)
                 fprintf(stderr, "pipe: context %d (device %d) — NUMA node %d, its %d slot workers %s; reader / writer / pool threads are not bound (they serve all contexts)\n",
                         ci, aqc_device_index(c), node, P->slots, bound ? "bound to that node's CPUs" : "not bound (single node, unknown, or AQC_PIPE_NUMA=0)");
         }
         Job j;
         int set = 0;
-        const bool use_spans = spans_on;
         while (!abort && jobq[ci]->pop(j)) {
-            aqc_text_chunk ch{};
-            ch.text1 = j.c[0].data; ch.bytes1 = j.c[0].bytes; ch.final1 = j.c[0].final ? 1 : 0;
-            if (nf == 2) { ch.text2 = j.c[1].data; ch.bytes2 = j.c[1].bytes; ch.final2 = j.c[1].final ? 1 : 0; }
-            ch.max_records = UINT64_MAX;
-            ch.first_index = (opt->chunk_index0 + j.idx * (opt->chunk_index_stride ? opt->chunk_index_stride : 1)) * K;
-            aqc_frame_info info{};
-            uint64_t tt = now_ns();
-            Gate& ug = *up_gate[group_of_ctx[ci]];
-            Gate& dg = *down_gate[group_of_ctx[ci]];
-            if (!gate_enter(ug, j.ticket, (uint64_t)P->slots)) { for (int f = 0; f < nf; ++f) release_ring(f, j.c[f].buf); return; }
-            int rc;
+            Turn t(*this, c, ci, slot, j);
+            if (!frame_chunk(t)) return;
+            const Step s = end_of_input(t);
+            if (s == Step::quit) return;
+            if (s == Step::skip) continue;          // the input ended before this chunk
+            OutChunk oc;
+            oc.idx = j.idx; oc.last = j.last; oc.worker = t.wid;
+            if (t.n == 0) {
+                // the input ended at this chunk's very first record (a mate file that ran dry at a chunk boundary, a partial record):
+                // nothing to run or to write, but the chunk is committed — it is the run's last
+                t.drop_input();
+                if (!outq.push(oc)) return;
+                continue;
+            }
+            if (int rc = aqc_run(c, slot, UINT64_MAX)) { fail(rc, "aqc_run: %s", aqc_last_error()); return; }
+            if (!qc_turn(t)) return;
+            if (!opt->no_output) {
+                if (!format_and_fetch(t, oc, set)) return;
+                oc.set = set;
+                set ^= 1;
+            } else if (!sync_only(t)) return;
+            oc.n = t.n;
+            oc.fatal = t.fatal;
+            if (t.fatal) oc.last = true;
+            records += t.n;
+            if (!outq.push(oc) || t.fatal) return;
+        }
+    }
+
+    // framing (of host text, or of host text mixed with text in this device's memory) under the upload gate
+    bool frame_chunk(Turn& t) {
+        Job& j = t.j;
+        aqc_text_chunk& ch = t.ch;
+        ch.text1 = j.c[0].data; ch.bytes1 = j.c[0].bytes; ch.final1 = j.c[0].final ? 1 : 0;
+        if (nf == 2) { ch.text2 = j.c[1].data; ch.bytes2 = j.c[1].bytes; ch.final2 = j.c[1].final ? 1 : 0; }
+        ch.max_records = UINT64_MAX;
+        ch.first_index = (opt->chunk_index0 + j.idx * (opt->chunk_index_stride ? opt->chunk_index_stride : 1)) * K;
+        t.tt = now_ns();
+        int rc;
+        {
+            GatePass up(*this);
+            if (!up.enter(*up_gate[group_of_ctx[t.ci]], j.ticket)) return false;
             if (j.c[0].ext || (nf == 2 && j.c[1].ext)) {
                 // parts of the chunk are text in this device's memory (a .gz input decoded here): they move inside HBM
                 std::vector<aqc_text_extent> ex[2];
                 for (int f = 0; f < nf; ++f)
                     if (j.c[f].ext)
                         for (const aqcgz::DevSegment& g : *j.c[f].ext) ex[f].push_back(aqc_text_extent{(uint64_t)g.dst_off, (uint64_t)g.len, g.dev});
-                rc = aqc_frame_mixed(c, slot, &ch, ex[0].data(), ex[0].size(), j.c[0].last_byte, ex[1].data(), ex[1].size(), nf == 2 ? j.c[1].last_byte : (uint8_t)'\n', &info);
+                rc = aqc_frame_mixed(t.c, t.slot, &ch, ex[0].data(), ex[0].size(), j.c[0].last_byte, ex[1].data(), ex[1].size(), nf == 2 ? j.c[1].last_byte : (uint8_t)'\n', &t.info);
                 for (int f = 0; f < nf; ++f) j.c[f].ext.reset();        // (the sections — and their text — are free to go)
-            } else rc = aqc_frame(c, slot, &ch, &info);
-            gate_leave(ug);
-            ns_frame += now_ns() - tt;
-            tt = now_ns();
-            // the text has left the host buffers — which are free again, unless the good records are going to be written from
-            // them (spans mode: they are released when the chunk has been committed)
-            if (!use_spans || rc) for (int f = 0; f < nf; ++f) release_ring(f, j.c[f].buf);
-            if (rc) { fail(rc, "aqc_frame: %s", aqc_last_error()); return; }
-            auto drop_input = [&] { if (use_spans) for (int f = 0; f < nf; ++f) release_ring(f, j.c[f].buf); };
-            // Does the input end in this chunk?  The lock step of preprocesser.py:412-429 over what the framing found: R1 is read
-            // first; a reader is dry when its chunk ended (an empty line: eof, or the file's last chunk) and every record it held is
-            // used.  Decided in chunk order, BEFORE the chunk is run: chunks behind the end never touch a counter.
-            {
-                const bool fin1 = j.c[0].final, fin2 = nf == 2 ? j.c[1].final : fin1;
-                const bool done1 = (info.eof1 || fin1) && info.avail1 == info.n;
-                const bool done2 = nf == 2 && (info.eof2 || fin2) && info.avail2 == info.n;
-                const bool stop = done1 || (done2 && info.avail1 > info.n);
-                std::unique_lock<std::mutex> lk(fr_mu);
-                fr_cv.wait(lk, [&] { return abort.load() || framed_next == j.idx; });
-                if (abort) { drop_input(); return; }
-                const bool behind_end = end_chunk != UINT64_MAX;
-                bool foreign = false;
-                if (!behind_end) {
-                    if (stop) {
-                        end_chunk = j.idx;
-                        extra_bases = (!done1 && done2 && info.avail1 > info.n) ? info.next_len1 : 0;
-                        j.last = true;
-                    } else if (info.n != K) foreign = true;      // neither K records nor an end: nothing upstream's reader could have produced from these chunks
-                }
-                framed_next = j.idx + 1;
-                lk.unlock();
-                fr_cv.notify_all();
-                if (foreign) { anomaly = true; drop_input(); stop_all(); return; }
-                if (behind_end) { drop_input(); continue; }          // the input ended before this chunk
-                if (stop) end_input();
-            }
-            uint64_t n = info.n;
-            if (n == 0) {
-                // the input ended at this chunk's very first record (a mate file that ran dry at a chunk boundary, a partial record):
-                // nothing to run or to write, but the chunk is committed — it is the run's last
-                drop_input();
-                OutChunk oc0;
-                oc0.idx = j.idx; oc0.last = j.last; oc0.worker = wid;
-                if (!outq.push(oc0)) return;
-                continue;
-            }
-            bool fatal = false;       // upstream's run ends inside this chunk (an exception in its loop): records [0, n) are written, then the pipe stops
-            if ((rc = aqc_run(c, slot, UINT64_MAX))) { fail(rc, "aqc_run: %s", aqc_last_error()); return; }
-            // post-filter QC while TOTAL_READS < qc_sample (preprocesser.py:624-627), issued in chunk order
-            const uint64_t g0 = ch.first_index;
-            uint64_t n_qc = n;
-            if (opt->qc_sample > 0) n_qc = (uint64_t)opt->qc_sample - 1 > g0 ? std::min<uint64_t>(n, (uint64_t)opt->qc_sample - 1 - g0) : 0;
-            const bool may_qc = opt->qc_sample <= 0 || g0 < (uint64_t)opt->qc_sample - 1;
-            if (may_qc) {
-                std::unique_lock<std::mutex> lk(qc_mu);
-                qc_cv.wait(lk, [&] { return abort || qc_next == j.idx; });
-                if (!abort && n_qc > 0) {
-                    rc = aqc_qc_stat(c, slot, AQC_QC_R1_POST, 0, 0, n_qc, 1);
-                    if (!rc && nf == 2) rc = aqc_qc_stat(c, slot, AQC_QC_R2_POST, 1, 0, n_qc, 1);
-                    if (!rc) rc = aqc_sync(c, slot);
-                }
-                qc_next = j.idx + 1;
-                lk.unlock();
-                qc_cv.notify_all();
-                if (rc && !dies_at_record(c, slot, rc, j.idx, n, fatal)) { fail(rc, "aqc_qc_stat: %s", aqc_last_error()); return; }
-            } else {
-                // (chunks behind the sample never wait; the turn counter is passed on by the ones before)
-                std::lock_guard<std::mutex> g(qc_mu);
-                if (qc_next == j.idx) { qc_next = j.idx + 1; qc_cv.notify_all(); }
-            }
-            OutChunk oc;
-            oc.idx = j.idx;
-            oc.last = j.last;
-            oc.worker = wid;
-            if (!opt->no_output) {
-                bool have_set = false, in_gate = false;
-                // (a second round only when the device reports, as late as the download, that upstream's run ends at a record of
-                //  this chunk: the records before it are formatted again on their own)
-                uint64_t n_ev[2] = {0, 0};
-                for (int round = 0; ; ++round) {
-                    const char* where = "aqc_format";
-                    rc = use_spans ? aqc_format_spans(c, slot, n, opt->store_overlap, oc.sizes, n_ev) : aqc_format(c, slot, n, opt->store_overlap, oc.sizes);
-                    if (!rc) oc.fused = aqc_format_fused(c, slot) == 1;
-                    if (!rc && !have_set) {
-                        ns_kernels += now_ns() - tt;
-                        tt = now_ns();
-                        // wait for the writer to hand this buffer set back
-                        std::unique_lock<std::mutex> lk(set_mu);
-                        set_cv.wait(lk, [&] { return abort || set_free[wid * 2 + set]; });
-                        if (abort) return;
-                        set_free[wid * 2 + set] = 0;
-                        have_set = true;
-                        ns_wait_set += now_ns() - tt;
-                        tt = now_ns();
-                    }
-                    // .gz output: the members are made on the device (aqc_gzdev.hpp) and come back compressed — no host CPU for
-                    // deflate, a third of the bytes over PCIe.  --compression 0 (stored) and AQC_GZ_DEVICE=0 keep the host codec.
-                    oc.gz = gz_on_device;
-                    if (!rc && oc.gz) { where = "aqc_compress"; rc = aqc_compress(c, slot, io->gzip_level, oc.gz_sizes); }
-                    if (!rc) {
-                        if (!in_gate && !gate_enter(dg, j.ticket, (uint64_t)P->slots)) return;
-                        in_gate = true;
-                        // the six streams with one wait (aqc_fetch_streams)
-                        uint8_t* dstq[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-                        uint64_t capq[6] = {0, 0, 0, 0, 0, 0};
-                        for (int q = 0; q < 6; ++q) {
-                            if (!oc.sizes[q]) continue;
-                            HostBuf& hb = P->wbufs[wid].out[set][q];
-                            hb.ensure(oc.gz ? oc.gz_sizes[q] : oc.sizes[q]);
-                            if (!hb.p) { gate_leave(dg); fail(AQC_ERR_HIP, "page-locked allocation failed"); return; }
-                            dstq[q] = hb.p; capq[q] = hb.cap;
-                        }
-                        where = "fetching the output streams";
-                        rc = aqc_fetch_streams(c, slot, oc.gz ? 1 : 0, dstq, capq);
-                        if (!rc && use_spans) {
-                            // where the rebuilt and the bad records stood: everything between them is written from the input buffer
-                            auto sp = std::make_shared<OutChunk::Spans>();
-                            for (int f = 0; f < nf && !rc; ++f) {
-                                sp->ev[f].resize((size_t)n_ev[f]);
-                                rc = aqc_fetch_span_events(c, slot, f, sp->ev[f].data(), n_ev[f]);
-                                sp->in[f] = j.c[f].data;
-                                sp->end[f] = n == info.n ? (f == 0 ? info.consumed1 : info.consumed2) : 0;
-                                oc.in_buf[f] = j.c[f].buf;
-                            }
-                            if (!rc && n != info.n) {
-                                // (the chunk was cut at the record upstream dies at: the last piece ends where that record begins)
-                                uint64_t e2[2] = {0, 0};
-                                rc = aqc_span_end(c, slot, n, e2);
-                                sp->end[0] = e2[0]; sp->end[1] = e2[1];
-                            }
-                            for (int f = 0; f < nf && !rc; ++f) {
-                                uint64_t cursor = 0, total = 0;
-                                for (const aqc_span_event& e : sp->ev[f]) {
-                                    total += (e.in_start - cursor) + e.out_len;
-                                    cursor = (uint64_t)e.in_start + e.in_len;
-                                }
-                                sp->good_total[f] = total + (sp->end[f] > cursor ? sp->end[f] - cursor : 0);
-                            }
-                            if (!rc && spans_assemble) {
-                                // the good output of each file, put together here: the chunk's own bytes between the events, the rebuilt
-                                // records at them — on the pool, a task per ~1 MiB of output; then the input buffers are free again
-                                for (int f = 0; f < nf; ++f) {
-                                    HostBuf& gb = P->wbufs[wid].good[set][f];
-                                    gb.pageable = true;
-                                    gb.ensure((size_t)sp->good_total[f] + 64);
-                                    if (sp->good_total[f] && !gb.p) { rc = AQC_ERR_HIP; break; }
-                                    assemble_good(*sp, f, oc.sizes[3 * f] ? P->wbufs[wid].out[set][3 * f].p : nullptr, gb.p);
-                                    oc.good_ptr[f] = gb.p;
-                                    oc.good_bytes[f] = sp->good_total[f];
-                                }
-                                if (rc) { gate_leave(dg); drop_input(); fail(AQC_ERR_HIP, "allocation of a good-output buffer failed"); return; }
-                                for (int f = 0; f < nf; ++f) { release_ring(f, j.c[f].buf); oc.in_buf[f] = -1; }
-                            } else oc.spans = sp;
-                        }
-                    }
-                    if (!rc) break;
-                    if (round == 0 && !fatal && dies_at_record(c, slot, rc, j.idx, n, fatal)) continue;
-                    if (in_gate) gate_leave(dg);
-                    drop_input();
-                    fail(rc, "%s: %s", where, aqc_last_error());
-                    return;
-                }
-                if (in_gate) gate_leave(dg);
-                ns_fetch += now_ns() - tt;
-                oc.set = set;
-                set ^= 1;
-            } else {
-                if (!gate_enter(dg, j.ticket, (uint64_t)P->slots)) return;
-                gate_leave(dg);
-                if ((rc = aqc_sync(c, slot)) && !dies_at_record(c, slot, rc, j.idx, n, fatal)) { fail(rc, "aqc_sync: %s", aqc_last_error()); return; }
-            }
-            oc.n = n;
-            oc.fatal = fatal;
-            if (fatal) oc.last = true;
-            records += n;
-            if (!outq.push(oc) || fatal) return;
+            } else rc = aqc_frame(t.c, t.slot, &ch, &t.info);
         }
+        ns_frame += now_ns() - t.tt;
+        t.tt = now_ns();
+        // the text has left the host buffers — which are free again, unless the good records are going to be written from
+        // them (spans mode: they are released when the chunk has been committed)
+        if (!spans_on || rc) t.drop_input();
+        if (rc) { fail(rc, "aqc_frame: %s", aqc_last_error()); return false; }
+        t.n = t.info.n;
+        return true;
+    }
+
+    // Does the input end in this chunk?  The lock step of preprocesser.py:412-429 over what the framing found: R1 is read
+    // first; a reader is dry when its chunk ended (an empty line: eof, or the file's last chunk) and every record it held is
+    // used.  Decided in chunk order, BEFORE the chunk is run: chunks behind the end never touch a counter.
+    Step end_of_input(Turn& t) {
+        Job& j = t.j;
+        const aqc_frame_info& info = t.info;
+        const bool fin1 = j.c[0].final, fin2 = nf == 2 ? j.c[1].final : fin1;
+        const bool done1 = (info.eof1 || fin1) && info.avail1 == info.n;
+        const bool done2 = nf == 2 && (info.eof2 || fin2) && info.avail2 == info.n;
+        const bool stop = done1 || (done2 && info.avail1 > info.n);
+        std::unique_lock<std::mutex> lk(fr_mu);
+        fr_cv.wait(lk, [&] { return abort.load() || framed_next == j.idx; });
+        if (abort) return Step::quit;
+        const bool behind_end = end_chunk != UINT64_MAX;
+        bool foreign = false;
+        if (!behind_end) {
+            if (stop) {
+                end_chunk = j.idx;
+                extra_bases = (!done1 && done2 && info.avail1 > info.n) ? info.next_len1 : 0;
+                j.last = true;
+            } else if (info.n != K) foreign = true;      // neither K records nor an end: nothing upstream's reader could have produced from these chunks
+        }
+        framed_next = j.idx + 1;
+        lk.unlock();
+        fr_cv.notify_all();
+        if (foreign) { anomaly = true; t.drop_input(); stop_all(); return Step::quit; }
+        if (behind_end) return Step::skip;
+        if (stop) end_input();
+        return Step::go;
+    }
+
+    // post-filter QC while TOTAL_READS < qc_sample (preprocesser.py:624-627), issued in chunk order
+    bool qc_turn(Turn& t) {
+        const uint64_t idx = t.j.idx, g0 = t.ch.first_index;
+        uint64_t n_qc = t.n;
+        if (opt->qc_sample > 0) n_qc = (uint64_t)opt->qc_sample - 1 > g0 ? std::min<uint64_t>(t.n, (uint64_t)opt->qc_sample - 1 - g0) : 0;
+        const bool may_qc = opt->qc_sample <= 0 || g0 < (uint64_t)opt->qc_sample - 1;
+        if (!may_qc) {
+            // (chunks behind the sample never wait; the turn counter is passed on by the ones before)
+            std::lock_guard<std::mutex> g(qc_mu);
+            if (qc_next == idx) { qc_next = idx + 1; qc_cv.notify_all(); }
+            return true;
+        }
+        int rc = 0;
+        std::unique_lock<std::mutex> lk(qc_mu);
+        qc_cv.wait(lk, [&] { return abort || qc_next == idx; });
+        if (!abort && n_qc > 0) {
+            rc = aqc_qc_stat(t.c, t.slot, AQC_QC_R1_POST, 0, 0, n_qc, 1);
+            if (!rc && nf == 2) rc = aqc_qc_stat(t.c, t.slot, AQC_QC_R2_POST, 1, 0, n_qc, 1);
+            if (!rc) rc = aqc_sync(t.c, t.slot);
+        }
+        qc_next = idx + 1;
+        lk.unlock();
+        qc_cv.notify_all();
+        if (rc && !dies_at_record(t, rc)) { fail(rc, "aqc_qc_stat: %s", aqc_last_error()); return false; }
+        return true;
+    }
+
+    // format -> (compress) -> fetch into output set `set`, the fetch under the download gate.  A second round only when the device
+    // reports, as late as the download, that upstream's run ends at a record of this chunk: the records before it are formatted
+    // again on their own.
+    bool format_and_fetch(Turn& t, OutChunk& oc, int set) {
+        GatePass down(*this);
+        bool have_set = false;
+        uint64_t n_ev[2] = {0, 0};
+        for (int round = 0; ; ++round) {
+            const char* where = "aqc_format";
+            int rc = spans_on ? aqc_format_spans(t.c, t.slot, t.n, opt->store_overlap, oc.sizes, n_ev) : aqc_format(t.c, t.slot, t.n, opt->store_overlap, oc.sizes);
+            if (!rc) oc.fused = aqc_format_fused(t.c, t.slot) == 1;
+            if (!rc && !have_set) {
+                ns_kernels += now_ns() - t.tt;
+                t.tt = now_ns();
+                if (!acquire_set(t.wid, set)) return false;
+                have_set = true;
+                ns_wait_set += now_ns() - t.tt;
+                t.tt = now_ns();
+            }
+            oc.gz = gz_on_device;
+            if (!rc && oc.gz) { where = "aqc_compress"; rc = aqc_compress(t.c, t.slot, io->gzip_level, oc.gz_sizes); }
+            if (!rc) {
+                if (!down.held() && !down.enter(*down_gate[group_of_ctx[t.ci]], t.j.ticket)) return false;
+                where = "fetching the output streams";
+                if (!fetch_streams(t, oc, set, rc)) return false;
+                if (!rc && spans_on && !fetch_spans(t, oc, set, n_ev, rc)) return false;
+            }
+            if (!rc) break;
+            if (round == 0 && !t.fatal && dies_at_record(t, rc)) continue;
+            fail(rc, "%s: %s", where, aqc_last_error());
+            return false;
+        }
+        down.leave();
+        ns_fetch += now_ns() - t.tt;
+        return true;
+    }
+    // the six streams with one wait (aqc_fetch_streams); false: the run has failed here, else rc says how the fetch went
+    bool fetch_streams(Turn& t, OutChunk& oc, int set, int& rc) {
+        uint8_t* dstq[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        uint64_t capq[6] = {0, 0, 0, 0, 0, 0};
+        for (int q = 0; q < 6; ++q) {
+            if (!oc.sizes[q]) continue;
+            HostBuf& hb = P->wbufs[t.wid].out[set][q];
+            hb.ensure(oc.gz ? oc.gz_sizes[q] : oc.sizes[q]);
+            if (!hb.p) { fail(AQC_ERR_HIP, "page-locked allocation failed"); return false; }
+            dstq[q] = hb.p; capq[q] = hb.cap;
+        }
+        rc = aqc_fetch_streams(t.c, t.slot, oc.gz ? 1 : 0, dstq, capq);
+        return true;
+    }
+    // spans mode: where the rebuilt and the bad records stood — everything between them is written from the input buffer, by the
+    // file writers (the chunk keeps its input buffers) or, assembled here, as one stream.  false / rc: as fetch_streams.
+    bool fetch_spans(Turn& t, OutChunk& oc, int set, const uint64_t n_ev[2], int& rc) {
+        auto sp = std::make_shared<OutChunk::Spans>();
+        for (int f = 0; f < nf && !rc; ++f) {
+            sp->ev[f].resize((size_t)n_ev[f]);
+            rc = aqc_fetch_span_events(t.c, t.slot, f, sp->ev[f].data(), n_ev[f]);
+            sp->in[f] = t.j.c[f].data;
+            sp->end[f] = t.n == t.info.n ? (f == 0 ? t.info.consumed1 : t.info.consumed2) : 0;
+        }
+        if (!rc && t.n != t.info.n) {
+            // (the chunk was cut at the record upstream dies at: the last piece ends where that record begins)
+            uint64_t e2[2] = {0, 0};
+            rc = aqc_span_end(t.c, t.slot, t.n, e2);
+            sp->end[0] = e2[0]; sp->end[1] = e2[1];
+        }
+        if (rc) return true;
+        for (int f = 0; f < nf; ++f) {
+            uint64_t total = 0;
+            walk_spans(sp->ev[f].data(), 0, sp->ev[f].size(), sp->end[f], [&](uint64_t, uint64_t len) { total += len; }, [&](uint64_t len) { total += len; });
+            sp->good_total[f] = total;
+        }
+        if (!spans_assemble) {
+            oc.spans = sp;
+            for (int f = 0; f < nf; ++f) oc.in_buf[f] = t.in[f].hand_on();
+            return true;
+        }
+        // the good output of each file, put together here: the chunk's own bytes between the events, the rebuilt
+        // records at them — on the pool, a task per ~1 MiB of output; then the input buffers are free again
+        for (int f = 0; f < nf; ++f) {
+            HostBuf& gb = P->wbufs[t.wid].good[set][f];
+            gb.pageable = true;
+            gb.ensure((size_t)sp->good_total[f] + 64);
+            if (sp->good_total[f] && !gb.p) { fail(AQC_ERR_HIP, "allocation of a good-output buffer failed"); return false; }
+            assemble_good(*sp, f, oc.sizes[3 * f] ? P->wbufs[t.wid].out[set][3 * f].p : nullptr, gb.p);
+            oc.good_ptr[f] = gb.p;
+            oc.good_bytes[f] = sp->good_total[f];
+        }
+        t.drop_input();
+        return true;
+    }
+    // no output: the chunk still takes its turn at the download gate, then waits for its kernels
+    bool sync_only(Turn& t) {
+        {
+            GatePass down(*this);
+            if (!down.enter(*down_gate[group_of_ctx[t.ci]], t.j.ticket)) return false;
+        }
+        const int rc = aqc_sync(t.c, t.slot);
+        if (rc && !dies_at_record(t, rc)) { fail(rc, "aqc_sync: %s", aqc_last_error()); return false; }
+        return true;
     }
 
     // The good output of file f of a chunk formatted by aqc_format_spans -> dst (what capi.assemble_spans does in the tests, and what
-    // the writev of the other spans mode hands the kernel piece by piece): the copies run on the pool, cut into tasks at events.
+    // the writev of the other spans mode hands the kernel piece by piece): the copies run on the pool, cut into tasks at events
+    // (a clean chunk has few events: a long run of untouched records then makes one task's copy).
     void assemble_good(const OutChunk::Spans& sp, int f, const uint8_t* patch, uint8_t* dst) {
-        const std::vector<aqc_span_event>& ev = sp.ev[f];
+        const aqc_span_event* ev = sp.ev[f].data();
+        const size_t n_ev = sp.ev[f].size();
         const uint8_t* in = sp.in[f];
-        const size_t TASK = 1u << 20;
-        // task boundaries: event index, input cursor, output offset, patch offset at the start of each task
-        struct Cut { size_t e; uint64_t cursor, out, poff; };
-        std::vector<Cut> cuts;
-        cuts.push_back(Cut{0, 0, 0, 0});
-        uint64_t cursor = 0, out = 0, poff = 0;
-        for (size_t i = 0; i < ev.size(); ++i) {
-            out += (ev[i].in_start - cursor) + ev[i].out_len;
-            poff += ev[i].out_len;
-            cursor = (uint64_t)ev[i].in_start + ev[i].in_len;
-            if (out - cuts.back().out >= TASK) cuts.push_back(Cut{i + 1, cursor, out, poff});
-        }
-        const uint64_t end = sp.end[f];
+        const uint64_t TASK = 1u << 20;
+        // where each task starts: event index, output offset, patch offset
+        struct Cut { size_t e; uint64_t out, poff; };
+        std::vector<Cut> cuts{Cut{0, 0, 0}};
+        size_t e = 0;
+        uint64_t out = 0, poff = 0;
+        walk_spans(ev, 0, n_ev, 0, [&](uint64_t, uint64_t len) { out += len; },
+                   [&](uint64_t len) {
+                       out += len; poff += len; ++e;
+                       if (out - cuts.back().out >= TASK) cuts.push_back(Cut{e, out, poff});
+                   });
         P->pool->parallel_for(cuts.size(), [&](size_t t) {
-            const Cut& c = cuts[t];
-            const size_t e1 = t + 1 < cuts.size() ? cuts[t + 1].e : ev.size();
-            uint64_t cur = c.cursor, o = c.out, po = c.poff;
-            for (size_t i = c.e; i < e1; ++i) {
-                const uint64_t run = ev[i].in_start - cur;
-                // (a long run of untouched records — a clean chunk has few events — is split so that no task copies much more than the others)
-                if (run) { memcpy(dst + o, in + cur, (size_t)run); o += run; }
-                if (ev[i].out_len) { memcpy(dst + o, patch + po, ev[i].out_len); o += ev[i].out_len; po += ev[i].out_len; }
-                cur = (uint64_t)ev[i].in_start + ev[i].in_len;
-            }
-            if (t + 1 == cuts.size() && end > cur) memcpy(dst + o, in + cur, (size_t)(end - cur));
+            const bool last = t + 1 == cuts.size();
+            uint64_t o = cuts[t].out, po = cuts[t].poff;
+            walk_spans(ev, cuts[t].e, last ? n_ev : cuts[t + 1].e, last ? sp.end[f] : 0,
+                       [&](uint64_t at, uint64_t len) { memcpy(dst + o, in + at, (size_t)len); o += len; },
+                       [&](uint64_t len) { if (len) { memcpy(dst + o, patch + po, (size_t)len); o += len; po += len; } });
         });
     }
 
@@ -1684,55 +1163,35 @@ struct Run {
     // record with everything before it written.  The device reports the earliest such record of the chunk (aqc_error_record): the
     // chunk is cut there and becomes the run's last one — the writer commits it in its turn, then the pipe stops and aqc_pipe_run
     // returns the error.  (Chunks are committed in order: a death in a later chunk never overtakes an earlier chunk's records.)
-    bool dies_at_record(aqc_ctx* c, int slot, int rc, uint64_t chunk_idx, uint64_t& n, bool& fatal) {
+    bool dies_at_record(Turn& t, int rc) {
         if (rc != AQC_ERR_INDEX && rc != AQC_ERR_ALPHABET && rc != AQC_ERR_ARG) return false;
         uint64_t rec = UINT64_MAX;
-        if (aqc_error_record(c, slot, &rec) || rec == UINT64_MAX || rec >= n) return false;
+        if (aqc_error_record(t.c, t.slot, &rec) || rec == UINT64_MAX || rec >= t.n) return false;
         {
             std::lock_guard<std::mutex> g(err_mu);
-            if (fatal_chunk == UINT64_MAX || chunk_idx < fatal_chunk) {
-                fatal_chunk = chunk_idx;
+            if (fatal_chunk == UINT64_MAX || t.j.idx < fatal_chunk) {
+                fatal_chunk = t.j.idx;
                 fatal_err = aqc_last_error();
                 fatal_code = rc;
             }
         }
-        n = rec;
-        fatal = true;
+        t.n = rec;
+        t.fatal = true;
         return true;
     }
 
-    // ---- writer: commit in chunk order ------------------------------------------------------------------------------------
-    static void bgzf_block(const uint8_t* src, size_t n, int level, std::vector<uint8_t>& out) {
-        // one gzip member with the BGZF extra field (BC: total block size - 1); members concatenate into one valid .gz.
-        // The deflate stream is the pipe's own (aqc_deflate.cpp); `--compression 0` stores.
-        out.resize(18 + aqcgz::deflate_bound(n) + 8);
-        const size_t clen = aqcgz::deflate_block(src, n, level, out.data() + 18);
-        const size_t bsize = 18 + clen + 8;
-        static const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-        memcpy(out.data(), hdr, 16);
-        out[16] = (uint8_t)((bsize - 1) & 0xff);
-        out[17] = (uint8_t)((bsize - 1) >> 8);
-        const uint32_t crc = aqcgz::crc32_fast(0u, src, n);
-        uint8_t* t = out.data() + 18 + clen;
-        for (int k = 0; k < 4; ++k) { t[k] = (uint8_t)(crc >> (8 * k)); t[4 + k] = (uint8_t)((uint32_t)n >> (8 * k)); }
-        out.resize(bsize);
-    }
-
-    // a committed chunk on its way through the per-file writer threads; the last one to finish hands the buffer set back
-    struct Commit {
-        OutChunk oc;
-        std::atomic<int> remaining{0};
-    };
-    std::unique_ptr<BQueue<std::shared_ptr<Commit>>> fileq[6];
-
-    void release_set(const OutChunk& oc) {
-        for (int f = 0; f < 2; ++f) release_ring(f, oc.in_buf[f]);       // (spans mode: the chunk's input buffers were its good records)
-        if (oc.set < 0) return;
-        {
-            std::lock_guard<std::mutex> g(set_mu);
-            set_free[oc.worker * 2 + oc.set] = 1;
-        }
-        set_cv.notify_all();
+    // ---- commit in chunk order, one writer per file -----------------------------------------------------------------------------------
+    // What output file q receives from a chunk, and how many bytes of text that is (what bytes_out counts; a device-made .gz
+    // stream is gz_sizes[q] bytes in the file).  Read by the commit thread (whom to queue it for) and by the file writer (what to write).
+    enum class Feed { nothing, assembled, spans, stream, device_gz };
+    struct Share { Feed kind; uint64_t bytes; };
+    Share share_of(const OutChunk& oc, int q) const {
+        const int f = q / 3;
+        uint64_t bytes = oc.sizes[q];
+        Feed kind = !io->gzip_out ? Feed::stream : oc.gz ? Feed::device_gz : Feed::stream;
+        if (q % 3 == 0 && oc.good_ptr[f]) { kind = Feed::assembled; bytes = oc.good_bytes[f]; }       // the slot worker has put the chunk's good output together
+        else if (q % 3 == 0 && oc.spans) { kind = Feed::spans; bytes = oc.spans->good_total[f]; }    // the chunk's own bytes between the events, the rebuilt records at them
+        return Share{bytes ? kind : Feed::nothing, bytes};
     }
 
     void file_writer(int q) {
@@ -1741,55 +1200,50 @@ struct Run {
         while (fileq[q]->pop(cm)) {
             const OutChunk& oc = cm->oc;
             const uint64_t tw = now_ns();
-            if (!abort && q % 3 == 0 && oc.good_ptr[q / 3]) {
-                // the slot worker has put the chunk's good output together (spans mode "assemble")
-                if (oc.good_bytes[q / 3] && !out[q].append(oc.good_ptr[q / 3], (size_t)oc.good_bytes[q / 3])) fail(AQC_ERR_ARG, "write error on output %d (disk full?)", q);
-            } else if (!abort && oc.spans && q % 3 == 0) {
-                // the good file of input q / 3: the chunk's own bytes between the events, the rebuilt records (stream 0) at them
+            const Share sh = abort ? Share{Feed::nothing, 0} : share_of(oc, q);
+            const uint8_t* p = oc.set >= 0 ? P->wbufs[oc.worker].out[oc.set][q].p : nullptr;      // stream q as the device made it
+            bool ok = true;
+            switch (sh.kind) {
+            case Feed::nothing: break;
+            case Feed::assembled: ok = out[q].append(oc.good_ptr[q / 3], (size_t)sh.bytes); break;
+            case Feed::spans: {
+                // the good file of input q / 3: the rebuilt records are stream q
                 const OutChunk::Spans& sp = *oc.spans;
                 const int f = q / 3;
-                const uint8_t* patch = oc.sizes[q] ? P->wbufs[oc.worker].out[oc.set][q].p : nullptr;
                 std::vector<struct iovec> iov;
                 iov.reserve(2 * sp.ev[f].size() + 1);
-                uint64_t cursor = 0, poff = 0;
-                for (const aqc_span_event& e : sp.ev[f]) {
-                    if (e.in_start > cursor) iov.push_back({(void*)(sp.in[f] + cursor), (size_t)(e.in_start - cursor)});
-                    if (e.out_len) { iov.push_back({(void*)(patch + poff), (size_t)e.out_len}); poff += e.out_len; }
-                    cursor = (uint64_t)e.in_start + e.in_len;
-                }
-                if (sp.end[f] > cursor) iov.push_back({(void*)(sp.in[f] + cursor), (size_t)(sp.end[f] - cursor)});
-                if (!iov.empty() && !out[q].appendv(iov)) fail(AQC_ERR_ARG, "write error on output %d (disk full?)", q);
-            } else if (!abort && oc.sizes[q]) {
-                const uint8_t* p = P->wbufs[oc.worker].out[oc.set][q].p;
-                bool ok = true;
-                if (!io->gzip_out) ok = out[q].append(p, (size_t)oc.sizes[q]);
-                else if (oc.gz) ok = out[q].append(p, (size_t)oc.gz_sizes[q]);
-                else {
-                    const size_t blk = 0xff00;                    // BGZF: at most 64 KiB per member, headers included (stored: text + 31 bytes)
-                    const size_t nb = (oc.sizes[q] + blk - 1) / blk;
-                    std::vector<std::vector<uint8_t>> z(nb);
-                    P->pool->parallel_for(nb, [&](size_t i) {
-                        const size_t o = i * blk;
-                        bgzf_block(p + o, std::min<size_t>(blk, oc.sizes[q] - o), io->gzip_level, z[i]);
-                    });
-                    size_t total = 0;
-                    for (auto& b : z) total += b.size();
-                    std::vector<uint8_t> cat(total);
-                    size_t o = 0;
-                    for (auto& b : z) { memcpy(cat.data() + o, b.data(), b.size()); o += b.size(); }
-                    ok = out[q].append(cat.data(), total);
-                }
-                if (!ok) fail(AQC_ERR_ARG, "write error on output %d (disk full?)", q);
+                uint64_t poff = 0;
+                walk_spans(sp.ev[f].data(), 0, sp.ev[f].size(), sp.end[f],
+                           [&](uint64_t at, uint64_t len) { iov.push_back({(void*)(sp.in[f] + at), (size_t)len}); },
+                           [&](uint64_t len) { if (len) { iov.push_back({(void*)(p + poff), (size_t)len}); poff += len; } });
+                ok = out[q].appendv(iov);
+                break;
             }
+            case Feed::device_gz: ok = out[q].append(p, (size_t)oc.gz_sizes[q]); break;
+            case Feed::stream: ok = io->gzip_out ? append_bgzf(q, p, (size_t)sh.bytes) : out[q].append(p, (size_t)sh.bytes); break;
+            }
+            if (!ok) fail(AQC_ERR_ARG, "write error on output %d (disk full?)", q);
             ns_write += now_ns() - tw;
             if (cm->remaining.fetch_sub(1) == 1) release_set(oc);
             writes_done.fetch_add(1);
         }
     }
-    // (file, chunk) writes handed to the file writers / finished by them: the run that dies at a record stops the pipe only once
-    // EVERY chunk committed before it has reached its files (round-5 advisory: waiting for the fatal chunk's own files alone let
-    // stop_all() cancel earlier chunks still queued on a file the fatal chunk does not write to)
-    std::atomic<uint64_t> writes_queued{0}, writes_done{0};
+    // text -> BGZF members deflated on the pool -> file q
+    bool append_bgzf(int q, const uint8_t* p, size_t n) {
+        const size_t blk = 0xff00;                    // BGZF: at most 64 KiB per member, headers included (stored: text + 31 bytes)
+        const size_t nb = (n + blk - 1) / blk;
+        std::vector<std::vector<uint8_t>> z(nb);
+        P->pool->parallel_for(nb, [&](size_t i) {
+            const size_t o = i * blk;
+            bgzf_block(p + o, std::min<size_t>(blk, n - o), io->gzip_level, z[i]);
+        });
+        size_t total = 0;
+        for (auto& b : z) total += b.size();
+        std::vector<uint8_t> cat(total);
+        size_t o = 0;
+        for (auto& b : z) { memcpy(cat.data() + o, b.data(), b.size()); o += b.size(); }
+        return out[q].append(cat.data(), total);
+    }
 
     void writer() {
         bind_io_thread("commit");
@@ -1805,17 +1259,18 @@ struct Run {
                 auto cm = std::make_shared<Commit>();
                 cm->oc = cur;
                 int live = 0;
-                uint64_t to_file[6];
+                bool to_file[6];
                 for (int q = 0; q < 6; ++q) {
-                    to_file[q] = (q % 3 == 0 && cur.good_ptr[q / 3]) ? cur.good_bytes[q / 3] : (cur.spans && q % 3 == 0) ? cur.spans->good_total[q / 3] : cur.sizes[q];
-                    res->bytes_out[q] += to_file[q];
-                    if (cur.set >= 0 && to_file[q] && out[q].fd >= 0) ++live;
+                    const Share sh = share_of(cur, q);
+                    res->bytes_out[q] += sh.bytes;
+                    to_file[q] = sh.kind != Feed::nothing && out[q].fd >= 0;
+                    if (cur.set >= 0 && to_file[q]) ++live;
                 }
                 if (live == 0 || abort) release_set(cur);
                 else {
                     cm->remaining = live;
                     for (int q = 0; q < 6; ++q)
-                        if (to_file[q] && out[q].fd >= 0) { writes_queued.fetch_add(1); fileq[q]->push(cm); }
+                        if (to_file[q]) { writes_queued.fetch_add(1); fileq[q]->push(cm); }
                 }
                 res->chunks += 1;
                 res->fused_chunks += cur.fused ? 1 : 0;
@@ -1837,7 +1292,86 @@ struct Run {
             stop_all();
         }
     }
-    std::shared_ptr<Commit> fatal_commit;
+
+    // ---- the run, from the caller's thread ------------------------------------------------------------------------------------------
+    // 0, or AQC_ERR_ARG with the file named in g_pipe_err
+    int open_outputs() {
+        if (opt->no_output) return 0;
+        for (int q = 0; q < 6; ++q) {
+            const char* path = io->out_path[q / 3][q % 3];
+            if (!path) continue;
+            if (!out[q].open_(path)) {
+                snprintf(g_pipe_err, sizeof(g_pipe_err), "cannot open %s for writing", path);
+                for (int k = 0; k < q; ++k) out[k].close_();
+                return AQC_ERR_ARG;
+            }
+        }
+        return 0;
+    }
+    template <class Body>
+    void timed(int kind, Body&& body) {
+        body();
+        cpu_us[kind] += (long)(thread_cpu_s() * 1e6);
+    }
+    void run_threads(double t0) {
+        cpu_proc0 = process_cpu_s();
+        cpu_pool0 = dbg ? P->pool->cpu_seconds() : 0.0;
+        std::vector<std::thread> fw;
+        for (int q = 0; q < 6; ++q)
+            if (out[q].fd >= 0) fw.emplace_back([this, q] { timed(0, [&] { file_writer(q); }); });
+        std::vector<std::thread> th;
+        for (int f = 0; f < nf; ++f) th.emplace_back([this, f] { timed(1, [&] { reader(f); }); });
+        th.emplace_back([this] { timed(2, [&] { dispatcher(); }); });
+        for (int ci = 0; ci < P->n_ctx; ++ci)
+            for (int s = 0; s < P->slots; ++s) th.emplace_back([this, ci, s] { timed(3, [&] { worker(ci, s); }); });
+        std::thread wr([this] { timed(4, [&] { writer(); }); });
+        for (auto& t : th) t.join();
+        if (dbg) fprintf(stderr, "pipe: readers / workers done at %.4f s\n", now_s() - t0);
+        // all producers are done: if the last chunk never arrived (abort / anomaly) the writer must not wait for it
+        outq.close();
+        wr.join();
+        for (auto& t : fw) t.join();
+        if (dbg) fprintf(stderr, "pipe: writers done at %.4f s\n", now_s() - t0);
+    }
+    void close_outputs() {
+        for (int q = 0; q < 6; ++q) {
+            if (out[q].fd < 0) continue;
+            if (io->gzip_out && !abort) {
+                // an empty BGZF member terminates the file (and makes an output with no records a valid .gz)
+                std::vector<uint8_t> e;
+                bgzf_block((const uint8_t*)"", 0, io->gzip_level, e);
+                (void)out[q].append(e.data(), e.size());
+            }
+            out[q].close_();
+        }
+    }
+    void debug_report(double t0) {
+        fprintf(stderr, "pipe: files closed at %.4f s\n", now_s() - t0);
+        const double proc = process_cpu_s() - cpu_proc0, pool = P->pool->cpu_seconds() - cpu_pool0;
+        double named = 0;
+        for (auto& c : cpu_us) named += 1e-6 * (double)c.load();
+        fprintf(stderr, "pipe: CPU seconds — process %.3f = pool %.3f + readers %.3f + dispatcher %.3f + slot workers %.3f + commit %.3f + file writers %.3f + other threads (GPU runtime, caller) %.3f\n",
+                proc, pool, 1e-6 * cpu_us[1], 1e-6 * cpu_us[2], 1e-6 * cpu_us[3], 1e-6 * cpu_us[4], 1e-6 * cpu_us[0], proc - pool - named);
+        uint64_t ds[8];
+        aqcgz::device_offload_stats(ds);
+        if (ds[5]) fprintf(stderr, "pipe: device gunzip so far (process-wide) — %llu groups, %llu sections given / %llu found; ms in scan %.1f, decode %.1f, chain + gather %.1f, H2D %.1f, D2H %.1f\n",
+                           (unsigned long long)ds[5], (unsigned long long)ds[6], (unsigned long long)ds[7], ds[0] / 1e3, ds[1] / 1e3, ds[2] / 1e3, ds[3] / 1e3, ds[4] / 1e3);
+        uint64_t rs[4];
+        aqcgz::device_resolve_stats(rs);
+        if (rs[0]) fprintf(stderr, "pipe: markers + CRC-32 resolved on the device so far (process-wide) — %llu runs of %llu sections, %.1f MB of text, %.1f ms inside resolve()\n",
+                           (unsigned long long)rs[0], (unsigned long long)rs[1], 1e-6 * (double)rs[3], rs[2] / 1e3);
+#ifdef AQC_GZ_PROFILE
+        fprintf(stderr, "pipe: gunzip thread-CPU ms — find %ld, decode (find included) %ld, translate %ld, crc %ld, consumer waiting %ld, accept %ld\n", aqcgz::gz_prof[0].exchange(0) / 1000,
+                aqcgz::gz_prof[1].exchange(0) / 1000, aqcgz::gz_prof[2].exchange(0) / 1000, aqcgz::gz_prof[3].exchange(0) / 1000, aqcgz::gz_prof[4].exchange(0) / 1000, aqcgz::gz_prof[5].exchange(0) / 1000);
+#endif
+    }
+    // the run's error, if any, into g_pipe_err: its code (`dflt` where the failure named none), or 0
+    int report_error(int dflt) {
+        if (err.empty()) return 0;
+        std::lock_guard<std::mutex> g(g_pipe_err_mu);
+        snprintf(g_pipe_err, sizeof(g_pipe_err), "%s", err.c_str());
+        return err_code ? err_code : dflt;
+    }
 };
 
 }  // namespace
@@ -1902,15 +1436,7 @@ void aqc_pipe_destroy(aqc_pipe* p) {
             if (p->gz_offload[f] && !p->gz_offload[f]->gave_up() && g_offload_pool.size() < 16)
                 g_offload_pool.push_back(PooledOffload{p->gz_offload_device[f], p->gz_offload_group[f], p->gz_offload_warm[f], std::move(p->gz_offload[f])});
     }
-    for (int f = 0; f < 2; ++f)
-        for (auto& b : p->in_buf[f]) b.release();
-    for (auto& w : p->wbufs)
-        for (int s = 0; s < 2; ++s)
-            for (int q = 0; q < 6; ++q) w.out[s][q].release();
-    for (auto& w : p->wbufs)
-        for (int s = 0; s < 2; ++s)
-            for (int f = 0; f < 2; ++f) w.good[s][f].release();
-    delete p;
+    delete p;       // (its buffers free themselves, here: HostBuf)
 }
 
 int aqc_pipe_run(aqc_pipe* P, const aqc_pipe_io* io, const aqc_pipe_opts* opt, aqc_pipe_result* res) {
@@ -1918,134 +1444,12 @@ int aqc_pipe_run(aqc_pipe* P, const aqc_pipe_io* io, const aqc_pipe_opts* opt, a
     memset(res, 0, sizeof(*res));
     if (!io->in_path[0] && !io->in_mem[0]) return AQC_ERR_ARG;
     const double t0 = now_s();
-    Run R;
-    R.P = P;
-    R.io = io;
-    R.opt = opt;
-    R.res = res;
-    R.nf = (io->in_path[1] || io->in_mem[1]) ? 2 : 1;
-    R.K = opt->chunk_records ? opt->chunk_records : (1u << 17);
-    {
-        // Plain-text outputs, OPT-IN: the good records that go out as their own bytes never leave the host (aqc_format_spans): no copy
-        // on the device (the device step of 10 M reads 4.7 -> 3.2 ms, 17.3 -> 10.7 GB of HBM traffic), no download (3.1 of the
-        // 3.44 GB per 10 M reads stay off PCIe: pinned -> pinned 105 -> 122 - 160 Mreads/s).  Two ways to get them into the good files:
-        //   AQC_SPANS=1  writev (round 5): the file writers writev the pieces straight from the input buffers — no host copy, but a
-        //                run of whole records is 3 - 4 KB in the bench workload and an iovec costs the kernel ~60 ns: 9.2 - 9.9 GB/s
-        //                against write()'s 11 - 12 on a path bound by exactly those two writers (file -> file 0.18 -> 0.23 s,
-        //                profiles/r05_spans_ab.txt);
-        //   AQC_SPANS=2  assemble (round 6): the slot worker puts each good file's chunk together in host memory — the chunk's own
-        //                bytes between the events, the rebuilt records at them, copied on the pool in ~1 MiB tasks — and the file
-        //                writer issues one big write() as it always did.  Tried as the DEFAULT and taken back: interleaved on one
-        //                box the text step gives 50.2 - 51.4 Mreads/s, this 39.6 - 48.2 (two inputs at once: 72 - 76 against 55 - 68;
-        //                the 100 M-read input 19 against 44 - 52; profiles/r06_spans_assemble_ab.txt) — the host copies every
-        //                output byte once more, on the 16 granted CPUs that the readers' and the writers' own copies already
-        //                share, and the writers then read buffers that pool threads of either socket have just written.
-        // So the DEFAULT stays the text step (aqc_format: everything formatted on the device and downloaded): a run is bound by its
-        // two file writers, and the text step is what leaves them alone.  Both spans modes pay where PCIe or the device is the
-        // bound and the host has cycles to spare.  (.gz output needs the whole text on the device, where its members are built; a
-        // .gz input decoded on the device keeps its text in HBM and has no host copy to assemble from.)
-        const char* e = getenv("AQC_SPANS");
-        R.spans_on = !io->gzip_out && !opt->no_output && e && (e[0] == '1' || e[0] == '2');
-        R.spans_assemble = R.spans_on && e[0] == '2';
-    }
-    for (int f = 0; f < R.nf; ++f) {
-        R.inq[f].reset(new BQueue<InChunk>(2));
-        // (the whole ring only when chunks keep their input buffers until they are written — spans mode; else one buffer per slot + two:
-        //  every buffer used is a buffer page-locked, which a one-shot run pays for)
-        const size_t use = (R.spans_on && !R.spans_assemble) ? P->in_buf[f].size() : std::min(P->in_buf[f].size(), (size_t)(P->n_ctx * P->slots + 2));
-        R.ring_free[f].assign(P->in_buf[f].size(), 0);
-        for (size_t i = 0; i < use; ++i) R.ring_free[f][i] = 1;
-    }
-    for (int i = 0; i < P->n_ctx; ++i) R.jobq.emplace_back(new BQueue<Run::Job>((size_t)P->slots));
-    R.set_free.assign(P->wbufs.size() * 2, 1);
-    {
-        // contexts on the same physical device share one pair of DMA gates
-        std::vector<int> devs;
-        for (int i = 0; i < P->n_ctx; ++i) {
-            const int dv = aqc_device_index(P->ctx[i]);
-            int g = -1;
-            for (size_t k = 0; k < devs.size(); ++k) if (devs[k] == dv) g = (int)k;
-            if (g < 0) { g = (int)devs.size(); devs.push_back(dv); }
-            R.group_of_ctx.push_back(g);
-        }
-        for (size_t k = 0; k < devs.size(); ++k) { R.up_gate.emplace_back(new Run::Gate()); R.down_gate.emplace_back(new Run::Gate()); }
-        R.group_tickets.assign(devs.size(), 0);
-        // one node for the I/O threads when every context's GPU hangs off the same one
-        R.io_node = aqc_device_numa_node(P->ctx[0]);
-        for (int i = 1; i < P->n_ctx; ++i)
-            if (aqc_device_numa_node(P->ctx[i]) != R.io_node) R.io_node = -1;
-    }
-    if (!opt->no_output) {
-        for (int q = 0; q < 6; ++q) {
-            const char* path = io->out_path[q / 3][q % 3];
-            if (!path) continue;
-            if (!R.out[q].open_(path)) {
-                snprintf(g_pipe_err, sizeof(g_pipe_err), "cannot open %s for writing", path);
-                for (int k = 0; k < q; ++k) R.out[k].close_();
-                return AQC_ERR_ARG;
-            }
-        }
-    }
-    for (int q = 0; q < 6; ++q) R.fileq[q].reset(new BQueue<std::shared_ptr<Run::Commit>>(0));
-    {
-        const char* e = getenv("AQC_GZ_DEVICE");
-        R.gz_on_device = io->gzip_out && io->gzip_level >= 1 && !opt->no_output && !(e && e[0] == '0');
-    }
-    const bool dbg = getenv("AQC_PIPE_DEBUG") != nullptr;
-    if (dbg) fprintf(stderr, "pipe: outputs open at %.4f s\n", now_s() - t0);
-    // (AQC_PIPE_DEBUG: CPU seconds per kind of thread, printed at the end — who uses the host's cores)
-    std::atomic<long> cpu_us[5] = {{0}, {0}, {0}, {0}, {0}};       // file writers, readers, dispatcher, slot workers, commit thread
-    const double cpu_proc0 = process_cpu_s(), cpu_pool0 = dbg ? P->pool->cpu_seconds() : 0.0;
-    auto timed = [&cpu_us](int kind, auto&& body) { body(); cpu_us[kind] += (long)(thread_cpu_s() * 1e6); };
-    std::vector<std::thread> fw;
-    for (int q = 0; q < 6; ++q)
-        if (R.out[q].fd >= 0) fw.emplace_back([&R, q, &timed] { timed(0, [&] { R.file_writer(q); }); });
-    std::vector<std::thread> th;
-    for (int f = 0; f < R.nf; ++f) th.emplace_back([&R, f, &timed] { timed(1, [&] { R.reader(f); }); });
-    th.emplace_back([&R, &timed] { timed(2, [&] { R.dispatcher(); }); });
-    for (int ci = 0; ci < P->n_ctx; ++ci)
-        for (int s = 0; s < P->slots; ++s) th.emplace_back([&R, ci, s, &timed] { timed(3, [&] { R.worker(ci, s); }); });
-    std::thread wr([&R, &timed] { timed(4, [&] { R.writer(); }); });
-    for (auto& t : th) t.join();
-    if (dbg) fprintf(stderr, "pipe: readers / workers done at %.4f s\n", now_s() - t0);
-    // all producers are done: if the last chunk never arrived (abort / anomaly) the writer must not wait for it
-    R.outq.close();
-    wr.join();
-    for (auto& t : fw) t.join();
-    if (dbg) fprintf(stderr, "pipe: writers done at %.4f s\n", now_s() - t0);
-    for (int q = 0; q < 6; ++q) {
-        if (R.out[q].fd >= 0) {
-            if (io->gzip_out && !R.abort) {
-                // an empty BGZF member terminates the file (and makes an output with no records a valid .gz)
-                std::vector<uint8_t> e;
-                Run::bgzf_block((const uint8_t*)"", 0, io->gzip_level, e);
-                (void)R.out[q].append(e.data(), e.size());
-            }
-            R.out[q].close_();
-        }
-    }
-    if (dbg) {
-        fprintf(stderr, "pipe: files closed at %.4f s\n", now_s() - t0);
-        const double proc = process_cpu_s() - cpu_proc0, pool = P->pool->cpu_seconds() - cpu_pool0;
-        double named = 0;
-        for (auto& c : cpu_us) named += 1e-6 * (double)c.load();
-        fprintf(stderr, "pipe: CPU seconds — process %.3f = pool %.3f + readers %.3f + dispatcher %.3f + slot workers %.3f + commit %.3f + file writers %.3f + other threads (GPU runtime, caller) %.3f\n",
-                proc, pool, 1e-6 * cpu_us[1], 1e-6 * cpu_us[2], 1e-6 * cpu_us[3], 1e-6 * cpu_us[4], 1e-6 * cpu_us[0], proc - pool - named);
-        {
-            uint64_t ds[8];
-            aqcgz::device_offload_stats(ds);
-            if (ds[5]) fprintf(stderr, "pipe: device gunzip so far (process-wide) — %llu groups, %llu sections given / %llu found; ms in scan %.1f, decode %.1f, chain + gather %.1f, H2D %.1f, D2H %.1f\n",
-                               (unsigned long long)ds[5], (unsigned long long)ds[6], (unsigned long long)ds[7], ds[0] / 1e3, ds[1] / 1e3, ds[2] / 1e3, ds[3] / 1e3, ds[4] / 1e3);
-            uint64_t rs[4];
-            aqcgz::device_resolve_stats(rs);
-            if (rs[0]) fprintf(stderr, "pipe: markers + CRC-32 resolved on the device so far (process-wide) — %llu runs of %llu sections, %.1f MB of text, %.1f ms inside resolve()\n",
-                               (unsigned long long)rs[0], (unsigned long long)rs[1], 1e-6 * (double)rs[3], rs[2] / 1e3);
-        }
-#ifdef AQC_GZ_PROFILE
-        fprintf(stderr, "pipe: gunzip thread-CPU ms — find %ld, decode (find included) %ld, translate %ld, crc %ld, consumer waiting %ld, accept %ld\n", aqcgz::gz_prof[0].exchange(0) / 1000,
-                aqcgz::gz_prof[1].exchange(0) / 1000, aqcgz::gz_prof[2].exchange(0) / 1000, aqcgz::gz_prof[3].exchange(0) / 1000, aqcgz::gz_prof[4].exchange(0) / 1000, aqcgz::gz_prof[5].exchange(0) / 1000);
-#endif
-    }
+    Run R(P, io, opt, res);
+    if (const int rc = R.open_outputs()) return rc;
+    if (R.dbg) fprintf(stderr, "pipe: outputs open at %.4f s\n", now_s() - t0);
+    R.run_threads(t0);
+    R.close_outputs();
+    if (R.dbg) R.debug_report(t0);
     res->records = R.records.load();
     res->t_read = 1e-9 * (double)R.ns_read.load(); res->t_count = 1e-9 * (double)R.ns_count.load();
     res->t_frame = 1e-9 * (double)R.ns_frame.load(); res->t_kernels = 1e-9 * (double)R.ns_kernels.load();
@@ -2054,12 +1458,7 @@ int aqc_pipe_run(aqc_pipe* P, const aqc_pipe_io* io, const aqc_pipe_opts* opt, a
     res->anomaly = R.anomaly ? 1 : 0;
     res->extra_bases = R.extra_bases;
     res->seconds = now_s() - t0;
-    if (!R.err.empty()) {
-        std::lock_guard<std::mutex> g(g_pipe_err_mu);
-        snprintf(g_pipe_err, sizeof(g_pipe_err), "%s", R.err.c_str());
-        return R.err_code ? R.err_code : AQC_ERR_HIP;
-    }
-    return 0;
+    return R.report_error(AQC_ERR_HIP);
 }
 
 // ---- byte sources on their own: what fastq.Reader's file object is upstream (fastq.py:23-28), with the pipe's readers behind
@@ -2130,7 +1529,7 @@ int aqc_bgzf_compress(const uint8_t* src, uint64_t n, int32_t level, uint8_t* ds
     uint64_t o = 0;
     std::vector<uint8_t> z;
     for (uint64_t i = 0; i < n || (n == 0 && i == 0); i += blk) {
-        Run::bgzf_block(src + i, (size_t)std::min<uint64_t>(blk, n - i), level, z);
+        bgzf_block(src + i, (size_t)std::min<uint64_t>(blk, n - i), level, z);
         if (o + z.size() > cap) return AQC_ERR_ARG;
         memcpy(dst + o, z.data(), z.size());
         o += z.size();
@@ -2140,6 +1539,7 @@ int aqc_bgzf_compress(const uint8_t* src, uint64_t n, int32_t level, uint8_t* ds
     return 0;
 }
 
+// one reader of the pipe on its own: a pipe without contexts whose two ring buffers are plain memory, a run without output
 int aqc_pipe_split(const aqc_pipe_io* io, int32_t file_index, uint64_t chunk_records, int32_t io_threads, uint64_t* bytes,
                    uint64_t* lines, uint64_t cap, uint64_t* n_chunks, uint32_t* crc) {
     if (!io || file_index < 0 || file_index > 1 || !n_chunks || !crc) return AQC_ERR_ARG;
@@ -2152,17 +1552,11 @@ int aqc_pipe_split(const aqc_pipe_io* io, int32_t file_index, uint64_t chunk_rec
         for (auto& b : P.in_buf[f]) b.pageable = true;
     }
     aqc_pipe_opts opt{};
+    opt.chunk_records = chunk_records;
+    opt.no_output = 1;
     aqc_pipe_result res{};
-    Run R;
-    R.P = &P;
-    R.io = io;
-    R.opt = &opt;
-    R.res = &res;
-    R.nf = 1;
-    R.K = chunk_records ? chunk_records : (1u << 17);
     const int f = file_index;
-    R.inq[f].reset(new BQueue<InChunk>(2));
-    R.ring_free[f].assign(P.in_buf[f].size(), 1);
+    Run R(&P, io, &opt, &res, f);
     std::thread rd([&R, f] { R.reader(f); });
     uint64_t k = 0;
     uint32_t c = (uint32_t)crc32(0L, Z_NULL, 0);
@@ -2174,16 +1568,9 @@ int aqc_pipe_split(const aqc_pipe_io* io, int32_t file_index, uint64_t chunk_rec
         R.release_ring(f, ch.buf);
     }
     rd.join();
-    for (int g = 0; g < 2; ++g)
-        for (auto& b : P.in_buf[g]) b.release();
     *n_chunks = k;
     *crc = c;
-    if (!R.err.empty()) {
-        std::lock_guard<std::mutex> g(g_pipe_err_mu);
-        snprintf(g_pipe_err, sizeof(g_pipe_err), "%s", R.err.c_str());
-        return R.err_code ? R.err_code : AQC_ERR_ARG;
-    }
-    return 0;
+    return R.report_error(AQC_ERR_ARG);
 }
 
 }  // extern "C"
