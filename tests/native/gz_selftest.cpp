@@ -60,6 +60,130 @@ static bool zlib_inflate_raw(const uint8_t* src, size_t n, std::vector<uint8_t>&
     return rc == Z_STREAM_END;
 }
 
+// ---- D. build_codebook: the code the device encoders share (aqc_gzdev.hpp), checked by its properties and through zlib ----------
+static const int CB_LEN_BASE[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
+static const int CB_LEN_EXTRA[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
+static const int CB_DIST_BASE[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
+static const int CB_DIST_EXTRA[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
+
+// depth of the deepest leaf of the UNLIMITED Huffman code for counts + 1 (what build_codebook feeds its builder): says whether a
+// case reaches the 15-bit repair at all
+static int unlimited_depth(const uint32_t* freq, int n) {
+    std::vector<std::pair<uint64_t, int>> nodes;       // (weight, depth of the deepest leaf below)
+    for (int s = 0; s < n; ++s) nodes.push_back({(uint64_t)freq[s] + 1u, 0});
+    while (nodes.size() > 1) {
+        std::sort(nodes.begin(), nodes.end(), [](const std::pair<uint64_t, int>& a, const std::pair<uint64_t, int>& b) { return a.first != b.first ? a.first > b.first : a.second > b.second; });
+        const auto a = nodes.back(); nodes.pop_back();
+        const auto b = nodes.back(); nodes.pop_back();
+        nodes.push_back({a.first + b.first, std::max(a.second, b.second) + 1});
+    }
+    return nodes[0].second;
+}
+
+// lengths in 1..15, Kraft sum exactly one, and the codes are RFC 1951 3.2.2's for those lengths (stored bit-reversed)
+static void check_code(const char* what, const char* which, const uint32_t* code, int n) {
+    uint32_t kraft = 0;
+    int count[16] = {0};
+    for (int s = 0; s < n; ++s) {
+        const int l = (int)(code[s] >> 16);
+        CHECK(l >= 1 && l <= 15, "build_codebook %s: %s symbol %d has length %d", what, which, s, l);
+        if (l < 1 || l > 15) return;
+        kraft += 1u << (15 - l);
+        count[l]++;
+    }
+    CHECK(kraft == (1u << 15), "build_codebook %s: %s code is not complete (Kraft sum %u / 32768)", what, which, kraft);
+    uint32_t next[16], c = 0;
+    for (int l = 1; l <= 15; ++l) { c = (c + (uint32_t)count[l - 1]) << 1; next[l] = c; }
+    for (int s = 0; s < n; ++s) {
+        const int l = (int)(code[s] >> 16);
+        const uint32_t canon = next[l]++;
+        uint32_t rev = 0;
+        for (int k = 0; k < l; ++k) rev |= ((canon >> k) & 1u) << (l - 1 - k);
+        CHECK((code[s] & 0xffffu) == rev, "build_codebook %s: %s symbol %d: code %#x, canonical %#x (length %d)", what, which, s, code[s] & 0xffffu, rev, l);
+    }
+}
+
+// expect_limit: 1 = the counts must force the 15-bit limit, 0 = must not, -1 = either
+static void check_codebook(const char* what, const uint32_t* lit_freq, const uint32_t* dist_freq, int expect_limit) {
+    GzCodebook cb;
+    const bool ok = build_codebook(lit_freq, dist_freq, &cb);
+    CHECK(ok, "build_codebook %s failed", what);
+    if (!ok) return;
+    const int deep = std::max(unlimited_depth(lit_freq, 286), unlimited_depth(dist_freq, 30));
+    CHECK(expect_limit < 0 || (deep > 15) == (expect_limit == 1), "build_codebook %s: unlimited depth %d, the 15-bit limit was %s", what, deep, expect_limit ? "to be forced" : "not to be reached");
+    check_code(what, "literal/length", cb.lit, 286);
+    check_code(what, "distance", cb.dist, 30);
+    CHECK(cb.hdr_bits >= 17 && cb.hdr_bits <= 8 * sizeof(cb.hdr), "build_codebook %s: %u header bits", what, cb.hdr_bits);
+    // one block that uses every code: the header, all 256 literals, matches that fill the window, then every distance symbol and
+    // every length symbol with the smallest and the largest extra bits in turn, end of block
+    std::vector<uint8_t> bits((size_t)192 * 4 + 64 * 1024, 0), expect;
+    uint64_t at = 0;
+    auto put = [&](uint32_t v, int n) { for (int k = 0; k < n; ++k, ++at) if ((v >> k) & 1u) bits[at >> 3] |= (uint8_t)(1u << (at & 7)); };
+    for (uint32_t i = 0; i < cb.hdr_bits; ++i) put((cb.hdr[i >> 5] >> (i & 31)) & 1u, 1);
+    auto match = [&](int len, int dist) {
+        int ls = 28, ds = 29;
+        while (CB_LEN_BASE[ls] > len) --ls;
+        if (len == 258) ls = 28;
+        while (CB_DIST_BASE[ds] > dist) --ds;
+        put(cb.lit[257 + ls] & 0xffffu, (int)(cb.lit[257 + ls] >> 16));
+        put((uint32_t)(len - CB_LEN_BASE[ls]), CB_LEN_EXTRA[ls]);
+        put(cb.dist[ds] & 0xffffu, (int)(cb.dist[ds] >> 16));
+        put((uint32_t)(dist - CB_DIST_BASE[ds]), CB_DIST_EXTRA[ds]);
+        for (int k = 0; k < len; ++k) expect.push_back(expect[expect.size() - (size_t)dist]);
+    };
+    for (int b = 0; b < 256; ++b) { put(cb.lit[b] & 0xffffu, (int)(cb.lit[b] >> 16)); expect.push_back((uint8_t)b); }
+    while (expect.size() < 32768) match(258, 255);
+    for (int j = 0; j < 30; ++j) {
+        const int ls = j % 29;
+        // (length symbol 27 with all extra bits set would say 258, which has a symbol of its own)
+        const int xl = (j & 1) ? (1 << CB_LEN_EXTRA[ls]) - 1 - (ls == 27 ? 1 : 0) : 0;
+        const int xd = (j & 1) ? 0 : (1 << CB_DIST_EXTRA[j]) - 1;
+        match(CB_LEN_BASE[ls] + xl, CB_DIST_BASE[j] + xd);
+    }
+    put(cb.lit[256] & 0xffffu, (int)(cb.lit[256] >> 16));
+    std::vector<uint8_t> back;
+    const bool inflated = zlib_inflate_raw(bits.data(), (size_t)((at + 7) >> 3), back, expect.size());
+    CHECK(inflated && back == expect, "build_codebook %s: zlib says %d, %zu bytes of %zu", what, (int)inflated, back.size(), expect.size());
+}
+
+static void codebook_cases(const std::vector<uint8_t>& fastq) {
+    uint32_t lit[286], dist[30];
+    auto clear = [&] { memset(lit, 0, sizeof(lit)); memset(dist, 0, sizeof(dist)); };
+    clear();
+    check_codebook("all-zero counts", lit, dist, 0);
+    clear(); lit['E'] = 1000000;
+    check_codebook("one literal", lit, dist, 0);
+    // Fibonacci-like (each count 1.34 x the one before) over 40 literals: 357 K symbols in all, within the 16 x 65280 bytes a
+    // sample can hold; with the 246 symbols of count 1 below them the unlimited code is deeper than 15 bits.  The distance
+    // counts are Fibonacci's own over 24 symbols (121 K matches).
+    clear();
+    {
+        double c = 1;
+        uint64_t sum = 0;
+        for (int k = 0; k < 40; ++k, c *= 1.34) { lit[33 + k] = (uint32_t)c; sum += lit[33 + k]; }
+        uint32_t a = 1, b = 1;
+        for (int k = 0; k < 24; ++k) { dist[k] = a; const uint32_t t = a + b; a = b; b = t; }
+        CHECK(sum <= 16u * 65280u, "the Fibonacci-like counts add up to %llu", (unsigned long long)sum);
+    }
+    check_codebook("fibonacci-like", lit, dist, 1);
+    clear(); lit['A'] = 500; lit[257 + 28] = 40; dist[0] = 40;
+    check_codebook("only distance symbol 0", lit, dist, 0);
+    // a real FASTQ buffer: its bytes, and its runs of 5 and more as matches at distance 1 (the sampling pass's rule)
+    clear();
+    for (size_t i = 0; i < fastq.size();) {
+        size_t r = 1;
+        while (i + r < fastq.size() && fastq[i + r] == fastq[i] && r < 259) ++r;
+        lit[fastq[i]]++;
+        if (r - 1 >= 5) {
+            int ls = 28;
+            while (CB_LEN_BASE[ls] > (int)(r - 1)) --ls;
+            lit[257 + ls]++; dist[0]++;
+            i += r;
+        } else ++i;
+    }
+    check_codebook("fastq", lit, dist, -1);
+}
+
 int main(int argc, char** argv) {
     const bool bench = argc > 1 && !strcmp(argv[1], "bench");
     std::vector<std::pair<std::string, std::vector<uint8_t>>> sets;
@@ -94,6 +218,8 @@ int main(int argc, char** argv) {
         }
         sets.push_back({"fibonacci", fib});
     }
+    // ---- D. build_codebook (first: it is quick)
+    codebook_cases(sets[0].second);
     // ---- A. inflate_raw vs zlib-made streams
     for (auto& ds : sets) {
         for (int level = 0; level <= 9; ++level) {
