@@ -17,7 +17,11 @@
 #include <vector>
 
 #include "aqc_dev.hpp"
-#include "aqc_kernels.hpp"
+#include "aqc_prim.hpp"
+#include "aqc_batch.hpp"
+#include "aqc_record.hpp"
+#include "aqc_qcstat.hpp"
+#include "aqc_seams.hpp"
 #include "aqc_fast.hpp"
 #include "aqc_text.hpp"
 #include "aqc_census.hpp"
@@ -207,9 +211,7 @@ static int check_status(Slot& sl) {
     return 0;
 }
 
-#ifndef AQC_FUSE_WPBT
-#define AQC_FUSE_WPBT 12
-#endif
+constexpr int FUSE_WPBT = 12;      // waves per workgroup of the fused verdict kernel
 template <int NW, bool PAIRED, int WPBT, bool BARCODE, bool FUSE = false>
 static void launch_fast(aqc_ctx* c, Slot* s, const aqc_config& cfg, const DevStats& st, uint64_t accum_limit, const FuseArgs* fz = nullptr) {
     constexpr uint64_t per_block = (uint64_t)WPBT * FastWaveLds<NW, PAIRED, FUSE>::PPW;
@@ -667,7 +669,7 @@ int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
             fz.fstate1 = (uint32_t*)s->fz_rec[0].p; fz.fstate2 = (uint32_t*)s->fz_rec[1].p;
             fz.state = (unsigned long long*)s->fz_state.p;
             fz.ticket = (unsigned int*)s->fz_misc.p; fz.abort = (int*)s->fz_misc.p + 1; fz.totals = (unsigned long long*)s->fz_misc.p + 1;
-            launch_fast<10, true, AQC_FUSE_WPBT, false, true>(c, s, cfg, st, accum_limit, &fz);
+            launch_fast<10, true, FUSE_WPBT, false, true>(c, s, cfg, st, accum_limit, &fz);
             s->fused = true;
         } else if (s->max_len <= 160) {
             launch_fast_tier<10, 16, 12>(c, s, cfg, st, accum_limit);
@@ -928,7 +930,7 @@ static int frame_impl(aqc_ctx* c, int slot, const aqc_text_chunk* ch, aqc_frame_
     }
     // 3. lock-step record count (preprocesser.py:412-429)
     // (a record whose quality line is not as long as its sequence line is a record like any other: fastq.py:37-49 does not look,
-    //  and every later stage keeps a view per string — LEN_IRR in aqc_kernels.hpp)
+    //  and every later stage keeps a view per string — LEN_IRR in aqc_batch.hpp)
     const uint64_t n = fo.n;
     memset(info, 0, sizeof(*info));
     info->n = n;
@@ -1101,9 +1103,6 @@ static int format_impl(aqc_ctx* c, int slot, int verdict_slot, uint64_t n, int32
         unsigned int* d_nwhole = d_ngen + GEN_LISTS;
         const bool sparse = v.spans || v.fused;
         unsigned copy_blocks = (unsigned)((n_tasks + (COPY_BLOCK / 32) * FMT_UNROLL - 1) / ((COPY_BLOCK / 32) * FMT_UNROLL));
-#ifdef AQC_COPY_PERSIST
-        if (copy_blocks > (unsigned)c->n_cu * AQC_COPY_PERSIST) copy_blocks = (unsigned)c->n_cu * AQC_COPY_PERSIST;
-#endif
         for (int pass = 0; pass < (v.store_overlap ? 2 : 1); ++pass) {
             HIP_TRY(hipMemsetAsync(d_ngen, 0, 2 * sizeof(unsigned int) * GEN_LISTS, s->stream));
             // GEN_LISTS x k workgroups; k from the worst case, at most 32 per list

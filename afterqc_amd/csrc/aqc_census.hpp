@@ -7,8 +7,9 @@
 #include <stdint.h>
 
 #include "afterqc_hip.h"
-#include "aqc_kernels.hpp"
-#include "aqc_text.hpp"
+#include "aqc_prim.hpp"
+#include "aqc_batch.hpp"      // LEN_MASK: the length words of a framed chunk
+#include "aqc_text.hpp"       // the text stage's own: its workgroup size (TXT_BLOCK) and the character classes of framing (is_space, is_digit)
 
 namespace aqc {
 
@@ -189,12 +190,7 @@ __global__ __launch_bounds__(TXT_BLOCK) void poly_census_kernel(const uint8_t* _
         mine += base != 0;
     }
     // exclusive prefix of the hits over the workgroup: in the wave by shuffles, across the waves through LDS
-    unsigned int incl = mine;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const unsigned int v = (unsigned int)__shfl_up((int)incl, d, WAVE);
-        if (lane >= d) incl += v;
-    }
+    const unsigned int incl = wave_incl_sum_shfl(mine, lane);
     if (lane == WAVE - 1) s_wave[wave] = incl;
     __syncthreads();
     unsigned int before = incl - mine, total = 0;

@@ -1,6 +1,6 @@
 // aqc_fast.hpp — the hot kernel: "one LANE per READ" (two lanes per pair), generation 5.
 //
-// Why: the wave-per-record kernel (aqc_kernels.hpp) spends ~1500 wave-instructions per pair, which
+// Why: the wave-per-record kernel (aqc_record.hpp) spends ~1500 wave-instructions per pair, which
 // caps it at ~1 % of the HBM roofline.  To stream pairs at a useful fraction of 8 TB/s the whole
 // pipeline must cost on the order of 100 wave-instructions per pair (256 CUs x 4 SIMDs x ~1.1 G
 // wave-instr/s / 5 G pairs/s), i.e. every lane has to do useful work all the time and byte
@@ -36,7 +36,11 @@
 // validates the alphabet on the fly (v_perm round trip; a record with any other byte is deferred).  Generation 2 needed a
 // separate canonicalisation pass (read 3.0 GB + write 3.2 GB per 5 M pairs, 2.8x the time of this kernel) for that.
 #pragma once
-#include "aqc_kernels.hpp"
+#include <type_traits>
+
+#include "afterqc_hip.h"
+#include "aqc_prim.hpp"
+#include "aqc_batch.hpp"
 
 namespace aqc {
 
@@ -47,15 +51,6 @@ constexpr uint32_t ODD = 0xAAAAAAAAu;
 constexpr uint32_t PADLO = 0x44444444u, PAD1 = 0x43414341u, PAD2 = 0x54475447u;
 constexpr int NONE_CAND = 0x7fffffff;
 
-// 16 bytes from an arbitrarily aligned address: one global_load_dwordx4
-__device__ __forceinline__ uint4 load16u(const uint8_t* p) {
-    uint4 v;
-#if defined(AQC_ABL) && (AQC_ABL & 128)
-    p = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(p) & ~(uintptr_t)15);      // (ablation: what would loads on the 16-byte grid give?)
-#endif
-    __builtin_memcpy(&v, p, 16);
-    return v;
-}
 // (mask & a) | (~mask & b): v_bfi_b32
 __device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) { return (a & mask) | (b & ~mask); }
 // bytes of d that are none of A C G T N come back non-zero: table round trip through the 3-bit code (c >> 1) & 7
@@ -68,52 +63,6 @@ __device__ __forceinline__ uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t 
 __device__ __forceinline__ uint32_t udot4(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_udot4(a, b, c, false); }
 // mask with the low 2*nb bits set, nb in 0..16
 __device__ __forceinline__ uint32_t base_mask(int nb) { return nb >= 16 ? 0xffffffffu : ((1u << (2 * nb)) - 1u); }
-
-// Wave-wide max / sum of a lane value, in uniform control flow (all 64 lanes active), as a wave-uniform result: four DPP
-// steps inside the rows of 16 lanes (lane ^ 1, lane ^ 2, half-row mirror, row mirror), then the four row results through
-// v_readlane and scalar arithmetic.  The __shfl_xor form goes through the LDS crossbar (six ds_bpermute round trips) and
-// keeps its six lane-address registers alive for the whole kernel.
-template <int CTRL>
-__device__ __forceinline__ int dpp_move(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false); }
-__device__ __forceinline__ int wave_max_i(int v) {
-    v = max(v, dpp_move<0xB1>(v));       // quad_perm [1,0,3,2]
-    v = max(v, dpp_move<0x4E>(v));       // quad_perm [2,3,0,1]
-    v = max(v, dpp_move<0x141>(v));      // row_half_mirror
-    v = max(v, dpp_move<0x140>(v));      // row_mirror
-    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-               max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-__device__ __forceinline__ void store16f(uint8_t* p, uint4 v) { __builtin_memcpy(p, &v, 16); }
-__device__ __forceinline__ int wave_sum_u(int v) {
-    v += dpp_move<0xB1>(v);
-    v += dpp_move<0x4E>(v);
-    v += dpp_move<0x141>(v);
-    v += dpp_move<0x140>(v);
-    return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) + (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
-}
-
-// Inclusive prefix sum / running maximum over the 64 lanes, in uniform control flow: four DPP row_shr steps scan the rows of 16
-// lanes (lanes shifted in from outside a row read 0), the three row totals come through v_readlane.
-template <int CTRL>
-__device__ __forceinline__ int dpp_shr0(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-__device__ __forceinline__ int wave_incl_sum(int v, int lane) {
-    v += dpp_shr0<0x111>(v);
-    v += dpp_shr0<0x112>(v);
-    v += dpp_shr0<0x114>(v);
-    v += dpp_shr0<0x118>(v);
-    const int t0 = __builtin_amdgcn_readlane(v, 15), t1 = __builtin_amdgcn_readlane(v, 31), t2 = __builtin_amdgcn_readlane(v, 47);
-    const int row = lane >> 4;
-    return v + (row >= 1 ? t0 : 0) + (row >= 2 ? t1 : 0) + (row >= 3 ? t2 : 0);
-}
-__device__ __forceinline__ int wave_incl_max(int v, int lane) {      // (values >= 0)
-    v = max(v, dpp_shr0<0x111>(v));
-    v = max(v, dpp_shr0<0x112>(v));
-    v = max(v, dpp_shr0<0x114>(v));
-    v = max(v, dpp_shr0<0x118>(v));
-    const int t0 = __builtin_amdgcn_readlane(v, 15), t1 = __builtin_amdgcn_readlane(v, 31), t2 = __builtin_amdgcn_readlane(v, 47);
-    const int row = lane >> 4;
-    return max(max(v, row >= 1 ? t0 : 0), max(row >= 2 ? t1 : 0, row >= 3 ? t2 : 0));
-}
 
 // 16 sequence bytes -> lo plane (2 bits/base: (c >> 1) & 3), e plane ('N' flag, bit 3 of the byte, on the odd bit)
 __device__ __forceinline__ void pack_dword(uint32_t d, uint32_t& lo8, uint32_t& e8) {
@@ -147,11 +96,7 @@ __device__ __forceinline__ void trim_view(int len, int front, int tail, int& st,
 
 // the length this kernel works with: a mate marked LEN_IRR (its quality line has a length of its own: the general kernel's
 // business) counts as EMPTY — one v_max per lane and batch; phase 1 then sees padding only and never forms an address from it
-#ifdef AQC_NO_IRR_VMAX      // measurement builds only (tools/build_ablate.sh): the kernel without that v_max — wrong for irregular records
-__device__ __forceinline__ uint32_t lane_len(uint32_t len_word) { return len_word; }
-#else
 __device__ __forceinline__ uint32_t lane_len(uint32_t len_word) { return (uint32_t)max((int)len_word, 0); }
-#endif
 
 template <int NW, bool PAIRED, bool FUSE = false>
 struct FastWaveLds {
@@ -204,9 +149,7 @@ __device__ __forceinline__ uint32_t comp_acgtn(uint32_t c) {
 }
 __device__ __forceinline__ int base_idx_acgt(uint32_t c) { return (int)((0x3120u >> (((c >> 1) & 3u) * 4u)) & 0xfu); }   // A T C G -> 0 1 2 3
 
-// exchange a value with the partner lane (lane ^ 1): DPP quad_perm [1,0,3,2]
-__device__ __forceinline__ int xchg(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true); }
-// the partner lane's predicate (all lanes must call it).  One DPP move: the ballot form needs the lane's 64-bit bit mask,
+// the partner lane's predicate (xchg: aqc_prim.hpp) (all lanes must call it).  One DPP move: the ballot form needs the lane's 64-bit bit mask,
 // a loop invariant the compiler keeps in two registers for the whole kernel
 __device__ __forceinline__ bool xchg_pred(bool b) { return xchg(b ? 1 : 0) != 0; }
 // number of set bits of m below this lane
@@ -227,6 +170,15 @@ __device__ __forceinline__ uint32_t mm_word(uint32_t mlo0, uint32_t mlo1, uint32
     return mm & base_mask(nb);
 }
 
+// ---- measurement switches ---------------------------------------------------------------------------------------------------------------
+// These are ALL the compile-time measurement switches the device code has; each is an instrument laid over the one product code path,
+// none selects a second implementation (tools/build_ablate.sh, tools/gpu_ablate.sh build with them):
+//   AQC_PROFILE     s_memtime stamps per phase: PROF* here (the verdict kernel), KPROF* in aqc_qcstat.hpp (the k-mer kernel)
+//   AQC_ABL         bits 1 - 32, the verdict kernel with one stage switched off each (results are WRONG, only instruction counts /
+//                   times mean anything)
+//   AQC_FUSE_ABL    the same for the fused variant's placement and copy
+// The questions the former A/B switches asked (window grids of the copies, cooperative verification, flat against global loads, ...)
+// are answered in DESIGN.md 3.5 / 3.6 and profiles/r06_*; their losing branches are gone from the tree.
 #ifdef AQC_PROFILE
 #define PROF_DEFER(k, cond) do { if (cond) atomicAdd(&R->st.counters[AQC_N_COUNTERS + 10 + (k)], 1ull); } while (0)
 #define PROF_DECL unsigned long long prof_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long prof_last = __builtin_amdgcn_s_memtime(); const unsigned long long prof_t0 = prof_last;
@@ -239,22 +191,11 @@ __device__ __forceinline__ uint32_t mm_word(uint32_t mlo0, uint32_t mlo1, uint32
 #define PROF_FLUSH
 #endif
 
-#ifndef AQC_MIN_WAVES
-#define AQC_MIN_WAVES 4
-#endif
-#ifndef AQC_PRIO2
-#define AQC_PRIO2 2
-#endif
-#ifndef AQC_PRIO1
-#define AQC_PRIO1 0
-#endif
-#ifndef AQC_COOP_VERIFY
-#define AQC_COOP_VERIFY 1      // 1: the survivors' diagonals are verified by the whole wave, a lane per (survivor, 16-base word); 0: every lane its own
-#endif
 #ifndef AQC_ABL
-#define AQC_ABL 0      // ablation builds only (tools/gpu_ablate.sh; results are WRONG, only instruction counts / times mean anything):
-                       // 1 no alphabet validation, 2 no length masks, 4 no polyX screen, 8 no diagonal scan, 16 no correction walk,
-                       // 32 no N count, 64 no phase 1 packing (loads only), 128 every 16-byte load moved down to the 16-byte grid
+#define AQC_ABL 0      // 1 no alphabet validation, 2 no length masks, 4 no polyX screen, 8 no diagonal scan, 16 no correction walk, 32 no N count
+#endif
+#ifndef AQC_FUSE_ABL
+#define AQC_FUSE_ABL 0          // 1 no copy, 2 no stores, 4 no loads, 8 no look-back
 #endif
 
 // what the barcode stage needs of aqc_config, decoded once per kernel (uniform): verify as 2-bit codes
@@ -298,17 +239,12 @@ struct FastArgs {
     FuseArgs fz;
 };
 typedef const FastArgs __attribute__((address_space(4))) * FastArgsRare;
-#ifndef AQC_FUSE_UNROLL
-#define AQC_FUSE_UNROLL 12
-#endif
-#ifndef AQC_FUSE_ABL
-#define AQC_FUSE_ABL 0          // measurement builds only: 1 no copy, 2 no stores, 4 no loads, 8 no look-back
-#endif
 
 // (one workgroup of WPBT waves per CU — its LDS rows allow no second one — is WPBT / 4 waves per SIMD: that is the occupancy the
 //  register budget is sized for: 128 VGPRs for the 16-wave 2 x 150 variant, 168 for the 12-wave ones)
+constexpr int FAST_MIN_WAVES = 4;
 template <int NW, bool PAIRED, int WPBT, bool BARCODE, bool FUSE = false>
-__global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < AQC_MIN_WAVES ? (WPBT + 3) / 4 : AQC_MIN_WAVES) void fast_filter_overlap_kernel(FastArgs K) {
+__global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < FAST_MIN_WAVES ? (WPBT + 3) / 4 : FAST_MIN_WAVES) void fast_filter_overlap_kernel(FastArgs K) {
     static_assert(!FUSE || (PAIRED && !BARCODE), "the fused variant is the plain paired one");
     const DevBatch& fb = K.fb;
     const aqc_config& cfg = K.cfg;
@@ -378,7 +314,7 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < AQC_MIN_WAVES ? (WPBT
     int since_flush = 0;
     auto flush_totals = [&]() {
         unsigned long long* C = acc.counters;
-        auto fld = [&](uint32_t r, int sh, uint32_t mask) -> unsigned long long { return (unsigned long long)(uint32_t)wave_sum_u((int)((r >> sh) & mask)); };
+        auto fld = [&](uint32_t r, int sh, uint32_t mask) -> unsigned long long { return (unsigned long long)(uint32_t)wave_sum_dpp((int)((r >> sh) & mask)); };
         const unsigned long long t_n = fld(R0, 0, 0xff), t_good = fld(R0, 8, 0xff), t_ar = fld(R0, 16, 0xff), t_ov = fld(R0, 24, 0xff);
         const unsigned long long t_tb = fld(R1, 0, 0xffff), t_gb = fld(R1, 16, 0xffff), t_ab = fld(R2, 0, 0xffff), t_ol = fld(R2, 16, 0xffff);
         const unsigned long long t_od = fld(R3, 0, 0xff), t_rc = fld(R3, 8, 0xff), t_bc = fld(R3, 16, 0xff), t_mk = fld(R3, 24, 0xff), t_sk = fld(R4, 0, 0xff);
@@ -510,10 +446,10 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < AQC_MIN_WAVES ? (WPBT
                 continue;
             }
             const bool in = lane <= fp;
-            bg1 += (uint32_t)wave_sum_u(in ? (int)((sa >> 31) & 0x7fffffffull) : 0);
-            bg2 += (uint32_t)wave_sum_u(in ? (int)(sa & 0x7fffffffull) : 0);
-            bb1 += (uint32_t)wave_sum_u(in ? (int)((sb >> 31) & 0x7fffffffull) : 0);
-            bb2 += (uint32_t)wave_sum_u(in ? (int)(sb & 0x7fffffffull) : 0);
+            bg1 += (uint32_t)wave_sum_dpp(in ? (int)((sa >> 31) & 0x7fffffffull) : 0);
+            bg2 += (uint32_t)wave_sum_dpp(in ? (int)(sa & 0x7fffffffull) : 0);
+            bb1 += (uint32_t)wave_sum_dpp(in ? (int)((sb >> 31) & 0x7fffffffull) : 0);
+            bb2 += (uint32_t)wave_sum_dpp(in ? (int)(sb & 0x7fffffffull) : 0);
             if (pfx) break;
             j -= WAVE;
         }
@@ -561,12 +497,12 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < AQC_MIN_WAVES ? (WPBT
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     uint8_t* const d = ((xd[u] >> 31) ? o2 : o1) + (xd[u] & FUSE_POS);
-                    if (AQC_FUSE_ABL & 2) { if (xd[u] != 0xffffffffu && xv[u].x == 0x12345678u && xv[u].w == 0x9abcdef0u) store16f(d, xv[u]); }
-                    else if (xd[u] != 0xffffffffu) store16f(d, xv[u]);
+                    if (AQC_FUSE_ABL & 2) { if (xd[u] != 0xffffffffu && xv[u].x == 0x12345678u && xv[u].w == 0x9abcdef0u) store16u(d, xv[u]); }
+                    else if (xd[u] != 0xffffffffu) store16u(d, xv[u]);
                 }
             }
         };
-        if (P.mx <= 384) copy_pass(std::integral_constant<int, 24>{}, std::integral_constant<int, AQC_FUSE_UNROLL>{});
+        if (P.mx <= 384) copy_pass(std::integral_constant<int, 24>{}, std::integral_constant<int, 12>{});
         else copy_pass(std::integral_constant<int, 64>{}, std::integral_constant<int, 16>{});
         __builtin_amdgcn_wave_barrier();
     };
@@ -585,7 +521,7 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < AQC_MIN_WAVES ? (WPBT
         FastArgsRare Rb = R;
         asm volatile("" : "+s"(Rb));
         const int o_do_trim = do_trim, o_run_req = run_req, o_r2b = r2b, o_thr4 = thr4, o_poly_word = poly_word;
-        __builtin_amdgcn_s_setprio(AQC_PRIO1);
+        __builtin_amdgcn_s_setprio(0);
         const uint32_t base = cur * PPW;
         // exactly ONE batch of lookahead (its descriptors travel while this batch is processed): a slow wave never sits
         // on more than one batch the faster waves could have taken
@@ -687,7 +623,7 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < AQC_MIN_WAVES ? (WPBT
             // Read 2 is cut into chunks from its END: chunk c holds the bases [L2 - 16 (c + 1), L2 - 16 c), so that reversed
             // (and complemented) it IS word c of reverse_r2 — the stream starts at bit 0 of word 0 whatever the length,
             // and an untrimmed pair needs no alignment pass in phase 2.  (Unaligned 16-byte loads were taken to cost the same as
-            // aligned ones — round 6's ablation says they cost this kernel ~9 %, AQC_ABL 128, profiles/r06_copy_window_grid.txt, not acted
+            // aligned ones — round 6's ablation says they cost this kernel ~9 %, a build since removed, profiles/r06_copy_window_grid.txt, not acted
             // on here; the chunk of the read's first bases may begin up to 15 bytes before the read, chunks wholly before it
             // are clamped to 16 bytes before: hence the 64-byte bias, every arena has that much readable space in front.)
 #pragma unroll
@@ -751,11 +687,11 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < AQC_MIN_WAVES ? (WPBT
         }
         // phase 2 is pure arithmetic on LDS: run it ahead of the waves that are still waiting for their chunk loads (a wave
         // back in phase 1 drops to priority 0 again) — measured -3 % on the 2 x 150 workload, interleaved A/B on one box
-        __builtin_amdgcn_s_setprio(AQC_PRIO2);
+        __builtin_amdgcn_s_setprio(2);
         PROF(0);
 
         // ------------------------------------------------------------------ phase 2: lane per read
-        // (a mate whose quality line has a length of its own — LEN_IRR in its length word, aqc_kernels.hpp — arrives here with
+        // (a mate whose quality line has a length of its own — LEN_IRR in its length word, aqc_batch.hpp — arrives here with
         //  length 0, see lane_len: the pair goes to the general kernel like an empty read)
         const int L1 = (int)pr[WL::D_L1];
         const int L2 = PAIRED ? (int)pr[WL::D_L2] : 0;
@@ -1148,7 +1084,6 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < AQC_MIN_WAVES ? (WPBT
                 }
                 PROF(4);
                 // exact verification of up to three survivors per lane, in order (util.py:177-184 / 200-207)
-#if AQC_COOP_VERIFY
                 // By the WHOLE wave: a diagonal is QL / 16 words long — two for the ~30-base overlaps of a long insert, ten for an
                 // adapter read-through — and a lane that walks its own diagonal keeps the other 63 waiting for the longest one
                 // (measured: scan + verification 36 of the kernel's 78 vector instructions per pair, the scan itself 16).  So the
@@ -1214,23 +1149,6 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < AQC_MIN_WAVES ? (WPBT
                         __builtin_amdgcn_wave_barrier();
                     }
                 }
-#else
-#pragma unroll
-                for (int v = 0; v < 3; ++v) {
-                    const int c = v == 0 ? s0 : v == 1 ? s1 : s2;
-                    const bool check = live && !found && c != NONE_CAND;
-                    if (!__ballot(check)) break;
-                    const int QL = min(len_own - c, len_par);
-                    if (check) {
-                        const unsigned long long dm = diag_mismatches(c, QL);
-                        const int tot = (int)((dm >> 27) & 0x1ffu), c50 = (int)(dm >> 36);
-                        if (tot < 3 || (c50 < 3 && QL >= 52)) {
-                            found = true; f_off = c; f_len = QL; f_tot = tot;
-                            f_p0 = (int)(dm & 0x1ffu); f_p1 = (int)((dm >> 9) & 0x1ffu); f_p2 = (int)((dm >> 18) & 0x1ffu);
-                        }
-                    }
-                }
-#endif
                 PROF(5);
                 // a lane whose three survivors all failed and that may have more continues after the third one
                 const bool more = live && !found && s2 != NONE_CAND;
@@ -1294,7 +1212,6 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < AQC_MIN_WAVES ? (WPBT
             }
             const int w_n = min(dist, w_tot);                 // mismatches the walk handles
             walker = walk_pair && i_found_it && !(AQC_ABL & 16);
-#if AQC_COOP_VERIFY
             {
                 // the columns of the walker's first w_n mismatches: only the words the verification flagged are looked at (a pair
                 // walked along a diagonal of its own got its columns from diag_mismatches above)
@@ -1322,7 +1239,6 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < AQC_MIN_WAVES ? (WPBT
                     }
                 }
             }
-#endif
             if (__ballot(walker)) {
                 // Straight-line and in the streams' 2-bit codes (A 0, C 1, T 2, G 3; complement = code ^ 2): lanes that do not
                 // walk run along with column 0 and switch their results off.

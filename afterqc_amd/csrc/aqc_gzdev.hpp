@@ -24,8 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "aqc_kernels.hpp"
-#include "aqc_text.hpp"
+#include "aqc_prim.hpp"
 
 namespace aqc {
 
@@ -272,12 +271,7 @@ struct alignas(16) GzStage {
 
 __device__ __forceinline__ uint32_t gz_block_excl_scan(uint32_t v, uint32_t* lds /* [5] */, uint32_t& total) {
     const int lane = lane_id(), wave = threadIdx.x / WAVE;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)inc, d);
-        if (lane >= d) inc += o;
-    }
+    const uint32_t inc = wave_incl_sum_shfl(v, lane);
     __syncthreads();
     if (lane == WAVE - 1) lds[wave] = inc;
     __syncthreads();
@@ -295,7 +289,7 @@ __device__ __forceinline__ uint32_t gz_block_excl_scan(uint32_t v, uint32_t* lds
 // returns this thread's segment [a, b), the line its first byte is in, and whether the line table is usable
 __device__ __forceinline__ void gz_stage_member(GzStage& S, const uint8_t* src, int n, int& a, int& b, int& line, bool& use_lines) {
     for (int i = threadIdx.x * 16; i < n; i += GZ_THREADS * 16) {
-        const uint4 v = load16u_t(src + i);        // (the formatted streams are followed by 64 readable bytes)
+        const uint4 v = load16u(src + i);        // (the formatted streams are followed by 64 readable bytes)
         *reinterpret_cast<uint4*>(S.text + i) = v;
     }
     const int pad = GZ_TEXT - n;
@@ -468,7 +462,7 @@ __global__ __launch_bounds__(GZ_THREADS) void gz_pack_kernel(GzJob J) {
     uint8_t* dst = J.packed[q] + J.offsets[member];
     const int n = (int)J.sizes[member];
     for (int i = threadIdx.x * 16; i < n; i += GZ_THREADS * 16) {
-        if (i + 16 <= n) store16u(dst + i, load16u_t(src + i));
+        if (i + 16 <= n) store16u(dst + i, load16u(src + i));
         else for (int k = i; k < n; ++k) dst[k] = src[k];
     }
 }
@@ -543,7 +537,7 @@ __global__ __launch_bounds__(WAVE) void gz_encode_wave_kernel(GzJob J) {
     for (int i = lane; i < GZW_RING; i += WAVE) S.ring[i] = 0;
     {
         const uint8_t* src = J.text[q] + off;
-        for (int i = lane * 16; i < n; i += WAVE * 16) *reinterpret_cast<uint4*>(S.text + i) = load16u_t(src + i);      // (64 readable bytes follow a stream)
+        for (int i = lane * 16; i < n; i += WAVE * 16) *reinterpret_cast<uint4*>(S.text + i) = load16u(src + i);      // (64 readable bytes follow a stream)
         // what lies behind the member's end never matches anything
         for (int i = n + lane; i < ((n + 15) & ~15) + 64 && i < GZW_TEXT + 64; i += WAVE) S.text[i] = 0;
     }
@@ -654,12 +648,7 @@ __global__ __launch_bounds__(WAVE) void gz_encode_wave_kernel(GzJob J) {
                     bits |= (unsigned long long)(uint32_t)(dist - gz_dist_base(dsym)) << nb; nb += (uint32_t)xd;
                 }
             }
-            uint32_t inc = nb;
-#pragma unroll
-            for (int dlt = 1; dlt < WAVE; dlt <<= 1) {
-                const uint32_t o = (uint32_t)__shfl_up((int)inc, dlt);
-                if (lane >= dlt) inc += o;
-            }
+            const uint32_t inc = wave_incl_sum_shfl(nb, lane);
             const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
             if (tok) {
                 const uint32_t at = bitpos + inc - nb;

@@ -15,8 +15,8 @@
 #include <stdint.h>
 
 #include "afterqc_hip.h"
-#include "aqc_kernels.hpp"
-#include "aqc_fast.hpp"      // the DPP wave sums / scans
+#include "aqc_prim.hpp"
+#include "aqc_batch.hpp"
 
 namespace aqc {
 
@@ -25,31 +25,6 @@ constexpr int TXT_BYTES_PER_THREAD = 64;
 constexpr int TXT_TILE = TXT_BLOCK * TXT_BYTES_PER_THREAD;    // 16 KiB of text per workgroup
 constexpr int SCAN_ITEMS = 16;
 constexpr int SCAN_TILE = TXT_BLOCK * SCAN_ITEMS;             // 4096 values per workgroup
-
-// exclusive prefix of one value per thread over a 256-thread workgroup; `total` = sum over the workgroup
-__device__ __forceinline__ unsigned long long block_excl_scan(unsigned long long v, unsigned long long* lds /* [4] */,
-                                                              unsigned long long& total) {
-    const int lane = lane_id(), wave = threadIdx.x / WAVE;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const unsigned long long o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();                       // lds may still be read by the previous call
-    if (lane == WAVE - 1) lds[wave] = inc;
-    __syncthreads();
-    unsigned long long base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < TXT_BLOCK / WAVE; ++w) {
-        if (w >= (int)(blockDim.x / WAVE)) break;            // (workgroups of 64 .. 256 threads)
-        const unsigned long long t = lds[w];
-        if (w < wave) base += t;
-        total += t;
-    }
-    return base + inc - v;
-}
 
 // ---- generic three-pass exclusive scan of u32 values produced by a functor -----------------------------------
 template <class F>
@@ -129,11 +104,8 @@ __device__ __forceinline__ unsigned long long newline_mask64(const uint8_t* p, u
 // newline count (flag A), adds up its predecessors' counts until it meets one that already knows its inclusive prefix
 // (flag P), publishes its own prefix and emits.  The text is read once; the old count / scan / emit trio read it twice
 // and needed three launches per file.
-#ifndef AQC_IDX_SUB
-#define AQC_IDX_SUB 4
-#endif
 constexpr int IDX_K = 8;                              // 16-byte pieces a lane loads at a time (one sub-tile)
-constexpr int IDX_SUB = AQC_IDX_SUB;                  // sub-tiles per tile
+constexpr int IDX_SUB = 4;                            // sub-tiles per tile
 constexpr int IDX_P = IDX_K * IDX_SUB;                // pieces per lane per tile
 constexpr int IDX_TILE = TXT_BLOCK * 16 * IDX_P;      // 128 KiB: one ticket and one look-back per tile (same-address atomics
                                                       // serialise in L2 at ~8 ns each, so 32 KiB tiles capped the kernel near 4 TB/s)
@@ -238,7 +210,7 @@ __global__ __launch_bounds__(TXT_BLOCK) void text_index_kernel(IndexFile f0, Ind
 #pragma unroll
         for (int k = 0; k < IDX_K; ++k) v[k] = nx[k];
     }
-    const uint32_t wtot = (uint32_t)wave_sum_u((int)mine);
+    const uint32_t wtot = (uint32_t)wave_sum_dpp((int)mine);
     if (lane == 0) s_wave_tot[wave] = wtot;
     __syncthreads();
     unsigned long long total = 0, wave_off = 0;
@@ -392,7 +364,7 @@ __global__ __launch_bounds__(TXT_BLOCK) void frame_records_kernel(const uint8_t*
         }
         out.name_off[r] = s[0]; out.name_len[r] = l[0];
         // a quality line of another length than its sequence line: the reference does not mind (fastq.py:37-49 hands the lines
-        // over as they are) — the record is marked, every later stage keeps a view per string (aqc_kernels.hpp, LEN_IRR)
+        // over as they are) — the record is marked, every later stage keeps a view per string (aqc_batch.hpp, LEN_IRR)
         out.seq_off[r] = s[1];  out.seq_len[r] = l[1] | (l[1] != l[3] ? LEN_IRR : 0u);
         out.plus_off[r] = s[2]; out.plus_len[r] = l[2] | (l[1] != l[3] ? LEN_IRR : 0u);      // (the mark once more, where the writer's sizing pass reads anyway)
         out.qual_off[r] = s[3]; out.qual_len[r] = min(l[3], QLEN_MASK) | tail_nl | (all_nl ? QLEN_CONTIG : 0u);
@@ -756,14 +728,14 @@ __global__ __launch_bounds__(TXT_BLOCK) void fmt_tile_sums_kernel(FormatView v, 
             uint32_t sz[3] = {0, 0, 0}, ev = 0;
             if (r < n) fmt_sizes(v, r, file, sz, ev);
             // (a record is < 64 KiB, a wave's sum < 4 MiB: int arithmetic; all 64 lanes are here)
-            const int g = wave_sum_u((int)sz[0]), b = wave_sum_u((int)sz[1]);
+            const int g = wave_sum_dpp((int)sz[0]), b = wave_sum_dpp((int)sz[1]);
             if (lane == 0) { part[half][file * 3 + 0] = (uint32_t)g; part[half][file * 3 + 1] = (uint32_t)b; }
             if (v.store_overlap) {
-                const int o = wave_sum_u((int)sz[2]);
+                const int o = wave_sum_dpp((int)sz[2]);
                 if (lane == 0) part[half][file * 3 + 2] = (uint32_t)o;
             }
             if (v.spans) {                                               // streams 6, 7: the files' event counts
-                const int e = wave_sum_u((int)ev);
+                const int e = wave_sum_dpp((int)ev);
                 if (lane == 0) part[half][FMT_EVENT_STREAM + file] = (uint32_t)e;
             }
         }
@@ -808,13 +780,6 @@ __global__ __launch_bounds__(TXT_BLOCK) void fmt_tile_bases_kernel(unsigned long
     if (threadIdx.x == 0) total_out[blockIdx.x] = carry;
 }
 
-__device__ __forceinline__ void store16u(uint8_t* p, uint4 v) { __builtin_memcpy(p, &v, 16); }
-__device__ __forceinline__ uint4 load16u_t(const uint8_t* p) {
-    uint4 v;
-    __builtin_memcpy(&v, p, 16);
-    return v;
-}
-
 // ---- one record of one file, as the writer sees it --------------------------------------------------------------------
 // The output record is a sequence of pieces
 //     '@' FLAG | barcode bases | name tail | \n | bases | \n | strand line | \n | qualities | \n
@@ -822,20 +787,11 @@ __device__ __forceinline__ uint4 load16u_t(const uint8_t* p) {
 // that are neighbours in the text as well are merged while the list is built, so an untrimmed good record is ONE piece
 // (the record's own bytes), a tail-trimmed one three, a renamed (bad) one two more.
 constexpr int FMT_MAXP = 10;
-#ifndef AQC_GEN_ALIGN
-#define AQC_GEN_ALIGN 1       // the general copy kernel's pieces of >= GRID_MIN bytes: windows on the source's grid, one work item more per piece
-#endif
-#ifndef AQC_GEN_SMALL
-#define AQC_GEN_SMALL 1       // the general copy kernel's pieces of < 16 bytes: loaded with the windows, stored straight-line (0: rounds 2 - 5, a branch per size)
-#endif
-#ifndef AQC_GEN_DECODE_LDS
-#define AQC_GEN_DECODE_LDS 1
-#endif
-constexpr uint32_t GRID_MIN = 48;
+constexpr uint32_t GRID_MIN = 48;      // the general copy kernel's pieces of >= GRID_MIN bytes: windows on the source's grid, one work item more per piece
 // work items of a piece of `len` bytes in the general copy kernel: a short piece is one, a long one a 16-byte window per item —
 // on the source's grid (head window + aligned windows, the last one end-aligned) that is one more than len / 16 rounded up
 __host__ __device__ constexpr uint32_t piece_items(uint32_t len) {
-    return len >= 16u ? ((len + 15u) >> 4) + ((AQC_GEN_ALIGN && len >= GRID_MIN) ? 1u : 0u) : (len > 0u ? 1u : 0u);
+    return len >= 16u ? ((len + 15u) >> 4) + (len >= GRID_MIN ? 1u : 0u) : (len > 0u ? 1u : 0u);
 }
 constexpr uint32_t FMT_LIT_BIT = 0x80000000u;
 struct FmtPiece {
@@ -966,16 +922,6 @@ __device__ inline void fmt_build(const FormatView& v, uint64_t r, int file, int 
 struct FormatOut {
     uint8_t* p[6];        // [file * 3 + stream]
 };
-
-template <int N>
-__device__ __forceinline__ void copy_small(uint8_t* d, const uint8_t* s_, int len) {
-    // len in [N, 2N): two overlapping N-byte moves
-    uint8_t a[N], b[N];
-    __builtin_memcpy(a, s_, N);
-    __builtin_memcpy(b, s_ + len - N, N);
-    __builtin_memcpy(d, a, N);
-    __builtin_memcpy(d + len - N, b, N);
-}
 
 // ---- the writer: plan, then copy ------------------------------------------------------------------------------------------
 // fmt_plan_kernel (thread = record, workgroup = tile of FMT_TILE records): the record's offset in its stream (block scans
@@ -1190,14 +1136,8 @@ __global__ __launch_bounds__(FMT_TILE) void fmt_plan_kernel(FormatView v, uint64
     }
 }
 
-#ifndef AQC_FMT_UNROLL
-#define AQC_FMT_UNROLL 4
-#endif
-constexpr int FMT_UNROLL = AQC_FMT_UNROLL;
+constexpr int FMT_UNROLL = 4;
 constexpr int COPY_BLOCK = 256;
-#ifndef AQC_COPY_ALIGN
-#define AQC_COPY_ALIGN 2      // window grid of the whole-record copy: 0 none (rounds 2 - 5), 1 the destination's, 2 the source's (copy_whole_tasks)
-#endif
 
 // Records that are ONE piece (untrimmed, unedited, not renamed: the bulk of a -f 0 -t 0 run): 32 lanes, window
 // min(16 * lane, len - 16), load, store — as lean as a copy gets (tools/ubench/copy_rate.hip: this shape moves 6.9 GB in
@@ -1217,24 +1157,22 @@ __device__ __forceinline__ void copy_whole_tasks(const FormatView& v, const uint
         const uint8_t* const s0 = v.f[file].text + pa[u].z;
         int nw = (len + 15) >> 4;
         int off = 16 * lane32;
-#if AQC_COPY_ALIGN
-        // round 6: the windows stand on the 16-byte grid of the SOURCE (AQC_COPY_ALIGN 2; 1: of the destination, measured slower than no
+        // round 6: the windows stand on the 16-byte grid of the SOURCE (on the destination's they measured slower than with no
         // grid at all — profiles/r06_copy_window_grid.txt): lane 0 takes the record's first 16 bytes wherever they stand, lane k >= 1 the
         // k-th aligned window behind them, the last window end-aligned as before.  A wave's load instruction then touches every 64-byte
         // line once (off the grid each quad of lanes straddles two).  A record of > 496 bytes off the grid would take 33 windows: it
         // keeps the plain ones
         {
-            const int a = (16 - (int)((AQC_COPY_ALIGN == 1 ? (uintptr_t)d0 : (uintptr_t)s0) & 15u)) & 15;
+            const int a = (16 - (int)((uintptr_t)s0 & 15u)) & 15;
             const int nwa = 1 + ((len - a + 15) >> 4);
             const bool grid = a != 0 && nwa <= 32;
             nw = grid ? nwa : nw;
             off = grid && lane32 ? a + 16 * (lane32 - 1) : off;
         }
-#endif
         on[u] = plan_is_whole(pa[u]) && lane32 < nw;
         off = min(off, len - 16);
         dptr[u] = d0 + off;
-        if (on[u]) val[u] = load16u_t(s0 + off);
+        if (on[u]) val[u] = load16u(s0 + off);
     }
     // the correction walk's edits: byte patches applied in registers (windows that overlap carry the same patch)
     // (a wave-level test per record in flight and per patch: 8 % of a 2 x 150 run's records carry one or two, and half the rounds of a wave
@@ -1271,7 +1209,7 @@ __global__ __launch_bounds__(COPY_BLOCK) void fmt_copy_whole_kernel(FormatView v
                                                                    const uint4* __restrict__ plan_patch, FormatOut outs) {
     const int nfiles = v.paired ? 2 : 1;
     const int lane32 = threadIdx.x & 31;
-    // (grid-strided: the host launches one workgroup per 32 records, or — AQC_COPY_PERSIST builds — a fixed grid that loops)
+    // (grid-strided: the host launches one workgroup per 32 records)
     const uint64_t n_hw = ((uint64_t)gridDim.x * COPY_BLOCK) >> 5;
     for (uint64_t hw = ((uint64_t)blockIdx.x * COPY_BLOCK + threadIdx.x) >> 5; hw * FMT_UNROLL < n_tasks; hw += n_hw) {
         uint4 pa[FMT_UNROLL];
@@ -1320,10 +1258,7 @@ __global__ __launch_bounds__(COPY_BLOCK) void fmt_copy_whole_list_kernel(FormatV
 // item — a 16-byte window of a long piece (16-byte load + 16-byte store at any alignment, the piece's last window
 // end-aligned) or a whole short piece.  Stages (list, plans, decode, loads, patches, stores) run over both plans so that
 // each stage's memory operations travel together.
-#ifndef AQC_GEN_U
-#define AQC_GEN_U 2
-#endif
-constexpr int GEN_U = AQC_GEN_U;                           // plans per half-wave per round
+constexpr int GEN_U = 2;                                   // plans per half-wave per round
 constexpr int GEN_ROUND = (COPY_BLOCK / 32) * GEN_U;       // plans per workgroup per round
 static_assert(GEN_ROUND * PLAN_Q <= COPY_BLOCK, "one 16-byte word per thread stages a round's plans");
 
@@ -1371,7 +1306,6 @@ __global__ __launch_bounds__(COPY_BLOCK) void fmt_copy_kernel(FormatView v, cons
             const uint32_t idx = (uint32_t)(hwi * GEN_U + u);
             const bool live = idx < cnt;
             const uint4* P = s_plan + (live ? idx : 0u) * PLAN_Q;
-#if AQC_GEN_DECODE_LDS
             // (round 6) the fields of my piece are READ from the plan in LDS at an address worked out from k — a 32-bit source, two 16-bit
             // reads — and k itself is a packed byte compare: the eight-way selects and seven compares per window they replace were a
             // third of this kernel's vector instructions
@@ -1399,34 +1333,8 @@ __global__ __launch_bounds__(COPY_BLOCK) void fmt_copy_kernel(FormatView v, cons
                 const int dst_rd = (int)*reinterpret_cast<const uint16_t*>(pb + 62 + 2 * max(k, 1));                      // output offsets of pieces 1..7: q4
                 const int dst_off = k == 0 ? 0 : dst_rd;                                                                  // (read, then chosen: no branch around the read)
                 const uint32_t sk = *reinterpret_cast<const uint32_t*>(pb + (k == 0 ? 8 : 12 + 4 * k));                    // sources: q0.z | q1, q2.xyz
-#else
-            const uint4 q0 = P[0], q1 = P[1], q2 = P[2], q3 = P[3], q4 = P[4];
-            const bool ovf = live && (q0.y & PLAN_OVER) != 0;
-            more |= ovf ? 1u << u : 0u;
-            const uint32_t file = nfiles == 2 ? (s_ti[live ? idx : 0u] & 1u) : 0u;
-            const uint32_t fs = file * 3u + (q0.y & 0xffu);
-            const uint32_t items = (live && !ovf) ? q4.w >> 16 : 0u;
-            const unsigned long long cum = ((unsigned long long)q3.w << 32) | q3.z;
-#pragma unroll
-            for (int j = 0; j < GEN_PASSES; ++j) {
-                const int w = u * GEN_PASSES + j;
-                const uint32_t item = (uint32_t)lane32 + 32u * j;
-                const bool on = item < items;
-                // my piece: count the pieces whose cumulative item count I am at or beyond
-                int k = 0;
-#pragma unroll
-                for (int jj = 0; jj < PLAN_MAXP - 1; ++jj) k += item >= (uint32_t)((cum >> (8 * jj)) & 0xffu) ? 1 : 0;
-                k = on ? k : 0;
-                const int first_item = (int)(((cum << 8) >> (8 * k)) & 0xffu);
-                const uint32_t lw = k < 2 ? q0.w : k < 4 ? q2.w : k < 6 ? q3.x : q3.y;                  // lengths, two per word
-                const int lk = (int)((lw >> (16 * (k & 1))) & 0xffffu);
-                const uint32_t ow = k < 1 ? 0u : k < 3 ? q4.x : k < 5 ? q4.y : k < 7 ? q4.z : q4.w;     // output offsets of pieces 1..7
-                const int dst_off = k == 0 ? 0 : (int)((ow >> (16 * ((k - 1) & 1))) & 0xffffu);
-                const uint32_t sk = k == 0 ? q0.z : k == 1 ? q1.x : k == 2 ? q1.y : k == 3 ? q1.z : k == 4 ? q1.w : k == 5 ? q2.x : k == 6 ? q2.y : q2.z;
-#endif
                 // a long piece: my 16-byte window of it, the last one aligned to the piece's end; a short piece: all of it
                 int off = 16 * ((int)item - first_item);
-#if AQC_GEN_ALIGN
                 // (round 6) a piece of >= GRID_MIN bytes has one item more (piece_items): its first window where the piece starts, the
                 // others on the 16-byte grid of the SOURCE, so that a load instruction touches each 64-byte line once
                 {
@@ -1435,7 +1343,6 @@ __global__ __launch_bounds__(COPY_BLOCK) void fmt_copy_kernel(FormatView v, cons
                     const bool grid = lk >= (int)GRID_MIN && !(sk & FMT_LIT_BIT) && off;
                     off += (a - 16) & -(int)grid;                                    // (arithmetic, not a branch around eight instructions)
                 }
-#endif
                 off = lk >= 16 ? min(off, lk - 16) : 0;
                 so[w] = sk + (uint32_t)off;
                 dof[w] = q0.x + (uint32_t)(dst_off + off);
@@ -1454,11 +1361,7 @@ __global__ __launch_bounds__(COPY_BLOCK) void fmt_copy_kernel(FormatView v, cons
 #pragma unroll
         for (int w = 0; w < NWIN; ++w) {
             const uint32_t md = mw[w] & 31u;
-#if AQC_GEN_SMALL
             val[w] = gload_u128(md ? src_of(w) : tp0);       // (a short piece's 16 bytes too: the text is padded, a literal is a 16-byte row)
-#else
-            val[w] = load16u_t(md == 16u ? src_of(w) : tp0);
-#endif
             any_small |= (md - 1u) < 15u ? 1u : 0u;
         }
         // the correction walk's edits: byte patches applied in registers (windows that overlap carry the same patch)
@@ -1503,7 +1406,6 @@ __global__ __launch_bounds__(COPY_BLOCK) void fmt_copy_kernel(FormatView v, cons
 #pragma unroll
         for (int w = 0; w < NWIN; ++w)
             if ((mw[w] & 31u) == 16u) gstore_u128(dst_of(w), val[w]);
-#if AQC_GEN_SMALL
         // pieces of 1..15 bytes — a literal '@', a moved barcode, a stray newline: their bytes came with the windows' loads; 8 + 4 + 2 + 1
         // bytes stored as the length's bits say.  (Rounds 2 - 5 copied them behind the windows, a branch per size class with its own
         // load -> store round trip: two or three memory latencies per round of a barcode run, where every record has two of them.)
@@ -1523,19 +1425,6 @@ __global__ __launch_bounds__(COPY_BLOCK) void fmt_copy_kernel(FormatView v, cons
                 if (sm && (md & 1u)) gstore_u8(d + (md & 14u), (uint8_t)(pick >> ((md & 2u) * 8u)));
             }
         }
-#else
-        if (__ballot(any_small != 0)) {                    // pieces of 1..15 bytes: a literal '@', a moved barcode, a stray newline
-#pragma unroll
-            for (int w = 0; w < NWIN; ++w) {
-                const int md = (int)(mw[w] & 31u);
-                if (md >= 16 || md == 0) continue;
-                if (md >= 8) copy_small<8>(dst_of(w), src_of(w), md);
-                else if (md >= 4) copy_small<4>(dst_of(w), src_of(w), md);
-                else if (md >= 2) copy_small<2>(dst_of(w), src_of(w), md);
-                else dst_of(w)[0] = src_of(w)[0];
-            }
-        }
-#endif
         // ---- overflow records: any number of pieces / work items, piece by piece (records of more than 1 KiB, more than
         //      eight pieces or four patches)
         if (more) {
@@ -1554,7 +1443,7 @@ __global__ __launch_bounds__(COPY_BLOCK) void fmt_copy_kernel(FormatView v, cons
                     if (lk >= 16) {
                         for (int w0 = 16 * lane32; w0 < lk; w0 += 16 * 32) {
                             const int off = min(w0, lk - 16);
-                            store16u(dst + off, load16u_t(src + off));
+                            store16u(dst + off, load16u(src + off));
                         }
                     } else if (lane32 < lk) dst[lane32] = src[lane32];
                 }
@@ -1611,16 +1500,10 @@ __device__ __forceinline__ int own_bytes_patches(const uint4& w0, const uint4& w
 }
 
 constexpr int PC_BLOCK = 2 * FMT_TILE;       // thread = (record of the tile, file)
-#ifndef AQC_PC_UNROLL
-#define AQC_PC_UNROLL 4
-#endif
-constexpr int PC_UNROLL = AQC_PC_UNROLL;     // records in flight per half-wave in the copy phase
+constexpr int PC_UNROLL = 4;                 // records in flight per half-wave in the copy phase
 static_assert(PC_BLOCK == COPY_BLOCK, "the copy phase is fmt_copy_whole_kernel's");
 
-#ifndef AQC_PC_WAVES
-#define AQC_PC_WAVES 1
-#endif
-__global__ __launch_bounds__(PC_BLOCK, AQC_PC_WAVES) void fmt_place_copy_kernel(FormatView v, uint64_t n, uint64_t n_tiles, uint64_t n_super,
+__global__ __launch_bounds__(PC_BLOCK, 1) void fmt_place_copy_kernel(FormatView v, uint64_t n, uint64_t n_tiles, uint64_t n_super,
                                                                    const unsigned long long* __restrict__ tile_base, const unsigned long long* __restrict__ super_base,
                                                                    uint4* __restrict__ plan_gen, uint32_t* __restrict__ gen_list, unsigned int* __restrict__ n_gen,
                                                                    uint64_t gen_cap, FormatOut outs) {
