@@ -386,6 +386,8 @@ def load_library():
     lib.aqc_fetch_text.argtypes = [P, C.c_int, C.c_int, C.c_int, P, C.c_uint64]
     lib.aqc_fetch_streams.argtypes = [P, C.c_int, C.c_int32, C.POINTER(C.c_void_p * 6), C.POINTER(C.c_uint64 * 6)]
     lib.aqc_gunzip_dev.argtypes = [C.c_int, P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint64), P, C.c_int, C.c_uint64, C.c_uint64]
+    lib.aqc_bunzip2_dev.argtypes = [C.c_int, P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint64), P, C.c_int, C.c_uint64]
+    lib.aqc_bunzip2_dev.restype = C.c_int
     lib.aqc_compress.argtypes = [P, C.c_int, C.c_int32, P]
     lib.aqc_fetch_gz.argtypes = [P, C.c_int, C.c_int, C.c_int, P, C.c_uint64]
     lib.aqc_pipe_create.argtypes = [C.POINTER(P), C.c_int32, C.c_int32, C.c_int32, C.POINTER(P)]
@@ -409,6 +411,8 @@ def load_library():
     lib.aqc_source_gz_stats.restype = C.c_int
     lib.aqc_gz_input_stats.argtypes = [C.POINTER(C.c_uint64 * 4)]
     lib.aqc_gz_input_stats.restype = C.c_int
+    lib.aqc_bz2_input_stats.argtypes = [C.POINTER(C.c_uint64 * 4)]
+    lib.aqc_bz2_input_stats.restype = C.c_int
     lib.aqc_gz_deflate_block.argtypes = [P, C.c_uint64, C.c_int32, P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.aqc_gz_deflate_block.restype = C.c_int
     lib.aqc_gz_inflate_raw.argtypes = [P, C.c_uint64, P, C.c_uint64]
@@ -444,11 +448,11 @@ EXPORTED_SYMBOLS = ["aqc_abi_version", "aqc_device_count", "aqc_device_index", "
                     "aqc_qc_stat", "aqc_fetch_results", "aqc_fetch_quality_views", "aqc_error_record", "aqc_sync", "aqc_last_deferred", "aqc_kernel_ms", "aqc_timing_reset",
                     "aqc_timing_mean", "aqc_get_counters",
                     "aqc_get_histograms", "aqc_get_qc", "aqc_get_kmers", "aqc_overlap", "aqc_read_stats",
-                    "aqc_edit_distance", "aqc_frame", "aqc_frame_mixed", "aqc_reframe", "aqc_format", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused", "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms", "aqc_format_plain", "aqc_fetch_text", "aqc_fetch_streams", "aqc_compress", "aqc_fetch_gz", "aqc_gunzip_dev", "aqc_host_alloc",
+                    "aqc_edit_distance", "aqc_frame", "aqc_frame_mixed", "aqc_reframe", "aqc_format", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused", "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms", "aqc_format_plain", "aqc_fetch_text", "aqc_fetch_streams", "aqc_compress", "aqc_fetch_gz", "aqc_gunzip_dev", "aqc_bunzip2_dev", "aqc_host_alloc",
                     "aqc_host_free",
                     "aqc_pipe_create", "aqc_pipe_destroy", "aqc_pipe_run", "aqc_pipe_last_error",
                     "aqc_host_count_newlines", "aqc_bgzf_compress", "aqc_pipe_split",
-                    "aqc_source_open", "aqc_source_open2", "aqc_source_read", "aqc_source_error", "aqc_source_gz_stats", "aqc_gz_input_stats", "aqc_source_close",
+                    "aqc_source_open", "aqc_source_open2", "aqc_source_read", "aqc_source_error", "aqc_source_gz_stats", "aqc_gz_input_stats", "aqc_bz2_input_stats", "aqc_source_close",
                     "aqc_gz_deflate_block", "aqc_gz_inflate_raw", "aqc_gz_crc32",
                     # the reference's own native seam (editdistance/_editdistance.h:16,23), same names and signatures
                     "edit_distance", "seek_overlap"]
@@ -822,6 +826,27 @@ def bgzf_compress(data, level=2):
     if rc != 0:
         raise AqcError(rc, "aqc_bgzf_compress failed")
     return dst[:n.value].tobytes()
+
+
+def bunzip2_dev(data, cap, device=0, group_blocks=0, threads=1):
+    """aqc_bunzip2_dev: the .bz2 file image `data` decoded on GPU `device`, at most `cap` bytes of text -> (text, stats[8]);
+    AqcError for a damaged or truncated file (what bz2.decompress raises ValueError / OSError for)"""
+    lib = load_library()
+    src = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
+    out = np.zeros(int(cap) + 64, dtype=np.uint8)
+    stats = np.zeros(8, dtype=np.uint64)
+    n = C.c_uint64(0)
+    rc = lib.aqc_bunzip2_dev(int(device), src.ctypes.data, len(data), out.ctypes.data, int(cap), C.byref(n), stats.ctypes.data, int(threads), int(group_blocks))
+    if rc != 0:
+        raise AqcError(rc, (lib.aqc_last_error() or b"").decode("utf-8", "replace"))
+    return out[:n.value].tobytes(), stats
+
+
+def bz2_input_stats():
+    """aqc_bz2_input_stats: blocks committed, of them from a GPU, text bytes, of them from a GPU (bzip2 inputs of every pipe run so far)"""
+    out = (C.c_uint64 * 4)()
+    load_library().aqc_bz2_input_stats(C.byref(out))
+    return [int(x) for x in out]
 
 
 def pipe_split(source, chunk_records, gzip_in=False, io_threads=4, cap=1 << 16):

@@ -123,6 +123,9 @@ inline void walk_spans(const aqc_span_event* ev, size_t e0, size_t e1, uint64_t 
 struct PooledOffload { int device; size_t group; bool warm; std::unique_ptr<aqcgz::SectionOffload> dec; };
 std::mutex g_offload_mu;
 std::vector<PooledOffload> g_offload_pool;
+// the same for the device decoders of .bz2 inputs (aqc_bunzip2_offload.hip)
+struct PooledBunzip2 { int device; std::unique_ptr<aqcbz::StreamDecoder> dec; };
+std::vector<PooledBunzip2> g_bz2_pool;
 
 }  // namespace
 
@@ -140,6 +143,9 @@ struct aqc_pipe {
     size_t gz_offload_group[2] = {0, 0};
     bool gz_offload_tried[2] = {false, false};
     bool gz_offload_warm[2] = {false, false};       // the decoder of this file slot has run before: its device buffers and page-locked arenas exist
+    // per input file: the device decoder of its bzip2 blocks (created with the first .bz2 input that is given to the device)
+    std::unique_ptr<aqcbz::StreamDecoder> bz2_dec[2];
+    int bz2_dec_device[2] = {-1, -1};
     // The buffers come last: they are the first thing `delete` frees (aqc_pipe_destroy), ahead of the decoders and the pool.
     // per input file: ring of page-locked chunk buffers
     std::vector<HostBuf> in_buf[2];
@@ -488,7 +494,21 @@ struct Run {
                 stop_all();
                 return nullptr;
             }
-            src.reset(new Bz2Source(io->in_path[f], P->pool.get()));
+            // bzip2 input: a big stream's blocks go to the device of context f % n in groups.  OPT-IN (AQC_BZ2_DEVICE_IN=1) for
+            // streams of more than 8 MiB compressed; AQC_BZ2_DEVICE_MIN=<bytes> moves that limit (below 8 MiB: a test hook).  No
+            // cold limit is set here: the CLI table it has to come from (tools/gpu_bunzip2_dev.py) has not been measured yet —
+            // DESIGN.md §4.4.  AQC_BZ2_DEVICE_IN=0, no context, a smaller stream, a pbzip2-style file of many small streams:
+            // libbz2 alone, as before.
+            size_t bz_min = (size_t)(8u << 20) + 1;
+            if (const char* m = getenv("AQC_BZ2_DEVICE_MIN")) bz_min = (size_t)std::max(0ll, atoll(m));
+            const char* bz_in = getenv("AQC_BZ2_DEVICE_IN");
+            struct stat bst;
+            aqcbz::StreamDecoder* bz_dec = nullptr;
+            if (bz_in && bz_in[0] == '1' && !P->ctx.empty() && stat(io->in_path[f], &bst) == 0 && (size_t)bst.st_size >= bz_min) {
+                take_bunzip2(f);
+                bz_dec = P->bz2_dec[f].get();
+            }
+            src.reset(new Bz2Source(io->in_path[f], P->pool.get(), bz_dec, bz_min));
         } else if (io->gzip_in[f]) {
             // gzip input: the GPUs take groups of sections off the pool's hands (file f -> the device of context f % n)
             const bool device_in = env_on("AQC_GZ_DEVICE_IN");
@@ -535,6 +555,24 @@ struct Run {
         if (!P->gz_offload[f]) P->gz_offload[f].reset(aqcgz::make_device_offload(dev, group));
         P->gz_offload_device[f] = dev;
         P->gz_offload_group[f] = group;
+    }
+
+    // the device bunzip2 decoder of file slot f: the pipe's own from an earlier run, one from the pool earlier pipes left, or a new one
+    void take_bunzip2(int f) {
+        const int dev = aqc_device_index(P->ctx[(size_t)f % P->ctx.size()]);
+        if (P->bz2_dec[f] && (P->bz2_dec_device[f] != dev || P->bz2_dec[f]->gave_up())) P->bz2_dec[f].reset();
+        if (P->bz2_dec[f]) return;
+        {
+            std::lock_guard<std::mutex> g(g_offload_mu);
+            for (size_t i = 0; i < g_bz2_pool.size(); ++i)
+                if (g_bz2_pool[i].device == dev) {
+                    P->bz2_dec[f] = std::move(g_bz2_pool[i].dec);
+                    g_bz2_pool.erase(g_bz2_pool.begin() + (long)i);
+                    break;
+                }
+        }
+        if (!P->bz2_dec[f]) P->bz2_dec[f].reset(aqcbz::make_device_bunzip2(dev, 0));
+        P->bz2_dec_device[f] = dev;
     }
 
     // host memory: zero-copy chunks, counted over a span that grows until it holds K records
@@ -1435,6 +1473,9 @@ void aqc_pipe_destroy(aqc_pipe* p) {
         for (int f = 0; f < 2; ++f)
             if (p->gz_offload[f] && !p->gz_offload[f]->gave_up() && g_offload_pool.size() < 16)
                 g_offload_pool.push_back(PooledOffload{p->gz_offload_device[f], p->gz_offload_group[f], p->gz_offload_warm[f], std::move(p->gz_offload[f])});
+        for (int f = 0; f < 2; ++f)
+            if (p->bz2_dec[f] && !p->bz2_dec[f]->gave_up() && g_bz2_pool.size() < 16)
+                g_bz2_pool.push_back(PooledBunzip2{p->bz2_dec_device[f], std::move(p->bz2_dec[f])});
     }
     delete p;       // (its buffers free themselves, here: HostBuf)
 }
@@ -1495,6 +1536,12 @@ int aqc_source_gz_stats(aqc_source* s, uint64_t out[4]) {
 int aqc_gz_input_stats(uint64_t out[4]) {
     if (!out) return AQC_ERR_ARG;
     for (int i = 0; i < 4; ++i) out[i] = g_gz_in_stats[i].load();
+    return 0;
+}
+
+int aqc_bz2_input_stats(uint64_t out[4]) {
+    if (!out) return AQC_ERR_ARG;
+    for (int i = 0; i < 4; ++i) out[i] = g_bz2_in_stats[i].load();
     return 0;
 }
 

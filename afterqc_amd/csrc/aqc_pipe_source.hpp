@@ -29,6 +29,7 @@
 #include <immintrin.h>
 #endif
 
+#include "aqc_bz2.hpp"
 #include "aqc_gz.hpp"
 #include "aqc_pool.hpp"
 
@@ -184,28 +185,9 @@ struct FileSource : Source {
 // their text in order.  A file that ends inside a stream, or that libbz2 rejects, is an error.  (Every stream is decoded, as
 // python 3's BZ2File does — the path the serial loop takes for .bz2; python 2's reads only the first, qualitycontrol.py:77-78
 // warns about pbzip2 files.)
-struct Bz2Api {
-    struct Stream {
-        char* next_in; unsigned int avail_in, total_in_lo32, total_in_hi32;
-        char* next_out; unsigned int avail_out, total_out_lo32, total_out_hi32;
-        void* state; void* (*bzalloc)(void*, int, int); void (*bzfree)(void*, void*); void* opaque;
-    };
-    int (*init)(Stream*, int, int) = nullptr;
-    int (*step)(Stream*) = nullptr;
-    int (*end)(Stream*) = nullptr;
-    bool ok = false;
-    Bz2Api() {
-        void* h = nullptr;
-        for (const char* name : {"libbz2.so.1.0", "libbz2.so.1", "libbz2.so"})
-            if ((h = dlopen(name, RTLD_NOW | RTLD_GLOBAL))) break;
-        if (!h) return;
-        init = (int (*)(Stream*, int, int))dlsym(h, "BZ2_bzDecompressInit");
-        step = (int (*)(Stream*))dlsym(h, "BZ2_bzDecompress");
-        end = (int (*)(Stream*))dlsym(h, "BZ2_bzDecompressEnd");
-        ok = init && step && end;
-    }
-    static const Bz2Api& get() { static Bz2Api api; return api; }
-};
+using aqcbz::Bz2Api;       // aqc_bz2.hpp: shared with the device driver, which hands blocks back to libbz2
+
+std::atomic<uint64_t> g_bz2_in_stats[4];     // blocks of the streams a device decoder was given / of them decoded on a GPU / text bytes of every bzip2 input / of them from a GPU (process-wide)
 
 struct Bz2Source : Source {
     int fd = -1;
@@ -222,6 +204,11 @@ struct Bz2Source : Source {
     std::deque<std::vector<uint8_t>> q;         // decoded text, in order
     size_t q_bytes = 0, front_off = 0;
     bool done = false;
+    // a big stream's blocks go to this decoder in groups (aqc_bunzip2_offload.hip) when it is at least dev_min bytes compressed
+    aqcbz::StreamDecoder* dec = nullptr;
+    size_t dev_min = 0;
+    aqcbz::StreamStats dev_stats;
+    uint64_t text_bytes = 0;
 
     void fail(const char* msg) {
         {
@@ -234,7 +221,7 @@ struct Bz2Source : Source {
         }
         cv.notify_all();
     }
-    Bz2Source(const char* path, Pool* p) : pool(p) {
+    Bz2Source(const char* path, Pool* p, aqcbz::StreamDecoder* device_decoder = nullptr, size_t device_min = 0) : pool(p), dec(device_decoder), dev_min(device_min) {
         fd = open(path, O_RDONLY);
         if (fd < 0) { fail("cannot open the file"); return; }
         struct stat st;
@@ -257,58 +244,50 @@ struct Bz2Source : Source {
         }
         cv.notify_all();
         if (producer.joinable()) producer.join();
+        g_bz2_in_stats[2] += text_bytes;         // (every bzip2 source; libbz2 does not say how many blocks it decoded, so blocks are counted for device decoders' streams only)
+        if (dec) {
+            g_bz2_in_stats[0] += dev_stats.dev_blocks + dev_stats.host_blocks; g_bz2_in_stats[1] += dev_stats.dev_blocks;
+            g_bz2_in_stats[3] += dev_stats.dev_bytes;
+            if (getenv("AQC_PIPE_DEBUG"))
+                fprintf(stderr, "pipe: bunzip2 — %llu blocks from the device (%.1f MB of text), %llu handed back to libbz2 (%.1f MB)\n", (unsigned long long)dev_stats.dev_blocks,
+                        1e-6 * (double)dev_stats.dev_bytes, (unsigned long long)dev_stats.host_blocks, 1e-6 * (double)dev_stats.host_bytes);
+        }
         if (map) munmap((void*)map, size);
         if (fd >= 0) close(fd);
     }
     bool failed() const override { return bad; }
     const char* why() const override { return err; }
 
-    static bool stream_start(const uint8_t* p) {
-        static const uint8_t blk[6] = {0x31, 0x41, 0x59, 0x26, 0x53, 0x59}, eos[6] = {0x17, 0x72, 0x45, 0x38, 0x50, 0x90};
-        return p[0] == 'B' && p[1] == 'Z' && p[2] == 'h' && p[3] >= '1' && p[3] <= '9' && (memcmp(p + 4, blk, 6) == 0 || memcmp(p + 4, eos, 6) == 0);
-    }
-    // one stream -> text; false: libbz2 rejected it or it ends early.  *garbage: bytes follow the stream's end inside [a, b) that
-    // are not a stream — python's BZ2File reads up to there and ignores the rest of the FILE (its _compression.DecompressReader
-    // treats data that does not decompress as trailing garbage), so the caller stops behind this stream.
+    static bool stream_start(const uint8_t* p) { return aqcbz::is_stream_start(p); }
+    // one stream -> text; false: libbz2 rejected it or it ends early (aqcbz::host_decode: the one libbz2 loop, shared with the
+    // device decoder's hand-back).  *garbage: bytes follow the stream's end inside [a, b) that are not a stream — python's
+    // BZ2File reads up to there and ignores the rest of the FILE (its _compression.DecompressReader treats data that does not
+    // decompress as trailing garbage), so the caller stops behind this stream.
     // sink != nullptr: the text is handed over in pieces of PIECE bytes as they fill (a big stream never sits in memory whole:
     // round-5 advisory — a plain `bzip2` file is ONE stream, and the queue's 1 GiB bound only counted whole streams)
     static constexpr size_t PIECE = 16u << 20;
     bool decode(size_t a, size_t b, std::vector<uint8_t>& out, bool* garbage, const std::function<bool(std::vector<uint8_t>&&)>* sink = nullptr) {
-        const Bz2Api& api = Bz2Api::get();
-        Bz2Api::Stream z{};
-        if (api.init(&z, 0, 0) != 0) return false;
-        out.resize(sink ? PIECE : std::max<size_t>(1u << 20, (b - a) * 5));
-        size_t produced = 0;
-        z.next_in = (char*)(map + a);
-        size_t in_left = b - a;
-        bool ok = false;
-        for (;;) {
-            if (z.avail_in == 0 && in_left) { z.avail_in = (unsigned)std::min<size_t>(in_left, 1u << 30); in_left -= z.avail_in; }
-            if (out.size() - produced < (1u << 16)) {
-                if (sink) {
-                    out.resize(produced);
-                    if (!(*sink)(std::move(out))) break;                       // (stopped)
-                    out = std::vector<uint8_t>(PIECE);
-                    produced = 0;
-                } else out.resize(out.size() + out.size() / 2);
+        out.clear();
+        out.reserve(sink ? PIECE : std::max<size_t>(1u << 20, (b - a) * 5));
+        const aqcbz::Sink put = [&](const uint8_t* p, size_t n) {
+            if (!sink) { out.insert(out.end(), p, p + n); return true; }
+            while (n) {
+                const size_t k = std::min(n, PIECE - out.size());
+                out.insert(out.end(), p, p + k);
+                p += k; n -= k;
+                if (out.size() == PIECE) {
+                    if (!(*sink)(std::move(out))) return false;                       // (stopped)
+                    out = std::vector<uint8_t>();
+                    out.reserve(PIECE);
+                }
             }
-            z.next_out = (char*)out.data() + produced;
-            const size_t room = std::min<size_t>(out.size() - produced, 1u << 30);
-            z.avail_out = (unsigned)room;
-            const int rc = api.step(&z);
-            produced += room - z.avail_out;
-            if (rc == 4) {                                                      // BZ_STREAM_END
-                ok = true;
-                if (garbage) *garbage = z.avail_in != 0 || in_left != 0;
-                break;
-            }
-            if (rc != 0 || (z.avail_in == 0 && in_left == 0 && z.avail_out != 0)) break;   // error, or the stream ends early
-            if (stop) break;
-        }
-        api.end(&z);
-        out.resize(produced);
-        if (ok && sink && produced) ok = (*sink)(std::move(out));
-        return ok;
+            return true;
+        };
+        size_t end = b;
+        if (aqcbz::host_decode(map, a, b, 0, put, &end, nullptr, &stop) != 0) return false;
+        if (garbage) *garbage = end != b;
+        if (sink && !out.empty()) return (*sink)(std::move(out));
+        return true;
     }
     // decoded text into the queue, in order; false: the reader has gone
     bool enqueue(std::vector<uint8_t>&& text) {
@@ -317,6 +296,7 @@ struct Bz2Source : Source {
         cv.wait(lk, [&] { return stop.load() || q_bytes < (1u << 30); });
         if (stop) return false;
         q_bytes += text.size();
+        text_bytes += text.size();
         q.push_back(std::move(text));
         lk.unlock();
         cv.notify_all();
@@ -341,11 +321,26 @@ struct Bz2Source : Source {
             starts.push_back(size);
         }
         // small streams (pbzip2's blocks: <= 900 KB of text each) are decoded whole, a window of them in parallel on the pool; a
-        // big one — the single stream of a plain `bzip2` file — is decoded here, piece by piece, straight into the queue
+        // big one — the single stream of a plain `bzip2` file — is decoded here, piece by piece, straight into the queue, or, when
+        // the source was given a device decoder and the stream is at least dev_min bytes, block by block on the device
         const size_t window = (size_t)std::max(2, pool->size());
         const size_t BIG = 8u << 20;
         bool cut = false;                         // garbage behind a stream: python's reader ends the file there
         for (size_t k = 0; k + 1 < starts.size() && !stop && !bad && !cut;) {
+            if (dec && starts[k + 1] - starts[k] >= dev_min) {
+                // the device decodes the stream's blocks in groups; their text is queued in order, under the same back-pressure
+                const aqcbz::Sink sink = [this](const uint8_t* p, size_t n) {
+                    for (size_t o = 0; o < n; o += PIECE)
+                        if (!enqueue(std::vector<uint8_t>(p + o, p + std::min(n, o + PIECE)))) return false;
+                    return true;
+                };
+                size_t end = starts[k + 1];
+                const int rc = dec->decode(map, starts[k], starts[k + 1], sink, &end, &dev_stats, &stop);
+                if (rc != 0) { if (!stop) fail("corrupt or truncated bzip2 stream"); break; }
+                cut = end != starts[k + 1];
+                ++k;
+                continue;
+            }
             if (starts[k + 1] - starts[k] > BIG) {
                 std::vector<uint8_t> out;
                 bool garbage = false;
@@ -356,7 +351,7 @@ struct Bz2Source : Source {
                 continue;
             }
             size_t n = 0;
-            while (n < window && k + n + 1 < starts.size() && starts[k + n + 1] - starts[k + n] <= BIG) ++n;
+            while (n < window && k + n + 1 < starts.size() && starts[k + n + 1] - starts[k + n] <= BIG && !(dec && starts[k + n + 1] - starts[k + n] >= dev_min)) ++n;
             std::vector<std::vector<uint8_t>> outs(n);
             std::vector<char> good(n, 0), junk(n, 0);
             pool->parallel_for(n, [&](size_t i) { bool g = false; good[i] = decode(starts[k + i], starts[k + i + 1], outs[i], &g) ? 1 : 0; junk[i] = g ? 1 : 0; });

@@ -420,6 +420,18 @@ int aqc_fetch_gz(aqc_ctx* ctx, int slot, int file, int stream, uint8_t* dst, uin
  * scan + compact / decode / chain + gather kernels and in the H2D / D2H copies. */
 int aqc_gunzip_dev(int device, const uint8_t* gz, uint64_t size, uint8_t* out, uint64_t cap, uint64_t* n_out, uint64_t stats[8], int threads,
                    uint64_t section_bytes, uint64_t group_bytes);
+/* bzip2 INPUT decoded on the device (fastq.py:25-26: bz2.BZ2File(name, "r"); csrc/aqc_bunzip2_dev.hpp): the file image at
+ * bz[0, size) into out — every stream of it, as Python 3's BZ2File does; bytes behind a stream's end that are not a stream
+ * end the data there without an error.  The unit of work is the bzip2 BLOCK (a wave each; the blocks found by scanning every
+ * bit position for the two 48-bit magics), in groups of `group_blocks` blocks (0: sized so that the decoder's device buffers
+ * stay within 2.5 GB).  A block counts only if it starts at the bit its predecessor ended on and its CRC matches; the stream's
+ * combined CRC is checked on the host.  What does not chain — damage, a randomised block — goes back to libbz2 (loaded at run
+ * time; required), so a damaged or truncated file is the error libbz2 reports (a negative return).  A hand-back restarts the
+ * stream: libbz2 decodes it from its first byte and the text the device delivered is dropped from its output.
+ * stats: blocks decoded on the device / handed back to the host, bytes the host decoded, microseconds in the scan, entropy, BWT
+ * and expand kernels and in the copies.  `threads` is reserved (the host's share is one libbz2 thread). */
+int aqc_bunzip2_dev(int device, const uint8_t* bz, uint64_t size, uint8_t* out, uint64_t cap, uint64_t* n_out, uint64_t stats[8], int threads,
+                    uint64_t group_blocks);
 /* page-locked host memory for text chunks and fetched streams (hipHostMalloc): full-rate DMA */
 void* aqc_host_alloc(uint64_t bytes);
 void aqc_host_free(void* p);
@@ -456,7 +468,9 @@ typedef struct aqc_pipe_io {
                                       aqc_host_alloc is used in place, zero copy) */
     uint64_t in_mem_bytes[2];
     int32_t gzip_in[2];            /* 1: the file is a gzip stream (fastq.py:23-24); 2: a bzip2 file (fastq.py:25-26; decoded by libbz2, loaded at run
-                                      time, on the pipe's own threads: every stream of the file, streams in parallel) */
+                                      time, on the pipe's own threads: every stream of the file, streams in parallel; with AQC_BZ2_DEVICE_IN=1
+                                      the blocks of a stream of >= AQC_BZ2_DEVICE_MIN bytes, default 8 MiB, are decoded on the device:
+                                      csrc/aqc_bunzip2_dev.hpp) */
     const char* out_path[2][3];    /* per input: good / bad / overlap output file, NULL = that stream is dropped */
     int32_t gzip_out;              /* write .gz (preprocesser.py:318-321) */
     int32_t gzip_level;            /* --compression */
@@ -497,7 +511,8 @@ const char* aqc_pipe_last_error(void);
  * aqc_source_read fills dst with the next `want` decompressed bytes and returns their number (< want only at the end of
  * the stream, -1 on a read / format error: aqc_source_error says which). */
 typedef struct aqc_source aqc_source;
-aqc_source* aqc_source_open(const char* path, int32_t gzip, int32_t io_threads);      /* gzip: 0 plain, 1 gzip, 2 bzip2 */
+aqc_source* aqc_source_open(const char* path, int32_t gzip, int32_t io_threads);      /* gzip: 0 plain, 1 gzip, 2 bzip2 (always libbz2: a source on
+                                                                                          its own has no device decoder, a pipe's may) */
 /* gz_section_bytes: compressed bytes per speculative section (0: chosen from the file size; AQC_GZ_SECTION overrides) */
 aqc_source* aqc_source_open2(const char* path, int32_t gzip, int32_t io_threads, uint64_t gz_section_bytes);
 int64_t aqc_source_read(aqc_source* s, uint8_t* dst, uint64_t want);
@@ -507,6 +522,11 @@ int aqc_source_gz_stats(aqc_source* s, uint64_t out[4]);
 /* gzip inputs of every aqc_pipe_run of the process so far: sections committed, of them decoded on a GPU (aqc_gunzip_dev.hpp),
  * bytes of text, of them from sections decoded on a GPU.  AQC_GZ_DEVICE_IN=0 keeps gzip input on the host pool. */
 int aqc_gz_input_stats(uint64_t out[4]);
+/* bzip2 inputs of every aqc_pipe_run / aqc_source of the process so far: blocks committed and, of them, blocks decoded on a
+ * GPU (aqc_bunzip2_dev.hpp) — counted for the streams a device decoder was given: libbz2 does not say how many blocks it read —
+ * then bytes of text of every bzip2 input and, of them, bytes from blocks decoded on a GPU.  AQC_BZ2_DEVICE_IN=0 (the default)
+ * keeps bzip2 input on libbz2: out[0], out[1] and out[3] stay zero. */
+int aqc_bz2_input_stats(uint64_t out[4]);
 void aqc_source_close(aqc_source* s);
 /* the codec's pieces on their own (host only; the CPU tests pin them against zlib): one raw DEFLATE stream for src[0, n)
  * (dst must hold n + n / 1000 + 400 bytes; level <= 0 stores), its inverse into exactly `cap` bytes (-1: invalid data or a
