@@ -23,7 +23,9 @@
 #include "aqc_qcstat.hpp"
 #include "aqc_seams.hpp"
 #include "aqc_fast.hpp"
-#include "aqc_text.hpp"
+#include "aqc_textin.hpp"
+#include "aqc_fmt.hpp"
+#include "aqc_fmtcopy.hpp"
 #include "aqc_census.hpp"
 #include "aqc_gzdev.hpp"
 #include "aqc_gz.hpp"

@@ -9,7 +9,7 @@
 #include "afterqc_hip.h"
 #include "aqc_prim.hpp"
 #include "aqc_batch.hpp"      // LEN_MASK: the length words of a framed chunk
-#include "aqc_text.hpp"       // the text stage's own: its workgroup size (TXT_BLOCK) and the character classes of framing (is_space, is_digit)
+#include "aqc_textin.hpp"     // the text-in stage's own: its workgroup size (TXT_BLOCK) and the character classes of framing (is_space, is_digit)
 
 namespace aqc {
 

@@ -1,7 +1,7 @@
 // aqc_prim.hpp — what more than one stage of the gfx950 device code uses, one copy of each: the wave size and lane id, loads / stores
 // that name their address space, the 16-byte unaligned load / store, and the wave-wide reductions and scans.  It depends on no other
-// header of the project; every stage header (aqc_batch / aqc_record / aqc_qcstat / aqc_seams / aqc_fast / aqc_text / aqc_census /
-// aqc_gzdev) includes it for these and includes another stage's header only for what is that stage's own.
+// header of the project; every stage header (aqc_batch / aqc_record / aqc_qcstat / aqc_seams / aqc_fast / aqc_textin / aqc_fmt /
+// aqc_fmtcopy / aqc_census / aqc_gzdev) includes it for these and includes another stage's header only for what is that stage's own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -49,14 +49,11 @@ __device__ __forceinline__ uint4 load16u(const uint8_t* p) {
 }
 __device__ __forceinline__ void store16u(uint8_t* p, uint4 v) { __builtin_memcpy(p, &v, 16); }
 
-// ---- wave-wide sum, in two forms ------------------------------------------------------------------------------------------------------
+// ---- wave-wide sum ---------------------------------------------------------------------------------------------------------------------
 // wave_sum_dpp  is right in UNIFORM control flow only (all 64 lanes active) and returns a wave-uniform result: four DPP steps inside
 //               the rows of 16 lanes (lane ^ 1, lane ^ 2, half-row mirror, row mirror), then the four row results through v_readlane
-//               and scalar arithmetic.  This is the one the product kernels call.
-// wave_sum_shfl makes no such demand and may be called under ANY lane mask: __shfl_xor goes through the LDS crossbar, six ds_bpermute
-//               round trips, and keeps its six lane-address registers alive for the whole kernel — which is why no hot kernel uses
-//               it; it is the form for the general path's code, which runs under lane masks.
-// A call site says by the name which one it gets; switching a site from one to the other changes the kernel.
+//               and scalar arithmetic.  Code that runs under a lane mask sums with __shfl_xor at its own site instead: six ds_bpermute
+//               round trips through the LDS crossbar, and six lane-address registers alive for the whole kernel.
 template <int CTRL>
 __device__ __forceinline__ int dpp_move(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false); }
 __device__ __forceinline__ int wave_sum_dpp(int v) {
@@ -65,11 +62,6 @@ __device__ __forceinline__ int wave_sum_dpp(int v) {
     v += dpp_move<0x141>(v);      // row_half_mirror
     v += dpp_move<0x140>(v);      // row_mirror
     return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) + (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
-}
-__device__ __forceinline__ int wave_sum_shfl(int v) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, WAVE);
-    return v;
 }
 // wave-wide max, the DPP form (uniform control flow, wave-uniform result)
 __device__ __forceinline__ int wave_max_i(int v) {
