@@ -1,6 +1,6 @@
-// aqc_batch.hpp — a batch as it sits in HBM and what every stage shares about it: the batch / circle / statistics descriptors, how a
-// device error is raised at a record, the workgroup-private counters and their flush, and the small kernels that bring an uploaded
-// batch into the device form.
+// aqc_batch.hpp — a batch as it sits in HBM and what every stage shares about it: the batch / circle / statistics / k-mer table
+// descriptors, how a device error is raised at a record, and the workgroup-private counters and their flush.  It defines no kernel:
+// every C-API unit includes it (through aqc_ctx.hpp: the context and its slots are made of these descriptors).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -70,26 +70,28 @@ __device__ inline void flush_block_acc(BlockAcc& acc, const DevStats& st, int ti
     }
 }
 
-// an uploaded batch whose quality strings have lengths of their own (aqc_batch::qlen*): mark the mates that differ
-__global__ void mark_irregular_kernel(uint32_t* __restrict__ len, const uint32_t* __restrict__ qlen, uint64_t n) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && qlen[i] != len[i]) len[i] |= LEN_IRR;
-}
-
-// aqc_fetch_quality_views: the slice of the quality string that goes with the final read of every record
-__global__ void quality_views_kernel(DevBatch b, const aqc_result* __restrict__ results, int mate, uint32_t* __restrict__ out, uint64_t n) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t lw = mate == 0 ? b.len1[i] : b.len2[i];
-    if ((lw & LEN_IRR) && b.qlen1) { out[i] = mate == 0 ? b.qview1[i] : b.qview2[i]; return; }
-    const aqc_result r = results[i];
-    out[i] = mate == 0 ? ((uint32_t)r.start1 | ((uint32_t)r.len1 << 16)) : ((uint32_t)r.start2 | ((uint32_t)r.len2 << 16));
-}
-
-// the caller's 64-bit byte offsets (struct aqc_batch) -> the 32-bit device form
-__global__ void narrow_offsets_kernel(const uint64_t* __restrict__ in, uint32_t* __restrict__ out, uint64_t n) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (uint32_t)in[i];
-}
+// the k-mer dictionary of one statRead accumulator (the kernels: aqc_qcstat.hpp), a member of the context
+struct KmerTable {
+    // open-addressing table for k-mers containing anything but A,C,G,T (rare): keyed by the k raw bytes
+    unsigned long long* keys;    // 0 = empty
+    unsigned long long* counts;  // [capacity + 1]: entry `capacity` belongs to the all-NUL k-mer, whose key is 0 (see kmer_slot)
+    unsigned long long* order;   // [capacity + 1] min over 2*t (seen) / 2*t+1 (inserted as reverse complement)
+    uint64_t mask;               // capacity - 1
+    // dense tables for pure A/C/G/T k-mers, 4^k entries.  Index = (bit-1 plane << k) | bit-0 plane of the
+    // per-base code (c >> 1) & 3 (A=0 C=1 T=2 G=3); base j of the k-mer sits at bit j of each plane.
+    // One copy of the dense tables PER XCD (8 on MI355X): a wave updates the copy of the XCD it runs on with
+    // atomics that execute in that XCD's L2 (workgroup scope is enough: every accessor of a copy shares the L2),
+    // instead of device-scope atomics that have to travel to the memory side.  Copies are summed / min-ed when
+    // the dictionary is read back.
+    unsigned int* dense_count;         // [N_XCD][4^k]
+    unsigned long long* dense_first;   // [N_XCD][4^k] smallest scan time t at which the k-mer was seen (~0 = never)
+    // complete[b] != 0: every dense entry of reduce-workgroup b has a first-seen time (written by kmer_reduce_kernel).
+    // Time keys only grow from launch to launch, so once every entry has one no later launch can lower any of them
+    // and kmer_count_kernel stops probing the first-seen table (for random DNA that is after ~10^4 reads).
+    unsigned int* complete;            // [DENSE_ENTRIES / KRED_ENTRIES]
+};
+constexpr int N_XCD = 8;
+constexpr uint32_t DENSE_ENTRIES = 1u << 16;   // 4^8
+constexpr int KRED_ENTRIES = 256;       // dense entries per kmer_reduce_kernel workgroup
 
 }  // namespace aqc

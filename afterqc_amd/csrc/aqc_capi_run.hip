@@ -1,0 +1,527 @@
+// aqc_capi_run.hip — the C API's verdict stage: a batch up to the device (aqc_upload), the verdict kernels (aqc_run), the results
+// back (aqc_fetch_results, aqc_fetch_quality_views, aqc_last_deferred), the three function seams and the libed.so pair; and the
+// .gz output stage (aqc_compress, aqc_fetch_gz).  The context, its slots and the shared helpers: aqc_ctx.hpp.
+//
+// Why .gz out is here and not in a unit of its own: gz_encode_kernel does not compile to the same instructions there.  In a unit
+// without the verdict kernels the compiler leaves the bit writer's flush loop (GzSinkEmit::flush_words) rolled; beside them, as
+// in the single unit this API used to be, it peels it.  Nothing in the source ties the two, so the encoder stays with the
+// verdict kernels until it can be measured on its own (profiles/r11_capi_split.txt).
+//
+// Kernels launched here, and nowhere else (this is the one unit that includes aqc_upload.hpp, aqc_record.hpp, aqc_seams.hpp and
+// aqc_gzdev.hpp):
+//   aqc_upload.hpp   narrow_offsets_kernel, mark_irregular_kernel, quality_views_kernel
+//   aqc_record.hpp   filter_overlap_kernel, filter_overlap_list_kernel
+//   aqc_fast.hpp     fast_filter_overlap_kernel<NW, PAIRED, WPBT, BARCODE, FUSE> (a template: the variants are instantiated here)
+//   aqc_gzdev.hpp    gz_hist_kernel, gz_encode_wave_kernel, gz_encode_kernel, gz_offsets_kernel, gz_pack_kernel
+//   aqc_seams.hpp    overlap_seam_kernel, read_stats_seam_kernel, edit_distance_seam_kernel, edit_distance_any_kernel,
+//                    seek_overlap_kernel
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <mutex>
+#include <vector>
+
+#include "aqc_ctx.hpp"
+#include "aqc_prim.hpp"
+#include "aqc_upload.hpp"
+#include "aqc_record.hpp"
+#include "aqc_seams.hpp"
+#include "aqc_fast.hpp"
+#include "aqc_gzdev.hpp"
+#include "aqc_gz.hpp"
+#include <zlib.h>
+
+using namespace aqc;
+
+constexpr int FUSE_WPBT = 12;      // waves per workgroup of the fused verdict kernel
+template <int NW, bool PAIRED, int WPBT, bool BARCODE, bool FUSE = false>
+static void launch_fast(aqc_ctx* c, Slot* s, const aqc_config& cfg, const DevStats& st, uint64_t accum_limit, const FuseArgs* fz = nullptr) {
+    constexpr uint64_t per_block = (uint64_t)WPBT * FastWaveLds<NW, PAIRED, FUSE>::PPW;
+    uint64_t blocks = (s->n + per_block - 1) / per_block;
+    // persistent grid: as many workgroups as the LDS footprint lets a CU hold; batches are grid-strided
+    const size_t lds = sizeof(FastWaveLds<NW, PAIRED, FUSE>) * WPBT + sizeof(BlockAcc) + 64 + 17 * 16 + (FUSE ? 16 * 8 : 0);
+    uint64_t per_cu = (160 * 1024) / lds;
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    const uint64_t cap = (uint64_t)c->n_cu * per_cu;
+    if (blocks > cap) blocks = cap;
+    // pairs the fast kernel cannot decide exactly (exotic bytes, very short reads, ...) are queued and
+    // finished by the general wave-per-record pipeline right behind it on the same stream
+    (void)hipMemsetAsync(s->n_deferred.p, 0, sizeof(unsigned int), s->stream);
+    FastArgs K;
+    K.fb = s->view; K.cfg = cfg; K.circ = c->circles; K.results = (aqc_result*)s->results.p; K.st = st; K.accum_limit = accum_limit;
+    K.deferred = (uint32_t*)s->deferred.p; K.n_deferred = (unsigned int*)s->n_deferred.p;
+    K.fz = fz ? *fz : FuseArgs{};
+    hipLaunchKernelGGL((fast_filter_overlap_kernel<NW, PAIRED, WPBT, BARCODE, FUSE>), dim3((unsigned)blocks), dim3(WPBT * WAVE), 0, s->stream, K);
+}
+
+// one tier of the lane-per-pair kernel (NW words per read; waves per workgroup for pairs / single reads): paired x barcode
+template <int NW, int WPBT_PAIRED, int WPBT_SINGLE>
+static void launch_fast_tier(aqc_ctx* c, Slot* s, const aqc_config& cfg, const DevStats& st, uint64_t accum_limit) {
+    if (cfg.paired) { if (cfg.barcode) launch_fast<NW, true, WPBT_PAIRED, true>(c, s, cfg, st, accum_limit); else launch_fast<NW, true, WPBT_PAIRED, false>(c, s, cfg, st, accum_limit); }
+    else { if (cfg.barcode) launch_fast<NW, false, WPBT_SINGLE, true>(c, s, cfg, st, accum_limit); else launch_fast<NW, false, WPBT_SINGLE, false>(c, s, cfg, st, accum_limit); }
+}
+
+// (`front` readable bytes before the data as well: read 2 is loaded in 16-byte chunks counted from its END, the chunk
+// with a read's first bases may begin up to 16 bytes before the read)
+static int up(DevBuf& d, const void* src, size_t bytes, hipStream_t st, size_t front = 0) {
+    if (d.reserve(front + bytes + ARENA_SLACK)) return fail(AQC_ERR_HIP, "hipMalloc of %zu bytes failed", bytes);
+    if (bytes == 0) return 0;
+    HIP_TRY(hipMemcpyAsync((uint8_t*)d.p + front, src, bytes, hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// 64-bit host offsets -> 32-bit device offsets (through the slot's staging buffer, in stream order)
+static int up_offsets(Slot& s, DevBuf& d, const uint64_t* src, uint64_t n) {
+    if (d.reserve(sizeof(uint32_t) * (n ? n : 1)) || s.off_stage.reserve(sizeof(uint64_t) * (n ? n : 1)))
+        return fail(AQC_ERR_HIP, "hipMalloc failed");
+    if (n == 0) return 0;
+    HIP_TRY(hipMemcpyAsync(s.off_stage.p, src, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s.stream));
+    hipLaunchKernelGGL(narrow_offsets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream, (const uint64_t*)s.off_stage.p,
+                       (uint32_t*)d.p, n);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int fill_slot(aqc_ctx* c, Slot& s, const aqc_batch* b, bool need_qual, bool need_pair) {
+    const uint64_t n = b->n;
+    if (!b->seq1 || !b->off1 || !b->len1) return fail(AQC_ERR_ARG, "batch: seq1/off1/len1 are required");
+    const bool paired = b->seq2 != nullptr;
+    if (need_pair && !paired) return fail(AQC_ERR_ARG, "batch: this call needs seq2/off2/len2");
+    if (paired && (!b->off2 || !b->len2)) return fail(AQC_ERR_ARG, "batch: off2/len2 missing");
+    if (n >= (1ull << 31)) return fail(AQC_ERR_ARG, "batch: more than 2^31 records (split the batch)");
+    const uint64_t lim = (1ull << 32) - 4096;      // 32-bit byte offsets on the device, chunk loads may run 288 bytes past a read's start
+    if (b->bytes1 >= lim || b->qbytes1 >= lim || b->bytes2 >= lim || b->qbytes2 >= lim) return fail(AQC_ERR_ARG, "batch: an arena must be smaller than 4 GiB (split the batch)");
+    // make sure earlier work on this slot has drained before its buffers are overwritten / regrown
+    HIP_TRY(slot_sync(s));
+    int rc;
+    DevBatch v{};
+    v.n = n;
+    v.first_index = b->first_index;
+    if ((rc = up(s.seq1, b->seq1, b->bytes1, s.stream))) return rc;
+    v.seq1 = (const uint8_t*)s.seq1.p;
+    if (b->qual1 && need_qual) {
+        if (b->qual1 == b->seq1) v.qual1 = v.seq1;
+        else {
+            if ((rc = up(s.qual1, b->qual1, b->qbytes1 ? b->qbytes1 : b->bytes1, s.stream))) return rc;
+            v.qual1 = (const uint8_t*)s.qual1.p;
+        }
+    } else if (need_qual) return fail(AQC_ERR_ARG, "batch: qual1 is required");
+    if ((rc = up_offsets(s, s.off1, b->off1, n))) return rc;
+    v.off1 = (const uint32_t*)s.off1.p;
+    if (b->qoff1) {
+        if ((rc = up_offsets(s, s.qoff1, b->qoff1, n))) return rc;
+        v.qoff1 = (const uint32_t*)s.qoff1.p;
+    }
+    if ((rc = up(s.len1, b->len1, sizeof(uint32_t) * n, s.stream))) return rc;
+    v.len1 = (const uint32_t*)s.len1.p;
+    if (paired) {
+        if ((rc = up(s.seq2, b->seq2, b->bytes2, s.stream, TEXT_FRONT))) return rc;
+        v.seq2 = (const uint8_t*)s.seq2.p + TEXT_FRONT;
+        if (b->qual2 && need_qual) {
+            if (b->qual2 == b->seq2) v.qual2 = v.seq2;
+            else {
+                if ((rc = up(s.qual2, b->qual2, b->qbytes2 ? b->qbytes2 : b->bytes2, s.stream))) return rc;
+                v.qual2 = (const uint8_t*)s.qual2.p;
+            }
+        } else if (need_qual) return fail(AQC_ERR_ARG, "batch: qual2 is required");
+        if ((rc = up_offsets(s, s.off2, b->off2, n))) return rc;
+        v.off2 = (const uint32_t*)s.off2.p;
+        if (b->qoff2) {
+            if ((rc = up_offsets(s, s.qoff2, b->qoff2, n))) return rc;
+            v.qoff2 = (const uint32_t*)s.qoff2.p;
+        }
+        if ((rc = up(s.len2, b->len2, sizeof(uint32_t) * n, s.stream))) return rc;
+        v.len2 = (const uint32_t*)s.len2.p;
+    }
+    if (b->aux_ok && b->aux_lane && b->aux_tile && b->aux_x && b->aux_y) {
+        const void* src[5] = {b->aux_lane, b->aux_tile, b->aux_x, b->aux_y, b->aux_ok};
+        for (int k = 0; k < 5; k++)
+            if ((rc = up(s.aux[k], src[k], (k < 4 ? sizeof(int32_t) : 1) * n, s.stream))) return rc;
+        v.aux_lane = (const int32_t*)s.aux[0].p;
+        v.aux_tile = (const int32_t*)s.aux[1].p;
+        v.aux_x = (const int32_t*)s.aux[2].p;
+        v.aux_y = (const int32_t*)s.aux[3].p;
+        v.aux_ok = (const uint8_t*)s.aux[4].p;
+    }
+    if (s.results.reserve(sizeof(aqc_result) * (n ? n : 1))) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    s.has_irregular = b->qlen1 != nullptr && need_qual;
+    if (b->qlen1 && need_qual) {
+        // quality strings with lengths of their own: the mates that differ are marked in the device copy of their length words
+        if (paired && !b->qlen2) return fail(AQC_ERR_ARG, "batch: qlen1 without qlen2");
+        const uint32_t* ql[2] = {b->qlen1, b->qlen2};
+        DevBuf* lens[2] = {&s.len1, &s.len2};
+        for (int k = 0; k < (paired ? 2 : 1); ++k) {
+            if ((rc = up(s.qlen[k], ql[k], sizeof(uint32_t) * n, s.stream))) return rc;
+            if (s.qview[k].reserve(sizeof(uint32_t) * (n ? n : 1))) return fail(AQC_ERR_HIP, "hipMalloc failed");
+            if (n) hipLaunchKernelGGL(mark_irregular_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream, (uint32_t*)lens[k]->p,
+                                      (const uint32_t*)s.qlen[k].p, n);
+        }
+        HIP_TRY(hipGetLastError());
+        v.qlen1 = (const uint32_t*)s.qlen[0].p; v.qview1 = (uint32_t*)s.qview[0].p;
+        if (paired) { v.qlen2 = (const uint32_t*)s.qlen[1].p; v.qview2 = (uint32_t*)s.qview[1].p; }
+        else { v.qlen2 = v.qlen1; v.qview2 = v.qview1; }
+    }
+    uint32_t mx = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (b->len1[i] > mx) mx = b->len1[i];
+        if (paired && b->len2[i] > mx) mx = b->len2[i];
+    }
+    s.raw_max_len = mx;
+    s.view = v;
+    s.n = n;
+    s.paired = paired;
+    s.ran = false;
+    return 0;
+}
+
+extern "C" {
+
+// ---- upload and run ----------------------------------------------------------------------------------------------
+int aqc_upload(aqc_ctx* c, int slot, const aqc_batch* b) {
+    GET_SLOT(s);
+    int rc;
+    if (!b) return fail(AQC_ERR_ARG, "null batch");
+    if ((rc = fill_slot(c, *s, b, true, false))) return rc;
+    s->framed = s->formatted = false;
+    s->max_len = s->raw_max_len;
+    return 0;
+}
+
+static int grid_for(const aqc_ctx* c, uint64_t n) {
+    // persistent grid: enough workgroups to fill every CU several times over, records grid-strided
+    uint64_t blocks = (n + WPB - 1) / WPB;
+    uint64_t cap = (uint64_t)c->n_cu * 8;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    return (int)blocks;
+}
+
+int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
+    GET_SLOT(s);
+    if (!c->has_cfg) return fail(AQC_ERR_STATE, "aqc_run before aqc_set_config");
+    if (c->cfg.paired && !s->paired) return fail(AQC_ERR_STATE, "config says paired but the slot holds single-end records");
+    if (c->cfg.debubble && c->circles.n > 0 && !s->view.aux_ok) return fail(AQC_ERR_ARG, "debubble needs the aux_* arrays");
+    s->fused = false;
+    if (s->n == 0) { s->ran = true; return 0; }
+    aqc_config cfg = c->cfg;
+    if (!cfg.paired) cfg.no_overlap = 1;
+    DevStats st{c->counters, c->ovl_hist, c->dist_hist, s->status, err_key_of(*s)};
+    s->err_record = UINT64_MAX;
+    if (s->qc.pending()) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_qc, 0));      // (statRead of the previous run still reads the results)
+    HIP_TRY(hipEventRecord(launch_event(*s, AQC_K_FILTER_OVERLAP, 0), s->stream));
+    // lane-per-pair kernel whenever its preconditions hold; the general wave-per-record kernel otherwise
+    const int thr = cfg.qualified_quality_phred + 33;
+    // barcodes on that kernel: detectBarcode's three windows must lie in the first 32 bases and the verify sequence must
+    // be plain A/C/G/T (2-bit codes); anything else takes the general kernel
+    bool barcode_ok = true;
+    if (cfg.barcode) {
+        barcode_ok = cfg.barcode_verify_len >= 1 && cfg.barcode_length + 1 + cfg.barcode_verify_len <= 31;
+        for (int j = 0; j < cfg.barcode_verify_len && barcode_ok; ++j) {
+            const uint8_t ch = cfg.barcode_verify[j];
+            barcode_ok = ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T';
+        }
+    }
+    const bool fast_ok = !c->force_generic && barcode_ok && thr >= 0 && thr <= 127 && s->max_len <= 288 && s->max_len > 0;
+    s->used_fast = fast_ok;
+    if (!fast_ok) {
+        hipLaunchKernelGGL(filter_overlap_kernel, dim3(grid_for(c, s->n)), dim3(BLOCK), 0, s->stream, s->view, cfg, c->circles,
+                           (aqc_result*)s->results.p, st, accum_limit);
+    } else {
+        if (s->deferred.reserve(sizeof(uint32_t) * (s->n + 1)) || s->n_deferred.reserve(sizeof(unsigned int)))
+            return fail(AQC_ERR_HIP, "hipMalloc failed");
+        // AQC_FUSED=1: pairs of device-framed text whose records are plain four-line text are placed in their output
+        // streams by the verdict kernel itself, which also copies the good records that go out as their own bytes
+        const bool fuse_ok = c->fuse_opt && s->framed && cfg.paired && !cfg.barcode && s->max_len <= 160 && !s->has_irregular && s->consumed[0] + 16 * s->n < (1ull << 31) && s->consumed[1] + 16 * s->n < (1ull << 31);      // (31-bit stream offsets; a bad record grows by its flag text)
+        if (fuse_ok) {
+            constexpr uint64_t PPW = FastWaveLds<10, true, true>::PPW;
+            const uint64_t n_batches = (s->n + PPW - 1) / PPW;
+            if (s->fz_state.reserve(16 * n_batches) || s->fz_rec[0].reserve(4 * s->n) || s->fz_rec[1].reserve(4 * s->n) || s->fz_misc.reserve(64) ||
+                s->f_out[0].reserve(s->consumed[0] + 64) || s->f_out[3].reserve(s->consumed[1] + 64))
+                return fail(AQC_ERR_HIP, "hipMalloc failed");
+            HIP_TRY(hipMemsetAsync(s->fz_state.p, 0, 16 * n_batches, s->stream));
+            HIP_TRY(hipMemsetAsync(s->fz_misc.p, 0, 64, s->stream));
+            FuseArgs fz{};
+            fz.name_off1 = (const uint32_t*)s->t_name_off[0].p; fz.name_off2 = (const uint32_t*)s->t_name_off[1].p;
+            fz.out1 = (uint8_t*)s->f_out[0].p; fz.out2 = (uint8_t*)s->f_out[3].p;
+            fz.fstate1 = (uint32_t*)s->fz_rec[0].p; fz.fstate2 = (uint32_t*)s->fz_rec[1].p;
+            fz.state = (unsigned long long*)s->fz_state.p;
+            fz.ticket = (unsigned int*)s->fz_misc.p; fz.abort = (int*)s->fz_misc.p + 1; fz.totals = (unsigned long long*)s->fz_misc.p + 1;
+            launch_fast<10, true, FUSE_WPBT, false, true>(c, s, cfg, st, accum_limit, &fz);
+            s->fused = true;
+        } else if (s->max_len <= 160) {
+            launch_fast_tier<10, 16, 12>(c, s, cfg, st, accum_limit);
+        } else if (s->max_len <= 256) {
+            launch_fast_tier<16, 12, 11>(c, s, cfg, st, accum_limit);
+        } else {
+            // 257 .. 288 bases: 2x250 reads that still carry a barcode + verify prefix (BASELINE config 5: 267 bases)
+            launch_fast_tier<18, 12, 10>(c, s, cfg, st, accum_limit);
+        }
+        hipLaunchKernelGGL(filter_overlap_list_kernel, dim3((unsigned)c->n_cu), dim3(BLOCK), 0, s->stream, s->view, cfg, c->circles,
+                           (aqc_result*)s->results.p, st, accum_limit, (const uint32_t*)s->deferred.p,
+                           (const unsigned int*)s->n_deferred.p);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(launch_event(*s, AQC_K_FILTER_OVERLAP, 1), s->stream));
+    s->timed[AQC_K_FILTER_OVERLAP] = !s->collecting;
+    s->ran = true;
+    return 0;
+}
+
+// ---- results -----------------------------------------------------------------------------------------------------
+int aqc_fetch_results(aqc_ctx* c, int slot, aqc_result* out, uint64_t n) {
+    GET_SLOT(s);
+    if (!s->ran) return fail(AQC_ERR_STATE, "aqc_fetch_results before aqc_run");
+    if (n > s->n) return fail(AQC_ERR_ARG, "aqc_fetch_results: n exceeds the slot's records");
+    if (n) HIP_TRY(hipMemcpyAsync(out, s->results.p, sizeof(aqc_result) * n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(slot_sync(*s));
+    return check_status(*s);
+}
+
+int aqc_fetch_quality_views(aqc_ctx* c, int slot, int mate, uint32_t* out, uint64_t n) {
+    GET_SLOT(s);
+    if (!s->ran) return fail(AQC_ERR_STATE, "aqc_fetch_quality_views before aqc_run");
+    if (n > s->n || !out || mate < 0 || mate > 1 || (mate == 1 && !s->paired)) return fail(AQC_ERR_ARG, "aqc_fetch_quality_views: bad arguments");
+    if (n == 0) return 0;
+    if (s->off_stage.reserve(sizeof(uint32_t) * n)) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    hipLaunchKernelGGL(quality_views_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, s->view, (const aqc_result*)s->results.p, mate,
+                       (uint32_t*)s->off_stage.p, n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, s->off_stage.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(slot_sync(*s));
+    return 0;
+}
+
+int aqc_last_deferred(aqc_ctx* c, int slot, uint32_t* idx, uint64_t cap, uint64_t* n) {
+    GET_SLOT(s);
+    if (!n) return fail(AQC_ERR_ARG, "aqc_last_deferred: null argument");
+    if (!s->ran) return fail(AQC_ERR_STATE, "aqc_last_deferred before aqc_run");
+    HIP_TRY(slot_sync(*s));
+    *n = 0;
+    if (!s->used_fast || !s->n_deferred.p) return 0;
+    unsigned int m = 0;
+    HIP_TRY(hipMemcpy(&m, s->n_deferred.p, sizeof(m), hipMemcpyDeviceToHost));
+    *n = m;
+    const uint64_t w = m < cap ? m : cap;
+    if (idx && w) HIP_TRY(hipMemcpy(idx, s->deferred.p, sizeof(uint32_t) * w, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- gzip output on the device (aqc_gzdev.hpp) --------------------------------------------------------------------------------
+static int ensure_gz_tables(aqc_ctx* c) {
+    if (c->gz_crc.p) return 0;
+    GzCrcTables t;
+    for (uint32_t i = 0; i < 256; ++i) {
+        uint32_t v = i;
+        for (int k = 0; k < 8; ++k) v = (v >> 1) ^ (0xEDB88320u & (0u - (v & 1u)));
+        t.byte_table[i] = v;
+    }
+    // "advance the CRC register by n zero bytes" is linear: column j is what zlib's crc32_combine makes of the unit vector
+    for (int k = 0; k < 8; ++k)
+        for (int j = 0; j < 32; ++j) t.shift[k][j] = (uint32_t)crc32_combine((uLong)(1u << j), 0UL, (z_off_t)(GZ_SEG << k));
+    if (c->gz_crc.reserve(sizeof(t))) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    HIP_TRY(hipMemcpy(c->gz_crc.p, &t, sizeof(t), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int aqc_compress(aqc_ctx* c, int slot, int32_t level, uint64_t gz_bytes_out[6]) {
+    GET_SLOT(s);
+    int rc;
+    if (!gz_bytes_out) return fail(AQC_ERR_ARG, "aqc_compress: null argument");
+    if (!s->formatted) return fail(AQC_ERR_STATE, "aqc_compress before aqc_format");
+    if (level < 1) return fail(AQC_ERR_UNSUPPORTED, "aqc_compress: level %d (stored output is the host writer's business)", level);
+    if ((rc = ensure_gz_tables(c))) return rc;
+    static_assert(sizeof(GzCodebookDev) == sizeof(aqcgz::GzCodebook), "host and device codebook layouts must agree");
+    GzJob J{};
+    uint32_t n_members = 0;
+    // members of 64 x 255 bytes, a wave each (round 6: gz_encode_wave_kernel); AQC_GZ_ENCODER=seg: members of 256 x 255 bytes, a
+    // thread per 255-byte segment (gz_encode_kernel, rounds 3 - 5)
+    static const bool wave_enc = [] { const char* e = getenv("AQC_GZ_ENCODER"); return !(e && e[0] == 's'); }();
+    J.member_text = wave_enc ? (uint32_t)GZW_TEXT : (uint32_t)GZ_TEXT;
+    J.slot_bytes = wave_enc ? (uint32_t)GZW_SLOT : (uint32_t)GZ_SLOT;
+    for (int q = 0; q < 6; ++q) {
+        J.text[q] = (const uint8_t*)s->f_out[q].p;
+        J.bytes[q] = s->f_bytes[q];
+        J.first_block[q] = n_members;
+        n_members += (uint32_t)((s->f_bytes[q] + J.member_text - 1) / J.member_text);
+        s->g_bytes[q] = 0;
+        gz_bytes_out[q] = 0;
+    }
+    J.first_block[6] = n_members;
+    // (`compressed` is set once the streams exist: an error on the way must not let aqc_fetch_gz hand out empty streams)
+    if (n_members == 0) { s->compressed = true; return 0; }
+    if (s->g_stage.reserve((size_t)n_members * J.slot_bytes) || s->g_sizes.reserve(4 * (size_t)n_members) || s->g_offsets.reserve(8 * (size_t)n_members) ||
+        s->g_total.reserve(64) || s->g_hist.reserve(6 * 320 * 4) || s->g_code.reserve(6 * sizeof(GzCodebookDev)))
+        return fail(AQC_ERR_HIP, "hipMalloc failed");
+    for (int q = 0; q < 6; ++q) {
+        const uint64_t nb = J.first_block[q + 1] - J.first_block[q];
+        if (s->g_packed[q].reserve(nb * (J.member_text + 31) + 64)) return fail(AQC_ERR_HIP, "hipMalloc failed");
+        J.packed[q] = (uint8_t*)s->g_packed[q].p;
+    }
+    J.stage = (uint8_t*)s->g_stage.p; J.sizes = (uint32_t*)s->g_sizes.p; J.offsets = (uint64_t*)s->g_offsets.p; J.total = (uint64_t*)s->g_total.p;
+    J.hist = (uint32_t*)s->g_hist.p; J.code = (const GzCodebookDev*)s->g_code.p; J.crc = (const GzCrcTables*)c->gz_crc.p;
+    // 1. symbol counts of a sample of every stream's members
+    HIP_TRY(hipMemsetAsync(s->g_hist.p, 0, 6 * 320 * 4, s->stream));
+    hipLaunchKernelGGL(gz_hist_kernel, dim3(6 * GZ_SAMPLES), dim3(GZ_THREADS), 0, s->stream, J);
+    HIP_TRY(hipGetLastError());
+    uint32_t h[6][320];
+    HIP_TRY(hipMemcpyAsync(h, s->g_hist.p, sizeof(h), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    // 2. one code per stream, built on the host with the routines of its own encoder
+    std::vector<aqcgz::GzCodebook> cb(6);
+    for (int q = 0; q < 6; ++q)
+        if (!aqcgz::build_codebook(h[q], h[q] + 286, &cb[q])) return fail(AQC_ERR_STATE, "aqc_compress: could not build a Huffman code");
+    HIP_TRY(hipMemcpyAsync(s->g_code.p, cb.data(), 6 * sizeof(aqcgz::GzCodebook), hipMemcpyHostToDevice, s->stream));
+    // 3. members, their places, the contiguous streams
+    if (wave_enc) hipLaunchKernelGGL(gz_encode_wave_kernel, dim3(n_members), dim3(WAVE), 0, s->stream, J);
+    else hipLaunchKernelGGL(gz_encode_kernel, dim3(n_members), dim3(GZ_THREADS), 0, s->stream, J);
+    hipLaunchKernelGGL(gz_offsets_kernel, dim3(6), dim3(GZ_THREADS), 0, s->stream, J);
+    hipLaunchKernelGGL(gz_pack_kernel, dim3(n_members), dim3(GZ_THREADS), 0, s->stream, J);
+    HIP_TRY(hipGetLastError());
+    unsigned long long tot[6];
+    HIP_TRY(hipMemcpyAsync(tot, s->g_total.p, sizeof(tot), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));      // (cb and tot live on this stack frame)
+    for (int q = 0; q < 6; ++q) {
+        s->g_bytes[q] = tot[q];
+        gz_bytes_out[q] = tot[q];
+    }
+    rc = check_status(*s);
+    s->compressed = rc == 0;
+    return rc;
+}
+
+int aqc_fetch_gz(aqc_ctx* c, int slot, int file, int stream, uint8_t* dst, uint64_t cap) {
+    GET_SLOT(s);
+    if (!s->compressed) return fail(AQC_ERR_STATE, "aqc_fetch_gz before aqc_compress");
+    if (file < 0 || file > 1 || stream < 0 || stream > 2) return fail(AQC_ERR_ARG, "aqc_fetch_gz: bad file/stream");
+    const int q = file * 3 + stream;
+    return fetch_out(*s, s->g_packed[q].p, s->g_bytes[q], dst, cap, "aqc_fetch_gz");
+}
+
+// ---- function seams: run on a scratch slot (the last one) -------------------------------------------
+static int seam_prepare(aqc_ctx* c, const aqc_batch* b, bool need_qual, bool need_pair, Slot** out) {
+    if (!c || !b) return fail(AQC_ERR_ARG, "null argument");
+    Slot* s;
+    int rc = get_slot(c, c->n_slots - 1, &s);
+    if (rc) return rc;
+    if ((rc = fill_slot(c, *s, b, need_qual, need_pair))) return rc;
+    for (uint64_t i = 0; i < b->n; i++)
+        if (b->len1[i] > AQC_MAX_READ_LEN || (need_pair && b->len2[i] > AQC_MAX_READ_LEN))
+            return fail(AQC_ERR_READ_TOO_LONG, "record %llu is longer than %d", (unsigned long long)i, AQC_MAX_READ_LEN);
+    *out = s;
+    return 0;
+}
+
+static int seam_out_bytes(Slot* s, DevBuf& d, void* host, size_t bytes) {
+    if (bytes) HIP_TRY(hipMemcpyAsync(host, d.p, bytes, hipMemcpyDeviceToHost, s->stream));
+    return 0;
+}
+#define seam_out(s, d, host, n) seam_out_bytes(s, d, host, sizeof(*(host)) * (n))
+
+int aqc_overlap(aqc_ctx* c, const aqc_batch* b, int32_t* offset, int32_t* overlap_len, int32_t* diff) {
+    Slot* s;
+    int rc = seam_prepare(c, b, false, true, &s);
+    if (rc) return rc;
+    const uint64_t n = b->n;
+    if (n == 0) return 0;
+    DevBuf o[3];
+    for (auto& d : o)
+        if (d.reserve(4 * n)) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    hipLaunchKernelGGL(overlap_seam_kernel, dim3((unsigned)((n + WPB - 1) / WPB)), dim3(BLOCK), 0, s->stream, s->view,
+                       (int32_t*)o[0].p, (int32_t*)o[1].p, (int32_t*)o[2].p);
+    HIP_TRY(hipGetLastError());
+    if ((rc = seam_out(s, o[0], offset, n)) || (rc = seam_out(s, o[1], overlap_len, n)) || (rc = seam_out(s, o[2], diff, n))) return rc;
+    HIP_TRY(slot_sync(*s));
+    return 0;
+}
+
+int aqc_read_stats(aqc_ctx* c, const aqc_batch* b, int32_t max_poly, int32_t mismatch, int32_t qual, uint8_t* polyx,
+                   int32_t* low_qual, int32_t* n_count) {
+    Slot* s;
+    int rc = seam_prepare(c, b, true, false, &s);
+    if (rc) return rc;
+    const uint64_t n = b->n;
+    if (n == 0) return 0;
+    DevBuf o[3];
+    if (o[0].reserve(n) || o[1].reserve(4 * n) || o[2].reserve(4 * n)) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    hipLaunchKernelGGL(read_stats_seam_kernel, dim3((unsigned)((n + WPB - 1) / WPB)), dim3(BLOCK), 0, s->stream, s->view,
+                       max_poly, mismatch, qual, (uint8_t*)o[0].p, (int32_t*)o[1].p, (int32_t*)o[2].p);
+    HIP_TRY(hipGetLastError());
+    if ((rc = seam_out(s, o[0], polyx, n)) || (rc = seam_out(s, o[1], low_qual, n)) || (rc = seam_out(s, o[2], n_count, n))) return rc;
+    HIP_TRY(slot_sync(*s));
+    return 0;
+}
+
+int aqc_edit_distance(aqc_ctx* c, const aqc_batch* b, int32_t* dist) {
+    Slot* s;
+    int rc = seam_prepare(c, b, false, true, &s);
+    if (rc) return rc;
+    const uint64_t n = b->n;
+    if (n == 0) return 0;
+    DevBuf o;
+    if (o.reserve(4 * n)) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    hipLaunchKernelGGL(edit_distance_seam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, s->view,
+                       (int32_t*)o.p, s->status);
+    HIP_TRY(hipGetLastError());
+    if ((rc = seam_out(s, o, dist, n))) return rc;
+    HIP_TRY(slot_sync(*s));
+    return check_status(*s);
+}
+
+// ---- the reference's existing native seam: libed.so (editdistance/_editdistance.h:16,23, loaded by util.py:16-24) ----
+// Same two symbols, same signatures, so that `cdll.LoadLibrary(<this library>)` serves util.editDistance (util.py:70) and
+// util.overlap_hm_cpp (util.py:223).  Device-backed like everything else here (one lazily created context on GPU 0, one
+// small launch per call); no error channel exists in these signatures, so a failure is printed and the "none" value
+// of the interface comes back (0xFFFFFFFF / 0x7FFFFFFF).
+static std::mutex g_compat_mu;
+static aqc_ctx* g_compat = nullptr;
+// (on the heap and never deleted: a static DevBuf would call hipFree from a static destructor at exit(), in no fixed order
+//  against the HIP runtime's own tear-down)
+static DevBuf* const g_compat_buf = new DevBuf[4];
+
+static int compat_prepare(const char* a, size_t la, const char* b, size_t lb, size_t row_bytes) {
+    if (!g_compat) {
+        int rc = aqc_create(0, 1, &g_compat);
+        if (rc) { g_compat = nullptr; return rc; }
+    }
+    HIP_TRY(hipSetDevice(g_compat->device));
+    if (g_compat_buf[0].reserve(la + 16) || g_compat_buf[1].reserve(lb + 16) || g_compat_buf[2].reserve(row_bytes + 16) ||
+        g_compat_buf[3].reserve(16))
+        return fail(AQC_ERR_HIP, "hipMalloc failed");
+    if (la) HIP_TRY(hipMemcpy(g_compat_buf[0].p, a, la, hipMemcpyHostToDevice));
+    if (lb) HIP_TRY(hipMemcpy(g_compat_buf[1].p, b, lb, hipMemcpyHostToDevice));
+    return 0;
+}
+
+unsigned int edit_distance(const char* a, const unsigned int asize, const char* b, const unsigned int bsize) {
+    if (asize == 0) return bsize;                    // (_editdistance.cpp:101-102)
+    if (bsize == 0) return asize;
+    std::lock_guard<std::mutex> g(g_compat_mu);
+    int out = -1;
+    if (compat_prepare(a, asize, b, bsize, sizeof(int) * ((size_t)bsize + 1)) == 0) {
+        hipLaunchKernelGGL(edit_distance_any_kernel, dim3(1), dim3(WAVE), 0, 0, (const uint8_t*)g_compat_buf[0].p, (int)asize,
+                           (const uint8_t*)g_compat_buf[1].p, (int)bsize, (int*)g_compat_buf[2].p, (int*)g_compat_buf[3].p);
+        if (hipMemcpy(&out, g_compat_buf[3].p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) out = -1;
+    }
+    if (out < 0) fprintf(stderr, "libafterqc_hip: edit_distance failed: %s\n", aqc_last_error());
+    return (unsigned int)out;
+}
+
+int seek_overlap(const char* r1, const int len1, const char* r2, const int len2, const int limit_distance,
+                 const int complete_compare_require, const int overlap_require) {
+    std::lock_guard<std::mutex> g(g_compat_mu);
+    int out = 0x7FFFFFFF;
+    bool ok = len1 >= 0 && len2 >= 0 && compat_prepare(r1, (size_t)len1, r2, (size_t)len2, 0) == 0;
+    if (ok) {
+        hipLaunchKernelGGL(seek_overlap_kernel, dim3(1), dim3(WAVE), 0, 0, (const uint8_t*)g_compat_buf[0].p, len1,
+                           (const uint8_t*)g_compat_buf[1].p, len2, limit_distance, complete_compare_require, overlap_require,
+                           (int*)g_compat_buf[3].p);
+        ok = hipMemcpy(&out, g_compat_buf[3].p, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) { fprintf(stderr, "libafterqc_hip: seek_overlap failed: %s\n", aqc_last_error()); out = 0x7FFFFFFF; }
+    return out;
+}
+
+
+}  // extern "C"

@@ -1,7 +1,9 @@
 // aqc_prim.hpp — what more than one stage of the gfx950 device code uses, one copy of each: the wave size and lane id, loads / stores
-// that name their address space, the 16-byte unaligned load / store, and the wave-wide reductions and scans.  It depends on no other
-// header of the project; every stage header (aqc_batch / aqc_record / aqc_qcstat / aqc_seams / aqc_fast / aqc_textin / aqc_fmt /
-// aqc_fmtcopy / aqc_census / aqc_gzdev) includes it for these and includes another stage's header only for what is that stage's own.
+// that name their address space, the 16-byte unaligned load / store, the wave-wide reductions and scans, and the complement of a base.
+// It depends on no other header of the project and defines no kernel; every stage header (aqc_record / aqc_qcstat / aqc_seams /
+// aqc_fast / aqc_textin / aqc_fmt / aqc_fmtcopy / aqc_census / aqc_gzdev) includes it for these and includes another stage's header
+// only for what is that stage's own — and only where both belong to the same C-API unit (aqc_ctx.hpp): a header that defines a
+// non-template kernel is included by one unit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -132,6 +134,29 @@ __device__ __forceinline__ unsigned long long block_excl_scan(unsigned long long
         total += t;
     }
     return base + inc - v;
+}
+
+// ---- the complement of a base (the verdict kernels, the seams and the k-mer kernel's reverse complement) ------------------------------
+// util.py:27 COMP; returns 0 for bytes outside the table (KeyError upstream)
+__device__ __forceinline__ uint8_t comp_strict(uint8_t c) {
+    switch (c) {
+        case 'A': return 'T';
+        case 'T': return 'A';
+        case 'C': return 'G';
+        case 'G': return 'C';
+        case 'a': return 't';
+        case 't': return 'a';
+        case 'c': return 'g';
+        case 'g': return 'c';
+        case 'N': return 'N';
+        default: return 0;
+    }
+}
+
+// util.py:47-50 reverseComplement's per-base rule: unknown -> 'N'
+__device__ __forceinline__ uint8_t comp_or_n(uint8_t c) {
+    uint8_t r = comp_strict(c);
+    return r ? r : (uint8_t)'N';
 }
 
 }  // namespace aqc

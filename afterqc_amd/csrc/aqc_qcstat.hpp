@@ -1,13 +1,14 @@
-// aqc_qcstat.hpp — the statRead stage (qualitycontrol.py:73-122): the k-mer table, the read descriptors of the sampling kernels, the
-// per-cycle accumulators, and qc_stat_kernel / kmer_count_kernel / kmer_reduce_kernel / the two compact kernels.
+// aqc_qcstat.hpp — the statRead stage (qualitycontrol.py:73-122): the read descriptors of the sampling kernels, the per-cycle
+// accumulators, and qc_stat_kernel / kmer_count_kernel / kmer_reduce_kernel / the two compact kernels.  The k-mer table they fill
+// (KmerTable) is a member of the context and sits with the other descriptors in aqc_batch.hpp; comp_or_n comes from aqc_prim.hpp.
+// It defines kernels: aqc_capi_qc.hip is the one unit that includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "afterqc_hip.h"
 #include "aqc_prim.hpp"
-#include "aqc_batch.hpp"
-#include "aqc_record.hpp"      // comp_or_n: the reverse complement of a k-mer's bytes
+#include "aqc_batch.hpp"      // DevBatch, KmerTable and the sizes of its dense tables
 
 namespace aqc {
 
@@ -16,29 +17,7 @@ namespace aqc {
 // Block-private u32 accumulators in LDS, flushed with 64-bit global atomics at the end.
 // k-mers go to an open-addressing table in HBM keyed by the k raw bytes (k <= 8).
 // ------------------------------------------------------------------------------------------------
-struct KmerTable {
-    // open-addressing table for k-mers containing anything but A,C,G,T (rare): keyed by the k raw bytes
-    unsigned long long* keys;    // 0 = empty
-    unsigned long long* counts;  // [capacity + 1]: entry `capacity` belongs to the all-NUL k-mer, whose key is 0 (see kmer_slot)
-    unsigned long long* order;   // [capacity + 1] min over 2*t (seen) / 2*t+1 (inserted as reverse complement)
-    uint64_t mask;               // capacity - 1
-    // dense tables for pure A/C/G/T k-mers, 4^k entries.  Index = (bit-1 plane << k) | bit-0 plane of the
-    // per-base code (c >> 1) & 3 (A=0 C=1 T=2 G=3); base j of the k-mer sits at bit j of each plane.
-    // One copy of the dense tables PER XCD (8 on MI355X): a wave updates the copy of the XCD it runs on with
-    // atomics that execute in that XCD's L2 (workgroup scope is enough: every accessor of a copy shares the L2),
-    // instead of device-scope atomics that have to travel to the memory side.  Copies are summed / min-ed when
-    // the dictionary is read back.
-    unsigned int* dense_count;         // [N_XCD][4^k]
-    unsigned long long* dense_first;   // [N_XCD][4^k] smallest scan time t at which the k-mer was seen (~0 = never)
-    // complete[b] != 0: every dense entry of reduce-workgroup b has a first-seen time (written by kmer_reduce_kernel).
-    // Time keys only grow from launch to launch, so once every entry has one no later launch can lower any of them
-    // and kmer_count_kernel stops probing the first-seen table (for random DNA that is after ~10^4 reads).
-    unsigned int* complete;            // [DENSE_ENTRIES / KRED_ENTRIES]
-};
-constexpr int N_XCD = 8;
-constexpr uint32_t DENSE_ENTRIES = 1u << 16;   // 4^8
 constexpr int KRED_BLOCK = 256;
-constexpr int KRED_ENTRIES = 256;       // dense entries per kmer_reduce_kernel workgroup
 
 // id of the XCD this wave runs on (HW_REG_XCC_ID, bits 3:0)
 __device__ __forceinline__ uint32_t xcc_id() { return __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & (N_XCD - 1); }

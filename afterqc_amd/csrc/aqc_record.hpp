@@ -2,7 +2,8 @@
 // pair, stages the four byte strings of the pair in LDS and runs the whole per-read pipeline of preprocesser.py:436-631 on them with
 // ballot / popcount reductions.  Every stage is an exact restatement of the reference arithmetic; comments cite the reference lines.
 // Integer / byte work only — no MFMA, no floats except the f64 circle test of isInBubble.  The screens, process_record_wave and the
-// two general verdict kernels built on it.
+// two general verdict kernels built on it.  It defines kernels: aqc_capi_run.hip is the one unit that includes it (aqc_seams.hpp,
+// of the same unit, builds on it; the complement table the statRead stage shares with it is in aqc_prim.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,28 +17,6 @@ namespace aqc {
 constexpr int BLOCK = 256;
 constexpr int WPB = BLOCK / WAVE;      // waves (= records in flight) per workgroup
 constexpr int LSTR = 1024;             // LDS bytes per staged string (AQC_MAX_READ_LEN = 1000)
-
-// util.py:27 COMP; returns 0 for bytes outside the table (KeyError upstream)
-__device__ __forceinline__ uint8_t comp_strict(uint8_t c) {
-    switch (c) {
-        case 'A': return 'T';
-        case 'T': return 'A';
-        case 'C': return 'G';
-        case 'G': return 'C';
-        case 'a': return 't';
-        case 't': return 'a';
-        case 'c': return 'g';
-        case 'g': return 'c';
-        case 'N': return 'N';
-        default: return 0;
-    }
-}
-
-// util.py:47-50 reverseComplement's per-base rule: unknown -> 'N'
-__device__ __forceinline__ uint8_t comp_or_n(uint8_t c) {
-    uint8_t r = comp_strict(c);
-    return r ? r : (uint8_t)'N';
-}
 
 // ALL_BASES index A,T,C,G -> 0..3 (qualitycontrol.py:24), -1 otherwise
 __device__ __forceinline__ int base_idx(uint8_t c) {

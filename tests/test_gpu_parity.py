@@ -406,7 +406,7 @@ def test_qc_stat_from_two_threads(gpu_engine):
                 assert np.array_equal(a, c)
 
 
-# ---- verdict kernel tiers (aqc_capi.hip: <= 160 bases 10 words, <= 256 16 words, <= 288 18 words, else the general kernel) -----
+# ---- verdict kernel tiers (aqc_capi_run.hip: <= 160 bases 10 words, <= 256 16 words, <= 288 18 words, else the general kernel) -----
 @pytest.mark.parametrize("barcode", [False, True])
 @pytest.mark.parametrize("paired", [True, False])
 @pytest.mark.parametrize("max_len", [160, 161, 256, 257, 288, 289])

@@ -21,7 +21,7 @@ import qc_compare
 
 pytestmark = pytest.mark.gpu
 
-KMER_CAP = 1 << 21          # the open-addressing table's capacity (aqc_capi.hip)
+KMER_CAP = 1 << 21          # the open-addressing table's capacity (aqc_ctx.hpp)
 WORKERS = 4
 
 
