@@ -666,7 +666,9 @@ class Engine:
         return [int(x) for x in sizes]
 
     def compress(self, slot, level=2):
-        """the slot's formatted streams as gzip members, built on the device -> compressed bytes per stream"""
+        """the slot's formatted streams as gzip members, built on the device -> compressed bytes per stream.  level 1 - 5: the fast
+        encoder (runs and the column four lines up; members of 16320 bytes); 6 - 9: a hash-chain match search over a 32 KiB window
+        with 8 / 16 / 32 / 64 candidates per position (members of 0xff00 bytes); 0 and 10 or more are refused"""
         sizes = np.zeros(6, dtype=np.uint64)
         self._check(self.lib.aqc_compress(self.h, slot, int(level), _ptr(sizes)))
         return [int(x) for x in sizes]
@@ -728,7 +730,8 @@ class Pipe:
     def run(self, inputs, outputs=None, gzip_in=(False, False), gzip_out=False, gzip_level=2, chunk_records=0, qc_sample=200000,
             store_overlap=False, no_output=False, chunk_index0=0, chunk_index_stride=1):
         """inputs: list of 1-2 file names, or of (numpy uint8 array / HostBuffer.array, nbytes) tuples (text in memory);
-        outputs: per input (good, bad, overlap) file names or None.  Returns a PipeResult."""
+        outputs: per input (good, bad, overlap) file names or None.  gzip_level 1 - 9 goes to aqc_compress as it is (1 - 5: the fast
+        device encoder, 6 - 9: its hash-chain search), 0 writes stored members on the host.  Returns a PipeResult."""
         io = PipeIO()
         keep = []
         for k, src in enumerate(inputs):

@@ -8,11 +8,12 @@
 // verdict kernels until it can be measured on its own (profiles/r11_capi_split.txt).
 //
 // Kernels launched here, and nowhere else (this is the one unit that includes aqc_upload.hpp, aqc_record.hpp, aqc_seams.hpp and
-// aqc_gzdev.hpp):
+// aqc_gzdev.hpp + aqc_gzlz.hpp):
 //   aqc_upload.hpp   narrow_offsets_kernel, mark_irregular_kernel, quality_views_kernel
 //   aqc_record.hpp   filter_overlap_kernel, filter_overlap_list_kernel
 //   aqc_fast.hpp     fast_filter_overlap_kernel<NW, PAIRED, WPBT, BARCODE, FUSE> (a template: the variants are instantiated here)
 //   aqc_gzdev.hpp    gz_hist_kernel, gz_encode_wave_kernel, gz_encode_kernel, gz_offsets_kernel, gz_pack_kernel
+//   aqc_gzlz.hpp     gz_hist_lz_kernel, gz_encode_lz_kernel (levels 6 - 9)
 //   aqc_seams.hpp    overlap_seam_kernel, read_stats_seam_kernel, edit_distance_seam_kernel, edit_distance_any_kernel,
 //                    seek_overlap_kernel
 #include <hip/hip_runtime.h>
@@ -29,6 +30,7 @@
 #include "aqc_seams.hpp"
 #include "aqc_fast.hpp"
 #include "aqc_gzdev.hpp"
+#include "aqc_gzlz.hpp"
 #include "aqc_gz.hpp"
 #include <zlib.h>
 
@@ -331,6 +333,7 @@ int aqc_compress(aqc_ctx* c, int slot, int32_t level, uint64_t gz_bytes_out[6]) 
     if (!gz_bytes_out) return fail(AQC_ERR_ARG, "aqc_compress: null argument");
     if (!s->formatted) return fail(AQC_ERR_STATE, "aqc_compress before aqc_format");
     if (level < 1) return fail(AQC_ERR_UNSUPPORTED, "aqc_compress: level %d (stored output is the host writer's business)", level);
+    if (level > 9) return fail(AQC_ERR_ARG, "aqc_compress: level %d (1 .. 9)", level);
     if ((rc = ensure_gz_tables(c))) return rc;
     static_assert(sizeof(GzCodebookDev) == sizeof(aqcgz::GzCodebook), "host and device codebook layouts must agree");
     GzJob J{};
@@ -338,8 +341,13 @@ int aqc_compress(aqc_ctx* c, int slot, int32_t level, uint64_t gz_bytes_out[6]) 
     // members of 64 x 255 bytes, a wave each (round 6: gz_encode_wave_kernel); AQC_GZ_ENCODER=seg: members of 256 x 255 bytes, a
     // thread per 255-byte segment (gz_encode_kernel, rounds 3 - 5)
     static const bool wave_enc = [] { const char* e = getenv("AQC_GZ_ENCODER"); return !(e && e[0] == 's'); }();
-    J.member_text = wave_enc ? (uint32_t)GZW_TEXT : (uint32_t)GZ_TEXT;
-    J.slot_bytes = wave_enc ? (uint32_t)GZW_SLOT : (uint32_t)GZ_SLOT;
+    // levels 6 - 9: members of 256 x 255 bytes with a hash-chain match search, a wave each (gz_encode_lz_kernel, aqc_gzlz.hpp);
+    // AQC_GZ_LZ=0 sends them down the path of levels 1 - 5
+    static const bool lz_on = [] { const char* e = getenv("AQC_GZ_LZ"); return !(e && e[0] == '0'); }();
+    const bool lz = level >= 6 && lz_on;
+    const bool wave_members = wave_enc && !lz;
+    J.member_text = wave_members ? (uint32_t)GZW_TEXT : (uint32_t)GZ_TEXT;
+    J.slot_bytes = wave_members ? (uint32_t)GZW_SLOT : (uint32_t)GZ_SLOT;
     for (int q = 0; q < 6; ++q) {
         J.text[q] = (const uint8_t*)s->f_out[q].p;
         J.bytes[q] = s->f_bytes[q];
@@ -363,7 +371,8 @@ int aqc_compress(aqc_ctx* c, int slot, int32_t level, uint64_t gz_bytes_out[6]) 
     J.hist = (uint32_t*)s->g_hist.p; J.code = (const GzCodebookDev*)s->g_code.p; J.crc = (const GzCrcTables*)c->gz_crc.p;
     // 1. symbol counts of a sample of every stream's members
     HIP_TRY(hipMemsetAsync(s->g_hist.p, 0, 6 * 320 * 4, s->stream));
-    hipLaunchKernelGGL(gz_hist_kernel, dim3(6 * GZ_SAMPLES), dim3(GZ_THREADS), 0, s->stream, J);
+    if (lz) hipLaunchKernelGGL(gz_hist_lz_kernel, dim3(6 * GZ_SAMPLES), dim3(WAVE), 0, s->stream, J, gzlz_depth(level));
+    else hipLaunchKernelGGL(gz_hist_kernel, dim3(6 * GZ_SAMPLES), dim3(GZ_THREADS), 0, s->stream, J);
     HIP_TRY(hipGetLastError());
     uint32_t h[6][320];
     HIP_TRY(hipMemcpyAsync(h, s->g_hist.p, sizeof(h), hipMemcpyDeviceToHost, s->stream));
@@ -374,7 +383,8 @@ int aqc_compress(aqc_ctx* c, int slot, int32_t level, uint64_t gz_bytes_out[6]) 
         if (!aqcgz::build_codebook(h[q], h[q] + 286, &cb[q])) return fail(AQC_ERR_STATE, "aqc_compress: could not build a Huffman code");
     HIP_TRY(hipMemcpyAsync(s->g_code.p, cb.data(), 6 * sizeof(aqcgz::GzCodebook), hipMemcpyHostToDevice, s->stream));
     // 3. members, their places, the contiguous streams
-    if (wave_enc) hipLaunchKernelGGL(gz_encode_wave_kernel, dim3(n_members), dim3(WAVE), 0, s->stream, J);
+    if (lz) hipLaunchKernelGGL(gz_encode_lz_kernel, dim3(n_members), dim3(WAVE), 0, s->stream, J, gzlz_depth(level));
+    else if (wave_enc) hipLaunchKernelGGL(gz_encode_wave_kernel, dim3(n_members), dim3(WAVE), 0, s->stream, J);
     else hipLaunchKernelGGL(gz_encode_kernel, dim3(n_members), dim3(GZ_THREADS), 0, s->stream, J);
     hipLaunchKernelGGL(gz_offsets_kernel, dim3(6), dim3(GZ_THREADS), 0, s->stream, J);
     hipLaunchKernelGGL(gz_pack_kernel, dim3(n_members), dim3(GZ_THREADS), 0, s->stream, J);

@@ -407,7 +407,11 @@ int aqc_fetch_streams(aqc_ctx* ctx, int slot, int32_t gz, uint8_t* const dst[6],
  * block; matches = runs and "same column, four lines up"; one shared code per stream and call, built by the host from sampled
  * symbol counts; CRC-32 on the device).  gz_bytes_out[file * 3 + stream] = compressed bytes; aqc_fetch_gz copies one
  * compressed stream to host memory and waits for it.  Streams concatenate into valid .gz files; what they decompress to is
- * byte for byte what aqc_fetch_text hands out.  level >= 1 (stored output, level 0, stays with the host writer). */
+ * byte for byte what aqc_fetch_text hands out.  level 1 .. 5: the encoder described above (the level changes nothing; members
+ * of 16320 bytes by default).  level 6 .. 9: members of 0xff00 bytes whose matches come from a hash-chain search over the 32 KiB
+ * before a position, 8 / 16 / 32 / 64 candidates per position (aqc_gzlz.hpp) — smaller streams, more device time; the sample
+ * that the shared code is built from is tokenised by the same search.  level 0 (stored output stays with the host writer):
+ * AQC_ERR_UNSUPPORTED; level > 9: AQC_ERR_ARG. */
 int aqc_compress(aqc_ctx* ctx, int slot, int32_t level, uint64_t gz_bytes_out[6]);
 int aqc_fetch_gz(aqc_ctx* ctx, int slot, int file, int stream, uint8_t* dst, uint64_t cap);
 /* gzip INPUT decoded with the device's help (fastq.py:23-24: gzip.open(name, "r"); csrc/aqc_gunzip_dev.hpp): the gzip file at
