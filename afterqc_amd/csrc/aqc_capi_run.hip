@@ -8,7 +8,8 @@
 // verdict kernels until it can be measured on its own (profiles/r11_capi_split.txt).
 //
 // Kernels launched here, and nowhere else (this is the one unit that includes aqc_upload.hpp, aqc_record.hpp, aqc_seams.hpp and
-// aqc_gzdev.hpp + aqc_gzlz.hpp):
+// aqc_gzdev.hpp + aqc_gzlz.hpp; the member, bit-ring and symbol functions the three encoders share are in aqc_gzdev.hpp and
+// aqc_deflate_sym.hpp):
 //   aqc_upload.hpp   narrow_offsets_kernel, mark_irregular_kernel, quality_views_kernel
 //   aqc_record.hpp   filter_overlap_kernel, filter_overlap_list_kernel
 //   aqc_fast.hpp     fast_filter_overlap_kernel<NW, PAIRED, WPBT, BARCODE, FUSE> (a template: the variants are instantiated here)

@@ -44,6 +44,8 @@
 #pragma once
 #include <stdint.h>
 #include <string.h>
+
+#include "aqc_deflate_sym.hpp"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define GZB_HD __host__ __device__
@@ -143,12 +145,9 @@ struct GzbJob {
     uint32_t s_symcap;           // most symbols one section may have
 };
 
-// base value and number of extra bits of length symbol 257 + i and of distance symbol i (RFC 1951 3.2.5), COMPUTED: a table in
-// memory is a trip to the cache per token for every lane (two trips in a row for a match: that alone was 0.8 us per token)
-GZB_HD inline uint32_t gzb_len_extra(uint32_t i) { return (i < 8u || i == 28u) ? 0u : (i - 4u) >> 2; }
-GZB_HD inline uint32_t gzb_len_base(uint32_t i) { return i == 28u ? 258u : i < 8u ? 3u + i : 3u + ((4u + (i & 3u)) << ((i - 4u) >> 2)); }
-GZB_HD inline uint32_t gzb_dist_extra(uint32_t i) { return i < 4u ? 0u : (i - 2u) >> 1; }
-GZB_HD inline uint32_t gzb_dist_base(uint32_t i) { return i < 4u ? 1u + i : 1u + ((2u + (i & 1u)) << ((i - 2u) >> 1)); }
+// base value and number of extra bits of length symbol 257 + i and of distance symbol i (RFC 1951 3.2.5) are COMPUTED (len_base,
+// len_extra, dist_base, dist_extra of aqc_deflate_sym.hpp): a table in memory is a trip to the cache per token for every lane (two
+// trips in a row for a match: that alone was 0.8 us per token)
 // the order the code-length code's lengths come in (16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15), five bits each in two constants
 GZB_HD inline uint32_t gzb_cl_order(uint32_t i) {
     return i < 12u ? (uint32_t)(0x22caa324e804a30ull >> (5u * i)) & 31u : (uint32_t)(0x3c2e1346cull >> (5u * (i - 12u))) & 31u;
@@ -450,8 +449,8 @@ GZB_HD inline uint32_t gzb_tokenize(In& in, uint32_t limit_bit, const GzbLaneTab
             break;
         }
         const uint32_t ls = e >> 8;
-        const uint32_t xb = gzb_len_extra(ls);
-        const uint32_t len = gzb_len_base(ls) + ((uint32_t)bb & ((1u << xb) - 1u));
+        const uint32_t xb = len_extra(ls);
+        const uint32_t len = len_base(ls) + ((uint32_t)bb & ((1u << xb) - 1u));
         bb >>= xb;
         bn -= xb;
         GZB_REFILL();                                         // a distance code + its extra bits take <= 28
@@ -464,8 +463,8 @@ GZB_HD inline uint32_t gzb_tokenize(In& in, uint32_t limit_bit, const GzbLaneTab
         }
         const uint32_t dl = de & 15u, ds = (de >> 4) & 31u;
         bb >>= dl;
-        const uint32_t dxb = gzb_dist_extra(ds);
-        const uint32_t dd = gzb_dist_base(ds) + ((uint32_t)bb & ((1u << dxb) - 1u));
+        const uint32_t dxb = dist_extra(ds);
+        const uint32_t dd = dist_base(ds) + ((uint32_t)bb & ((1u << dxb) - 1u));
         bb >>= dxb;
         bn -= dl + dxb;
         GZB_EMIT(at, (len << 16) | (dd - 1u));

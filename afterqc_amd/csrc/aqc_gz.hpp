@@ -28,6 +28,11 @@ constexpr int LIT_ROOT = 11, DIST_ROOT = 8;
 constexpr int LIT_TABLE = (1 << LIT_ROOT) + 2048, DIST_TABLE = (1 << DIST_ROOT) + 1024;
 constexpr uint32_t MARKER = 0x8000u;
 constexpr size_t WINDOW = 32768;
+// base value and number of extra bits of length symbol 257 + i / distance symbol i (RFC 1951 3.2.5), for both directions
+inline constexpr uint16_t LEN_BASE[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
+inline constexpr uint8_t LEN_EXTRA[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
+inline constexpr uint16_t DIST_BASE[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
+inline constexpr uint8_t DIST_EXTRA[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
 
 // One DEFLATE stream position + the tables of the block it is in.  OutT = uint8_t (bytes) or uint16_t (symbols, see above).
 // run() decodes whole blocks and may be resumed after GZ_NEED_OUTPUT with a bigger / emptied output buffer: out[0 .. out_pos)

@@ -20,10 +20,17 @@
 //              matrices precomputed on the host); the member's first four bytes are complemented instead of starting the
 //              register at ~0, which makes leading padding harmless (the last member of a stream is right-aligned in the grid).
 //   compaction member sizes -> exclusive scan per stream -> contiguous stream (gz_pack_kernel).
+//
+// Three encoders write this format: gz_encode_kernel (above; AQC_GZ_ENCODER=seg), gz_encode_wave_kernel (the default: a wave per
+// member of 64 x 255 bytes, see there) and gz_encode_lz_kernel (aqc_gzlz.hpp, levels 6 - 9).  What they do the same way is stated
+// once, in front of them: gz_member_of / gz_sample_of, gz_load_code, gz_store_member, gz_crc_segment / gz_crc_short, gz_frame_member
+// for all three; gzw_open_block, gzw_parse, gzw_token_bits, gzw_ring_put, gzw_close_block, gzw_crc for the two that walk a member
+// in windows of 64 bytes.  The length / distance symbols of RFC 1951 3.2.5: aqc_deflate_sym.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aqc_deflate_sym.hpp"
 #include "aqc_prim.hpp"
 
 namespace aqc {
@@ -33,6 +40,11 @@ constexpr int GZ_THREADS = 256, GZ_SEG = 255;
 constexpr int GZ_SLOT = 65536;                   // staging bytes per member; the member starts at byte 2 (deflate data 4-aligned)
 constexpr int GZ_MAX_LINES = 4096;
 constexpr int GZ_HDR_WORDS = 192;
+constexpr int GZ_SAMPLES = 16;                   // pieces of GZ_TEXT bytes sampled per stream (evenly spaced)
+constexpr int GZW_TEXT = 64 * 255;               // gz_encode_wave_kernel: 16320 text bytes per member
+constexpr int GZW_SLOT = 16896;                  // staging bytes per member (its text stored + headers, and a window's worth of slack)
+constexpr int GZW_MAX_LINES = 512;
+constexpr int GZW_RING = 128;                    // staging words of a wave's bit ring
 
 struct GzCodebookDev {
     uint32_t lit[286];       // bit-reversed code | length << 16
@@ -63,28 +75,6 @@ struct GzJob {
     uint64_t* total;
 };
 
-// base value and number of extra bits of length symbol 257 + i / distance symbol i (RFC 1951 3.2.5) in closed form: a table in
-// constant memory indexed per lane is a vector load from memory per token (measured on the inflate side, aqc_gunzip_dev.hpp)
-__device__ __forceinline__ int gz_len_extra(int i) { return (i < 8 || i == 28) ? 0 : (i - 4) >> 2; }
-__device__ __forceinline__ int gz_len_base(int i) { return i == 28 ? 258 : i < 8 ? 3 + i : 3 + ((4 + (i & 3)) << ((i - 4) >> 2)); }
-__device__ __forceinline__ int gz_dist_extra(int i) { return i < 4 ? 0 : (i - 2) >> 1; }
-__device__ __forceinline__ int gz_dist_base(int i) { return i < 4 ? 1 + i : 1 + ((2 + (i & 1)) << ((i - 2) >> 1)); }
-
-// length 3..258 -> length symbol - 257; distance 1..32768 -> distance symbol (closed forms: no tables)
-__device__ __forceinline__ int gz_len_sym(int len) {
-    if (len == 258) return 28;
-    if (len < 11) return len - 3;
-    const int v = len - 3;                        // 8 .. 254
-    const int e = 31 - __clz(v) - 2;              // extra bits: v in [8,16) -> 1, [16,32) -> 2, ...
-    return 4 + 4 * e + ((v >> e) & 3);
-}
-__device__ __forceinline__ int gz_dist_sym(int d) {
-    if (d < 5) return d - 1;
-    const int v = d - 1;                          // >= 4
-    const int e = 31 - __clz(v) - 1;              // extra bits
-    return 2 + 2 * e + ((v >> e) & 1);
-}
-
 // which member is this, and of which stream
 __device__ __forceinline__ int gz_stream_of(const GzJob& J, uint32_t member) {
     int q = 0;
@@ -93,18 +83,230 @@ __device__ __forceinline__ int gz_stream_of(const GzJob& J, uint32_t member) {
     return q;
 }
 
+// ---- what every encoder does the same way: the member and its frame -----------------------------------------------------------------
+// member `member` of the launch, cut from its stream in pieces of member_text bytes: the stream q, the text J.text[q] + off, n bytes
+__device__ __forceinline__ void gz_member_of(const GzJob& J, uint32_t member, int member_text, int& q, uint64_t& off, int& n) {
+    q = gz_stream_of(J, member);
+    const uint32_t local = member - J.first_block[q];
+    off = (uint64_t)local * member_text;
+    n = (int)min<uint64_t>(member_text, J.bytes[q] - off);
+}
+// workgroup (q, k) of a sampling pass: piece k * stride of stream q in pieces of GZ_TEXT bytes, whatever the encoder's members are.
+// false: the stream has no such piece
+__device__ __forceinline__ bool gz_sample_of(const GzJob& J, int& q, uint64_t& off, int& n) {
+    q = blockIdx.x / GZ_SAMPLES;
+    const int k = blockIdx.x % GZ_SAMPLES;
+    const uint32_t nb = (uint32_t)((J.bytes[q] + GZ_TEXT - 1) / GZ_TEXT);
+    const uint32_t stride = nb > GZ_SAMPLES ? nb / GZ_SAMPLES : 1u;
+    const uint32_t local = (uint32_t)k * stride;
+    off = (uint64_t)local * GZ_TEXT;
+    n = (int)min<uint64_t>(GZ_TEXT, J.bytes[q] - off);
+    return local < nb;
+}
+// the member's place in the staging buffer; its deflate data at +18 is 4-byte aligned
+__device__ __forceinline__ uint8_t* gz_member_slot(const GzJob& J, uint32_t member, int slot_bytes) { return J.stage + (uint64_t)member * slot_bytes + 2; }
+__device__ __forceinline__ uint32_t* gz_member_data(uint8_t* mem) { return reinterpret_cast<uint32_t*>(mem + 18); }
+
+// the stream's code and the CRC byte table into LDS, by a workgroup of NT threads
+template <int NT>
+__device__ __forceinline__ void gz_load_code(const GzCodebookDev& cb, const uint32_t* byte_table, uint32_t* lc, uint32_t* dc, uint32_t* crc_tab) {
+    for (int i = threadIdx.x; i < 286; i += NT) lc[i] = cb.lit[i];
+    if (threadIdx.x < 30) dc[threadIdx.x] = cb.dist[threadIdx.x];
+    static_assert(256 % NT == 0, "the byte table in whole rounds of the workgroup");
+#pragma unroll
+    for (int i = 0; i < 256; i += NT) crc_tab[i + threadIdx.x] = byte_table[i + threadIdx.x];
+}
+
+// incompressible with this code: one stored block (BFINAL = 1, BTYPE = 0, LEN, ~LEN, bytes), n + 5 bytes of deflate data
+__device__ __forceinline__ void gz_store_member(uint8_t* mem, const uint8_t* text, int n, int tid, int nthreads) {
+    if (tid == 0) {
+        mem[18] = 1;
+        mem[19] = (uint8_t)n; mem[20] = (uint8_t)(n >> 8); mem[21] = (uint8_t)~n; mem[22] = (uint8_t)(~n >> 8);
+    }
+    for (int i = tid; i < n; i += nthreads) mem[23 + i] = text[i];
+}
+
+// raw CRC-32 register over text[a, b) from 0, the member's first four bytes complemented: that equals starting the member's
+// register at 0xffffffff, in a form zeros in front of the member do not disturb
+__device__ __forceinline__ uint32_t gz_crc_segment(const uint32_t* crc_tab, const uint8_t* text, int a, int b) {
+    uint32_t c = 0;
+    for (int p = a; p < b; ++p) {
+        uint32_t x = text[p];
+        if (p < 4) x ^= 0xffu;
+        c = crc_tab[(c ^ x) & 0xffu] ^ (c >> 8);
+    }
+    return c;
+}
+// the same register for a member of fewer than four bytes, where the complement trick does not apply: the plain way.  (Of all
+// three functions here the CRC-32 is the complement of what they return: gz_frame_member(.., ~c, ..))
+__device__ __forceinline__ uint32_t gz_crc_short(const uint32_t* crc_tab, const uint8_t* text, int n) {
+    uint32_t c = 0xffffffffu;
+    for (int p = 0; p < n; ++p) c = crc_tab[(c ^ text[p]) & 0xffu] ^ (c >> 8);
+    return c;
+}
+
+// the BGZF header in front of dbytes of deflate data and the trailer (CRC-32, ISIZE) behind them.  -> bytes of the member
+__device__ __forceinline__ uint32_t gz_frame_member(uint8_t* mem, uint32_t dbytes, uint32_t crc, int n) {
+    const uint32_t bsize = 18u + dbytes + 8u;
+    static const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+    for (int i = 0; i < 16; ++i) mem[i] = hdr[i];
+    mem[16] = (uint8_t)((bsize - 1) & 0xffu);
+    mem[17] = (uint8_t)((bsize - 1) >> 8);
+    uint8_t* t = mem + 18 + dbytes;
+    for (int k = 0; k < 4; ++k) { t[k] = (uint8_t)(crc >> (8 * k)); t[4 + k] = (uint8_t)((uint32_t)n >> (8 * k)); }
+    return bsize;
+}
+
+// ---- what the two one-wave-per-member encoders (gz_encode_wave_kernel, gz_encode_lz_kernel) do the same way: a window of 64
+// consecutive bytes, a lane per byte, is parsed into tokens, the tokens' bits go through a ring of GZW_RING words in LDS to the
+// member, front to back ------------------------------------------------------------------------------------------------------------
+// bits of the lanes before this one
+__device__ __forceinline__ unsigned long long gzw_lanes_below(int lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }
+
+// the block header: the ring emptied, whole words straight to the member, the partial one opens the ring.  -> the bit position
+__device__ __forceinline__ uint32_t gzw_open_block(const GzCodebookDev& cb, uint32_t* dwords, uint32_t* ring, int lane) {
+    const uint32_t hdr_bits = cb.hdr_bits;
+    static_assert(GZW_RING == 2 * WAVE, "two ring words per lane");
+#pragma unroll
+    for (int r = 0; r < 2; ++r) ring[lane + WAVE * r] = 0;
+    for (uint32_t i = (uint32_t)lane; i < (hdr_bits >> 5); i += WAVE) dwords[i] = cb.hdr[i];
+    if (lane == 0 && (hdr_bits & 31u)) ring[0] = cb.hdr[hdr_bits >> 5] & ((1u << (hdr_bits & 31u)) - 1u);
+    return hdr_bits;
+}
+
+// the greedy parse: the lanes of this window a token starts at.  vmask = lanes inside the member, blen = the token a lane would
+// start (1: a literal), `skip` = bytes at the window's front that an earlier token covers (< 64), carried on to the next window.
+// A walk over the token starts with scalar steps; a window without a match takes none: every lane is a literal
+__device__ __forceinline__ unsigned long long gzw_parse(unsigned long long vmask, bool has_match, int blen, int& skip) {
+    unsigned long long marks;
+    int e = skip;
+    if (!has_match) {
+        marks = vmask & ~((1ull << skip) - 1ull);
+        e = 64;
+    } else {
+        marks = 0;
+        const int last = 64 - (int)__builtin_clzll(vmask | 1ull);        // one behind the last valid lane
+        while (e < last) {
+            marks |= 1ull << e;
+            e += __builtin_amdgcn_readlane(blen, e);
+        }
+        if (e < 64) e = 64;                                              // (the member ends inside this window)
+    }
+    skip = e - 64;
+    return marks;
+}
+
+// a lane's token in bits (tok: it has one): the literal `lit`, or length blen > 1 at distance dist; and the lane scan that places it
+struct GzwBits {
+    unsigned long long bits;     // LSB first
+    uint32_t nb;                 // how many (<= 48)
+    uint32_t inc, total;         // inclusive sum of nb over the lanes; the window's sum
+};
+__device__ __forceinline__ GzwBits gzw_token_bits(const uint32_t* lc, const uint32_t* dc, bool tok, uint32_t lit, int blen, int dist, int lane) {
+    GzwBits t{0, 0, 0, 0};
+    if (tok) {
+        if (blen == 1) {
+            const uint32_t a = lc[lit];
+            t.bits = a & 0xffffu; t.nb = a >> 16;
+        } else {
+            const int lsym = len_sym(blen), dsym = dist_sym(dist);
+            const uint32_t a = lc[257 + lsym], d = dc[dsym];
+            t.bits = a & 0xffffu; t.nb = a >> 16;
+            t.bits |= (unsigned long long)(uint32_t)(blen - len_base(lsym)) << t.nb; t.nb += (uint32_t)len_extra(lsym);
+            t.bits |= (unsigned long long)(d & 0xffffu) << t.nb; t.nb += d >> 16;
+            t.bits |= (unsigned long long)(uint32_t)(dist - dist_base(dsym)) << t.nb; t.nb += (uint32_t)dist_extra(dsym);
+        }
+    }
+    t.inc = wave_incl_sum_shfl(t.nb, lane);
+    t.total = (uint32_t)__builtin_amdgcn_readlane((int)t.inc, 63);
+    return t;
+}
+
+// the window's bits into the ring at bitpos (OR-ed: neighbours share words), whole words out to the member with one coalesced store
+// per lane, the open word to the ring's front; bitpos moves on.  t.total <= 64 x 48 bits = 96 words: the ring holds them
+__device__ __forceinline__ void gzw_ring_put(uint32_t* ring, uint32_t* dwords, uint32_t& bitpos, bool tok, const GzwBits& t, int lane) {
+    if (tok) {
+        const uint32_t at = bitpos + t.inc - t.nb;
+        const uint32_t wi = (at >> 5) - (bitpos >> 5), sh = at & 31u;
+        const unsigned long long lo = t.bits << sh;
+        atomicOr(&ring[wi], (uint32_t)lo);
+        if (sh + t.nb > 32u) atomicOr(&ring[wi + 1], (uint32_t)(lo >> 32));
+        if (sh + t.nb > 64u) atomicOr(&ring[wi + 2], (uint32_t)(t.bits >> (64u - sh)));
+    }
+    const uint32_t w0 = bitpos >> 5, w1 = (bitpos + t.total) >> 5, nfull = w1 - w0;
+    __builtin_amdgcn_s_waitcnt(0xc07f);                                  // lgkmcnt(0): the ring's atomics are done
+    uint32_t keep[2] = {0, 0};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const uint32_t j = (uint32_t)lane + 64u * (uint32_t)r;
+        keep[r] = ring[j];
+        if (j < nfull) dwords[w0 + j] = keep[r];
+    }
+    const uint32_t open = nfull < (uint32_t)GZW_RING ? (uint32_t)__builtin_amdgcn_readlane((int)keep[nfull >> 6], (int)(nfull & 63u)) : 0u;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) ring[(uint32_t)lane + 64u * (uint32_t)r] = 0;
+    if (lane == 0) ring[0] = open;
+    bitpos += t.total;
+}
+
+// behind the last window: end of block and the open word, unless the member is `stored` already; a stored block when that is no
+// larger.  -> bytes of deflate data
+__device__ __forceinline__ uint32_t gzw_close_block(const uint32_t* ring, const uint32_t* lc, uint8_t* mem, const uint8_t* text, uint32_t bitpos, int n, int lane, bool stored) {
+    uint32_t dbytes = 0;
+    if (!stored) {
+        uint32_t* const dwords = gz_member_data(mem);
+        const uint32_t eob = lc[256];
+        if (lane == 0) {
+            const uint32_t sh = bitpos & 31u;
+            const unsigned long long v = (unsigned long long)ring[0] | ((unsigned long long)(eob & 0xffffu) << sh);
+            dwords[bitpos >> 5] = (uint32_t)v;
+            if (sh + (eob >> 16) > 32u) dwords[(bitpos >> 5) + 1] = (uint32_t)(v >> 32);
+        }
+        bitpos += eob >> 16;
+        dbytes = (bitpos + 7u) >> 3;
+        stored = dbytes >= (uint32_t)n + 5u;
+    }
+    if (stored) {
+        dbytes = (uint32_t)n + 5u;
+        gz_store_member(mem, text, n, lane, WAVE);
+    }
+    return dbytes;
+}
+
+// CRC-32 register of the member's text[0, n): the member right-aligned in a grid of segments of GZ_SEG bytes, a lane takes 2^K0 of them
+// (gz_crc_segment), then the combine tree over the lanes from the operator "advance by 2^K0 x 255 bytes" (T.shift[K0]) on
+template <int K0>
+__device__ __forceinline__ uint32_t gzw_crc(const uint8_t* text, int n, const uint32_t* crc_tab, const GzCrcTables& T, int lane) {
+    constexpr int PER_LANE = GZ_SEG << K0;
+    const int pad = WAVE * PER_LANE - n;
+    uint32_t c = gz_crc_segment(crc_tab, text, max(0, lane * PER_LANE - pad), max(0, (lane + 1) * PER_LANE - pad));
+#pragma unroll 1
+    for (int k = 0; k < 6; ++k) {
+        const int step = 1 << k;
+        const uint32_t right = (uint32_t)__shfl_down((int)c, step);
+        if ((lane & (2 * step - 1)) == 0) {
+            const uint32_t* M = T.shift[k + K0];
+            uint32_t r = right;
+            for (int j = 0; j < 32; ++j) r ^= ((c >> j) & 1u) ? M[j] : 0u;
+            c = r;
+        }
+    }
+    return c;
+}
+
+// ---- gz_encode_kernel's tokens: a thread per 255-byte segment ------------------------------------------------------------------------
 struct GzSinkHist {
     uint32_t* h;     // LDS [320]
     __device__ __forceinline__ void lit(uint32_t b) { atomicAdd(&h[b], 1u); }
-    __device__ __forceinline__ void match(int len, int dist) { atomicAdd(&h[257 + gz_len_sym(len)], 1u); atomicAdd(&h[286 + gz_dist_sym(dist)], 1u); }
+    __device__ __forceinline__ void match(int len, int dist) { atomicAdd(&h[257 + len_sym(len)], 1u); atomicAdd(&h[286 + dist_sym(dist)], 1u); }
 };
 struct GzSinkSize {
     const uint32_t* lc; const uint32_t* dc;     // LDS codebook
     uint32_t bits = 0;
     __device__ __forceinline__ void lit(uint32_t b) { bits += lc[b] >> 16; }
     __device__ __forceinline__ void match(int len, int dist) {
-        const int ls = gz_len_sym(len), ds = gz_dist_sym(dist);
-        bits += (lc[257 + ls] >> 16) + gz_len_extra(ls) + (dc[ds] >> 16) + gz_dist_extra(ds);
+        const int ls = len_sym(len), ds = dist_sym(dist);
+        bits += (lc[257 + ls] >> 16) + len_extra(ls) + (dc[ds] >> 16) + dist_extra(ds);
     }
 };
 struct GzSinkEmit {
@@ -127,12 +329,12 @@ struct GzSinkEmit {
     __device__ __forceinline__ void put(uint32_t code, int len) { acc |= (unsigned long long)code << nacc; nacc += len; flush_words(); }
     __device__ __forceinline__ void lit(uint32_t b) { const uint32_t c = lc[b]; put(c & 0xffffu, (int)(c >> 16)); }
     __device__ __forceinline__ void match(int len, int dist) {
-        const int ls = gz_len_sym(len), ds = gz_dist_sym(dist);
+        const int ls = len_sym(len), ds = dist_sym(dist);
         const uint32_t a = lc[257 + ls], d = dc[ds];
         put(a & 0xffffu, (int)(a >> 16));
-        if (gz_len_extra(ls)) put((uint32_t)(len - gz_len_base(ls)), gz_len_extra(ls));
+        if (len_extra(ls)) put((uint32_t)(len - len_base(ls)), len_extra(ls));
         put(d & 0xffffu, (int)(d >> 16));
-        if (gz_dist_extra(ds)) put((uint32_t)(dist - gz_dist_base(ds)), gz_dist_extra(ds));
+        if (dist_extra(ds)) put((uint32_t)(dist - dist_base(ds)), dist_extra(ds));
     }
     __device__ __forceinline__ void finish() { if (nacc > 0) atomicOr(&out[w], (uint32_t)acc); }
 };
@@ -184,8 +386,8 @@ __device__ __forceinline__ void gz_tokenize(const uint8_t* s, int a, int b, int 
             if (r >= 3) {
                 int gain;
                 if (EXACT) {
-                    const int lsym = gz_len_sym(r);
-                    gain = r * (int)(lc[c0] >> 16) - (int)((lc[257 + lsym] >> 16) + gz_len_extra(lsym) + (dc[0] >> 16));
+                    const int lsym = len_sym(r);
+                    gain = r * (int)(lc[c0] >> 16) - (int)((lc[257 + lsym] >> 16) + len_extra(lsym) + (dc[0] >> 16));
                 } else gain = r >= 5 ? r : 0;
                 if (gain > best_gain) { best_gain = gain; best_len = r; best_dist = 1; }
             }
@@ -201,8 +403,8 @@ __device__ __forceinline__ void gz_tokenize(const uint8_t* s, int a, int b, int 
                 if (m >= 3) {
                     int gain;
                     if (EXACT) {
-                        const int lsym = gz_len_sym(m), dsym = gz_dist_sym(dist);
-                        gain = lit_bits - (int)((lc[257 + lsym] >> 16) + gz_len_extra(lsym) + (dc[dsym] >> 16) + gz_dist_extra(dsym));
+                        const int lsym = len_sym(m), dsym = dist_sym(dist);
+                        gain = lit_bits - (int)((lc[257 + lsym] >> 16) + len_extra(lsym) + (dc[dsym] >> 16) + dist_extra(dsym));
                     } else gain = m >= 6 ? m : 0;
                     if (gain > best_gain) { best_gain = gain; best_len = m; best_dist = dist; }
                 }
@@ -315,19 +517,11 @@ __device__ __forceinline__ void gz_stage_member(GzStage& S, const uint8_t* src, 
 }
 
 // ---- sampling pass: symbol counts of some members of every stream -------------------------------------------------------------
-constexpr int GZ_SAMPLES = 16;           // members sampled per stream (evenly spaced)
-
 __global__ __launch_bounds__(GZ_THREADS) void gz_hist_kernel(GzJob J) {
     __shared__ GzStage S;
     __shared__ uint32_t h[320];
-    // workgroup (q, k) samples member k * stride of stream q
-    const int q = blockIdx.x / GZ_SAMPLES, k = blockIdx.x % GZ_SAMPLES;
-    const uint32_t nb = (uint32_t)((J.bytes[q] + GZ_TEXT - 1) / GZ_TEXT);      // (its own pieces of GZ_TEXT bytes, whatever the encoder's members are)
-    const uint32_t stride = nb > GZ_SAMPLES ? nb / GZ_SAMPLES : 1u;
-    if ((uint32_t)k * stride >= nb) return;
-    const uint32_t local = (uint32_t)k * stride;
-    const uint64_t off = (uint64_t)local * GZ_TEXT;
-    const int n = (int)min<uint64_t>(GZ_TEXT, J.bytes[q] - off);
+    int q, n; uint64_t off;
+    if (!gz_sample_of(J, q, off, n)) return;
     for (int i = threadIdx.x; i < 320; i += GZ_THREADS) h[i] = 0;
     int a, b, line; bool use_lines;
     gz_stage_member(S, J.text[q] + off, n, a, b, line, use_lines);
@@ -345,14 +539,10 @@ __global__ __launch_bounds__(GZ_THREADS) void gz_encode_kernel(GzJob J) {
     __shared__ uint32_t crc_tab[256];
     __shared__ uint32_t crc_part[GZ_THREADS];
     const uint32_t member = blockIdx.x;
-    const int q = gz_stream_of(J, member);
-    const uint32_t local = member - J.first_block[q];
-    const uint64_t off = (uint64_t)local * GZ_TEXT;
-    const int n = (int)min<uint64_t>(GZ_TEXT, J.bytes[q] - off);
+    int q, n; uint64_t off;
+    gz_member_of(J, member, GZ_TEXT, q, off, n);
     const GzCodebookDev& cb = J.code[q];
-    for (int i = threadIdx.x; i < 286; i += GZ_THREADS) lc[i] = cb.lit[i];
-    if (threadIdx.x < 30) dc[threadIdx.x] = cb.dist[threadIdx.x];
-    crc_tab[threadIdx.x] = J.crc->byte_table[threadIdx.x];
+    gz_load_code<GZ_THREADS>(cb, J.crc->byte_table, lc, dc, crc_tab);
     int a, b, line; bool use_lines;
     gz_stage_member(S, J.text[q] + off, n, a, b, line, use_lines);
     // ---- sizes -> positions
@@ -367,8 +557,8 @@ __global__ __launch_bounds__(GZ_THREADS) void gz_encode_kernel(GzJob J) {
     uint32_t dbytes = (all_bits + 7) >> 3;
     const bool stored = dbytes >= (uint32_t)n + 5u;
     if (stored) dbytes = (uint32_t)n + 5u;
-    uint8_t* const mem = J.stage + (uint64_t)member * GZ_SLOT + 2;       // the member; its deflate data at +18 is 4-byte aligned
-    uint32_t* const dwords = reinterpret_cast<uint32_t*>(mem + 18);
+    uint8_t* const mem = gz_member_slot(J, member, GZ_SLOT);
+    uint32_t* const dwords = gz_member_data(mem);
     if (!stored) {
         const uint32_t nw = (all_bits + 31) >> 5;
         for (uint32_t i = threadIdx.x; i <= nw; i += GZ_THREADS) dwords[i] = 0;
@@ -385,23 +575,10 @@ __global__ __launch_bounds__(GZ_THREADS) void gz_encode_kernel(GzJob J) {
             if ((i + 1) * 32 <= hdr_bits) atomicOr(&dwords[i], v);         // (word 0 .. may be shared with nobody, OR is simply safe)
             else atomicOr(&dwords[i], v & ((1u << (hdr_bits & 31u)) - 1u));
         }
-    } else {
-        // incompressible with this code: one stored block (BFINAL = 1, BTYPE = 0, LEN, ~LEN, bytes)
-        if (threadIdx.x == 0) {
-            mem[18] = 1;
-            mem[19] = (uint8_t)n; mem[20] = (uint8_t)(n >> 8); mem[21] = (uint8_t)~n; mem[22] = (uint8_t)(~n >> 8);
-        }
-        for (int i = threadIdx.x; i < n; i += GZ_THREADS) mem[23 + i] = S.text[i];
-    }
-    // ---- CRC-32 of the member's text: raw CRCs of the 256 grid segments (the first four text bytes complemented), combined
+    } else gz_store_member(mem, S.text, n, (int)threadIdx.x, GZ_THREADS);
+    // ---- CRC-32 of the member's text: raw CRCs of the 256 grid segments, combined through LDS
     {
-        uint32_t c = 0;
-        for (int p = a; p < b; ++p) {
-            uint32_t x = S.text[p];
-            if (p < 4) x ^= 0xffu;                          // = starting the register at 0xffffffff, in a form leading zeros do not disturb
-            c = crc_tab[(c ^ x) & 0xffu] ^ (c >> 8);
-        }
-        crc_part[threadIdx.x] = c;
+        crc_part[threadIdx.x] = gz_crc_segment(crc_tab, S.text, a, b);
         __syncthreads();
 #pragma unroll 1
         for (int k = 0; k < 8; ++k) {
@@ -420,21 +597,9 @@ __global__ __launch_bounds__(GZ_THREADS) void gz_encode_kernel(GzJob J) {
         }
     }
     if (threadIdx.x == 0) {
-        uint32_t crc = ~crc_part[0];
-        if (n < 4) {
-            // (fewer than four bytes: the complement trick does not apply; do it the plain way)
-            uint32_t c = 0xffffffffu;
-            for (int p = 0; p < n; ++p) c = crc_tab[(c ^ S.text[p]) & 0xffu] ^ (c >> 8);
-            crc = ~c;
-        }
-        const uint32_t bsize = 18u + dbytes + 8u;
-        static const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-        for (int i = 0; i < 16; ++i) mem[i] = hdr[i];
-        mem[16] = (uint8_t)((bsize - 1) & 0xffu);
-        mem[17] = (uint8_t)((bsize - 1) >> 8);
-        uint8_t* t = mem + 18 + dbytes;
-        for (int k = 0; k < 4; ++k) { t[k] = (uint8_t)(crc >> (8 * k)); t[4 + k] = (uint8_t)((uint32_t)n >> (8 * k)); }
-        J.sizes[member] = bsize;
+        uint32_t c = crc_part[0];
+        if (n < 4) c = gz_crc_short(crc_tab, S.text, n);
+        J.sizes[member] = gz_frame_member(mem, dbytes, ~c, n);
     }
 }
 
@@ -482,11 +647,6 @@ __global__ __launch_bounds__(GZ_THREADS) void gz_pack_kernel(GzJob J) {
 //     to the member with one coalesced store per lane.  The wave writes its member front to back: no sizing pass.
 // Same format as before — BGZF-compatible members, ONE final dynamic block with the stream's shared code, stored when that is
 // smaller — with members a quarter the size: +~2.5 % bytes (header and code per 16 KB, no column match in a member's first record).
-constexpr int GZW_TEXT = 64 * 255;               // 16320 text bytes per member
-constexpr int GZW_SLOT = 16896;                  // staging bytes per member (its text stored + headers, and a window's worth of slack)
-constexpr int GZW_MAX_LINES = 512;
-constexpr int GZW_RING = 128;                    // staging words
-
 __device__ __forceinline__ int gzw_ctz64(unsigned long long x) { return x ? (int)__builtin_ctzll(x) : 64; }
 // ones of the masks M[0..5) from bit l of M[0] on, up to the first zero
 __device__ __forceinline__ int gzw_ones_from(const unsigned long long (&M)[5], int l) {
@@ -526,15 +686,10 @@ __global__ __launch_bounds__(WAVE) void gz_encode_wave_kernel(GzJob J) {
     __shared__ GzwStage S;
     const int lane = (int)threadIdx.x;
     const uint32_t member = blockIdx.x;
-    const int q = gz_stream_of(J, member);
-    const uint32_t local = member - J.first_block[q];
-    const uint64_t off = (uint64_t)local * GZW_TEXT;
-    const int n = (int)min<uint64_t>(GZW_TEXT, J.bytes[q] - off);
+    int q, n; uint64_t off;
+    gz_member_of(J, member, GZW_TEXT, q, off, n);
     const GzCodebookDev& cb = J.code[q];
-    for (int i = lane; i < 286; i += WAVE) S.lc[i] = cb.lit[i];
-    if (lane < 30) S.dc[lane] = cb.dist[lane];
-    for (int i = lane; i < 256; i += WAVE) S.crc_tab[i] = J.crc->byte_table[i];
-    for (int i = lane; i < GZW_RING; i += WAVE) S.ring[i] = 0;
+    gz_load_code<WAVE>(cb, J.crc->byte_table, S.lc, S.dc, S.crc_tab);
     {
         const uint8_t* src = J.text[q] + off;
         for (int i = lane * 16; i < n; i += WAVE * 16) *reinterpret_cast<uint4*>(S.text + i) = load16u(src + i);      // (64 readable bytes follow a stream)
@@ -543,15 +698,12 @@ __global__ __launch_bounds__(WAVE) void gz_encode_wave_kernel(GzJob J) {
     }
     if (lane == 0) S.ls[0] = 0;
     __syncthreads();
-    uint8_t* const mem = J.stage + (uint64_t)member * GZW_SLOT + 2;         // the member; its deflate data at +18 is 4-byte aligned
-    uint32_t* const dwords = reinterpret_cast<uint32_t*>(mem + 18);
-    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;     // bits of the lanes before this one
-    // ---- the block header: whole words straight to the member, the partial one opens the ring
-    const uint32_t hdr_bits = cb.hdr_bits;
-    uint32_t bitpos = hdr_bits;
-    for (uint32_t i = (uint32_t)lane; i < (hdr_bits >> 5); i += WAVE) dwords[i] = cb.hdr[i];
-    if (lane == 0 && (hdr_bits & 31u)) S.ring[0] = cb.hdr[hdr_bits >> 5] & ((1u << (hdr_bits & 31u)) - 1u);
-    const uint32_t limit_bits = ((uint32_t)n + 5u) * 8u;                      // beyond this a stored block is smaller
+    uint8_t* const mem = gz_member_slot(J, member, GZW_SLOT);
+    uint32_t* const dwords = gz_member_data(mem);
+    const unsigned long long lt = gzw_lanes_below(lane);
+    uint32_t bitpos = gzw_open_block(cb, dwords, S.ring, lane);
+    // beyond this a stored block is smaller; tested AFTER a window is written: GZW_SLOT has a window's worth of slack
+    const uint32_t limit_bits = ((uint32_t)n + 5u) * 8u;
     bool stored = false;
     // ---- masks of window f: what matches its predecessor byte, what matches the column four lines up, where lines end
     unsigned long long M1[5], Mc[5], NL[5];
@@ -595,8 +747,8 @@ __global__ __launch_bounds__(WAVE) void gz_encode_wave_kernel(GzJob J) {
                 const int r = min(gzw_ones_from(M1, lane), 258);
                 int best_gain = 0;
                 if (r >= 3) {
-                    const int lsym = gz_len_sym(r);
-                    const int gain = r * (int)lb - (int)((S.lc[257 + lsym] >> 16) + gz_len_extra(lsym) + (S.dc[0] >> 16));
+                    const int lsym = len_sym(r);
+                    const int gain = r * (int)lb - (int)((S.lc[257 + lsym] >> 16) + len_extra(lsym) + (S.dc[0] >> 16));
                     if (gain > 0) { best_gain = gain; blen = r; dist = 1; }
                 }
                 if (use_lines && ((Mc[0] >> lane) & 1ull)) {
@@ -604,75 +756,19 @@ __global__ __launch_bounds__(WAVE) void gz_encode_wave_kernel(GzJob J) {
                     if (m >= 3) {
                         const int line = line_cur + __popcll(NL[0] & lt);
                         const int d = (int)S.ls[line] - (int)S.ls[line - 4];
-                        const int lsym = gz_len_sym(m), dsym = gz_dist_sym(d);
+                        const int lsym = len_sym(m), dsym = dist_sym(d);
                         // (the literals' bits taken as the first one's: exact for the long matches of a name against the name before
                         //  it would need the window's prefix sums and four more windows' — the decision is not close there)
-                        const int gain = m * (int)max(lb, 5u) - (int)((S.lc[257 + lsym] >> 16) + gz_len_extra(lsym) + (S.dc[dsym] >> 16) + gz_dist_extra(dsym));
+                        const int gain = m * (int)max(lb, 5u) - (int)((S.lc[257 + lsym] >> 16) + len_extra(lsym) + (S.dc[dsym] >> 16) + dist_extra(dsym));
                         if (gain > best_gain) { best_gain = gain; blen = m; dist = d; }
                     }
                 }
             }
-            // ---- the greedy parse: token starts of this window
-            unsigned long long marks;
-            const unsigned long long vmask = __ballot(valid);
-            int e = skip;
-            if (__ballot(valid && blen > 1) == 0ull) {
-                marks = vmask & ~((1ull << skip) - 1ull);                   // literals all the way
-                e = 64;
-            } else {
-                marks = 0;
-                const int last = 64 - (int)__builtin_clzll(vmask | 1ull);    // one behind the last valid lane
-                while (e < last) {
-                    marks |= 1ull << e;
-                    e += __builtin_amdgcn_readlane(blen, e);
-                }
-                if (e < 64) e = 64;                                          // (the member ends inside this window)
-            }
-            skip = e - 64;
-            // ---- the tokens' bits
+            // ---- the greedy parse, the tokens' bits, the ring
+            const unsigned long long marks = gzw_parse(__ballot(valid), __ballot(valid && blen > 1) != 0ull, blen, skip);
             const bool tok = (marks >> lane) & 1ull;
-            unsigned long long bits = 0;
-            uint32_t nb = 0;
-            if (tok) {
-                if (blen == 1) {
-                    const uint32_t a = S.lc[c];
-                    bits = a & 0xffffu; nb = a >> 16;
-                } else {
-                    const int lsym = gz_len_sym(blen), dsym = gz_dist_sym(dist);
-                    const uint32_t a = S.lc[257 + lsym], d = S.dc[dsym];
-                    bits = a & 0xffffu; nb = a >> 16;
-                    const int xl = gz_len_extra(lsym);
-                    bits |= (unsigned long long)(uint32_t)(blen - gz_len_base(lsym)) << nb; nb += (uint32_t)xl;
-                    bits |= (unsigned long long)(d & 0xffffu) << nb; nb += d >> 16;
-                    const int xd = gz_dist_extra(dsym);
-                    bits |= (unsigned long long)(uint32_t)(dist - gz_dist_base(dsym)) << nb; nb += (uint32_t)xd;
-                }
-            }
-            const uint32_t inc = wave_incl_sum_shfl(nb, lane);
-            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-            if (tok) {
-                const uint32_t at = bitpos + inc - nb;
-                const uint32_t wi = (at >> 5) - (bitpos >> 5), sh = at & 31u;
-                const unsigned long long lo = bits << sh;
-                atomicOr(&S.ring[wi], (uint32_t)lo);
-                if (sh + nb > 32u) atomicOr(&S.ring[wi + 1], (uint32_t)(lo >> 32));
-                if (sh + nb > 64u) atomicOr(&S.ring[wi + 2], (uint32_t)(bits >> (64u - sh)));
-            }
-            // whole words leave the ring, the open one moves to its front
-            const uint32_t w0 = bitpos >> 5, w1 = (bitpos + total) >> 5, nfull = w1 - w0;
-            __builtin_amdgcn_s_waitcnt(0xc07f);                              // lgkmcnt(0): the ring's atomics are done
-            uint32_t keep[2] = {0, 0};
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const uint32_t j = (uint32_t)lane + 64u * (uint32_t)r;
-                keep[r] = S.ring[j];
-                if (j < nfull) dwords[w0 + j] = keep[r];
-            }
-            const uint32_t open = nfull < (uint32_t)GZW_RING ? (uint32_t)__builtin_amdgcn_readlane((int)keep[nfull >> 6], (int)(nfull & 63u)) : 0u;
-#pragma unroll
-            for (int r = 0; r < 2; ++r) S.ring[(uint32_t)lane + 64u * (uint32_t)r] = 0;
-            if (lane == 0) S.ring[0] = open;
-            bitpos += total;
+            const GzwBits t = gzw_token_bits(S.lc, S.dc, tok, c, blen, dist, lane);
+            gzw_ring_put(S.ring, dwords, bitpos, tok, t, lane);
             if (bitpos > limit_bits) stored = true;
         }
         // ---- the masks move on by a window
@@ -681,67 +777,12 @@ __global__ __launch_bounds__(WAVE) void gz_encode_wave_kernel(GzJob J) {
         for (int k = 0; k < 4; ++k) { M1[k] = M1[k + 1]; Mc[k] = Mc[k + 1]; NL[k] = NL[k + 1]; }
         far_masks(w + 5, M1[4], Mc[4], NL[4]);
     }
-    uint32_t dbytes;
-    if (!stored) {
-        // end of block, then the open word
-        const uint32_t eob = S.lc[256];
-        if (lane == 0) {
-            const uint32_t sh = bitpos & 31u;
-            const unsigned long long v = (unsigned long long)S.ring[0] | ((unsigned long long)(eob & 0xffffu) << sh);
-            dwords[bitpos >> 5] = (uint32_t)v;
-            if (sh + (eob >> 16) > 32u) dwords[(bitpos >> 5) + 1] = (uint32_t)(v >> 32);
-        }
-        bitpos += eob >> 16;
-        dbytes = (bitpos + 7u) >> 3;
-        stored = dbytes >= (uint32_t)n + 5u;
-    }
-    if (stored) {
-        // incompressible with this code: one stored block (BFINAL = 1, BTYPE = 0, LEN, ~LEN, bytes)
-        dbytes = (uint32_t)n + 5u;
-        if (lane == 0) {
-            mem[18] = 1;
-            mem[19] = (uint8_t)n; mem[20] = (uint8_t)(n >> 8); mem[21] = (uint8_t)~n; mem[22] = (uint8_t)(~n >> 8);
-        }
-        for (int i = lane; i < n; i += WAVE) mem[23 + i] = S.text[i];
-    }
-    // ---- CRC-32 of the member's text: raw CRCs of the 64 grid segments (the first four text bytes complemented), combined
-    uint32_t crc;
-    {
-        const int pad = GZW_TEXT - n;
-        const int a = max(0, lane * GZ_SEG - pad), b = max(0, (lane + 1) * GZ_SEG - pad);
-        uint32_t c = 0;
-        for (int p = a; p < b; ++p) {
-            uint32_t x = S.text[p];
-            if (p < 4) x ^= 0xffu;                          // = starting the register at 0xffffffff, in a form leading zeros do not disturb
-            c = S.crc_tab[(c ^ x) & 0xffu] ^ (c >> 8);
-        }
-#pragma unroll 1
-        for (int k = 0; k < 6; ++k) {
-            const int step = 1 << k;
-            const uint32_t right = (uint32_t)__shfl_down((int)c, step);
-            if ((lane & (2 * step - 1)) == 0) {
-                const uint32_t* M = J.crc->shift[k];
-                uint32_t r = right;
-                for (int j = 0; j < 32; ++j) r ^= ((c >> j) & 1u) ? M[j] : 0u;
-                c = r;
-            }
-        }
-        crc = ~c;
-    }
+    const uint32_t dbytes = gzw_close_block(S.ring, S.lc, mem, S.text, bitpos, n, lane, stored);
+    static_assert(GZW_TEXT == WAVE * GZ_SEG, "a segment of the CRC grid per lane");
+    uint32_t c = gzw_crc<0>(S.text, n, S.crc_tab, *J.crc, lane);
     if (lane == 0) {
-        if (n < 4) {
-            uint32_t c = 0xffffffffu;
-            for (int p = 0; p < n; ++p) c = S.crc_tab[(c ^ S.text[p]) & 0xffu] ^ (c >> 8);
-            crc = ~c;
-        }
-        const uint32_t bsize = 18u + dbytes + 8u;
-        static const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-        for (int i = 0; i < 16; ++i) mem[i] = hdr[i];
-        mem[16] = (uint8_t)((bsize - 1) & 0xffu);
-        mem[17] = (uint8_t)((bsize - 1) >> 8);
-        uint8_t* t = mem + 18 + dbytes;
-        for (int k = 0; k < 4; ++k) { t[k] = (uint8_t)(crc >> (8 * k)); t[4 + k] = (uint8_t)((uint32_t)n >> (8 * k)); }
-        J.sizes[member] = bsize;
+        if (n < 4) c = gz_crc_short(S.crc_tab, S.text, n);
+        J.sizes[member] = gz_frame_member(mem, dbytes, ~c, n);
     }
 }
 

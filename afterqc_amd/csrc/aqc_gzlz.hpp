@@ -21,11 +21,14 @@
 //            candidate >= the position, or at a distance > 32768.  The hash is taken only where p + 2 < n, a comparison never
 //            goes past min(258, n - p) bytes, no position before the member's first byte exists in the tables.
 //   tokens   per position the longest match (the nearest of equals; distance 1 is tried first, it has the cheapest code), taken
-//            when its code is shorter than the literals' it replaces by the actual code lengths (gzlz_take).  The greedy parse
-//            over a window's token starts, the lane scan of the bit lengths, the LDS ring and the coalesced word stores are
-//            gz_encode_wave_kernel's.  No lazy step.
+//            when its code is shorter than the literals' it replaces by the actual code lengths (gzlz_take).  No lazy step.
+//   calls    from aqc_gzdev.hpp, shared with gz_encode_wave_kernel: gz_member_of / gz_sample_of, gz_load_code, gzw_open_block,
+//            gzw_parse (the greedy parse over a window's token starts), gzw_token_bits (a token's bits and the lane scan of their
+//            lengths), gzw_ring_put (the LDS ring and the coalesced word stores), gzw_close_block (end of block or stored),
+//            gzw_crc<2>, gz_crc_short, gz_frame_member.  Its own: the tables, the search, and the stored test BEFORE a window is
+//            written.  The length / distance symbols: aqc_deflate_sym.hpp.
 //   sample   gz_hist_lz_kernel tokenises the same 16 pieces per stream as gz_hist_kernel, with this search and fixed thresholds
-//            (no code exists yet), into the same g_hist layout.
+//            (no code exists yet), into the same hist layout.
 //
 // gzlz_hash / gzlz_link / gzlz_search / gzlz_take are __host__ __device__: tests/native/gzlz_selftest.cpp includes this header
 // without HIP and deals them out by plain loops in the kernel's window order.
@@ -37,6 +40,7 @@
 #else
 #define GZLZ_HD inline
 #endif
+#include "aqc_deflate_sym.hpp"
 
 namespace aqc {
 
@@ -48,23 +52,6 @@ constexpr int GZLZ_WINDOW = 64;                  // positions inserted, then sea
 
 // candidates a position tries on its chain
 GZLZ_HD int gzlz_depth(int level) { return level <= 6 ? 8 : level == 7 ? 16 : level == 8 ? 32 : 64; }
-
-// length 3..258 -> length symbol - 257, distance 1..32768 -> distance symbol, their extra bits (RFC 1951 3.2.5, closed forms)
-GZLZ_HD int gzlz_len_sym(int len) {
-    if (len == 258) return 28;
-    if (len < 11) return len - 3;
-    const int v = len - 3, e = 31 - __builtin_clz((unsigned)v) - 2;
-    return 4 + 4 * e + ((v >> e) & 3);
-}
-GZLZ_HD int gzlz_dist_sym(int d) {
-    if (d < 5) return d - 1;
-    const int v = d - 1, e = 31 - __builtin_clz((unsigned)v) - 1;
-    return 2 + 2 * e + ((v >> e) & 1);
-}
-GZLZ_HD int gzlz_len_extra(int i) { return (i < 8 || i == 28) ? 0 : (i - 4) >> 2; }
-GZLZ_HD int gzlz_len_base(int i) { return i == 28 ? 258 : i < 8 ? 3 + i : 3 + ((4 + (i & 3)) << ((i - 4) >> 2)); }
-GZLZ_HD int gzlz_dist_extra(int i) { return i < 4 ? 0 : (i - 2) >> 1; }
-GZLZ_HD int gzlz_dist_base(int i) { return i < 4 ? 1 + i : 1 + ((2 + (i & 1)) << ((i - 2) >> 1)); }
 
 // hash of the three bytes at p; the caller guarantees p + 2 < n
 GZLZ_HD uint32_t gzlz_hash(const uint8_t* s, int p) {
@@ -118,8 +105,8 @@ template <bool EXACT>
 GZLZ_HD bool gzlz_take(const uint8_t* s, int p, GzlzMatch m, const uint32_t* lc, const uint32_t* dc) {
     if (m.len < GZLZ_MIN) return false;
     if (!EXACT) return m.len > GZLZ_MIN || m.dist <= 4096;
-    const int ls = gzlz_len_sym(m.len), ds = gzlz_dist_sym(m.dist);
-    const int cost = (int)(lc[257 + ls] >> 16) + gzlz_len_extra(ls) + (int)(dc[ds] >> 16) + gzlz_dist_extra(ds);
+    const int ls = len_sym(m.len), ds = dist_sym(m.dist);
+    const int cost = (int)(lc[257 + ls] >> 16) + len_extra(ls) + (int)(dc[ds] >> 16) + dist_extra(ds);
     int lit = 0;
     for (int i = 0; i < m.len && lit <= cost; ++i) lit += (int)(lc[s[p + i]] >> 16);
     return lit > cost;
@@ -194,41 +181,20 @@ __device__ __forceinline__ unsigned long long gzlz_window(GzlzStage& S, int n, i
         const GzlzMatch m = gzlz_search(S.text, n, p, S.prev, depth);
         if (gzlz_take<EXACT>(S.text, p, m, S.lc, S.dc)) { blen = m.len; dist = m.dist; }
     }
-    // the greedy parse: token starts of this window (gz_encode_wave_kernel's walk)
-    const unsigned long long vmask = __ballot(valid);
-    unsigned long long marks;
-    int e = skip;
-    if (__ballot(blen > 1) == 0ull) {
-        marks = vmask & ~((1ull << skip) - 1ull);
-        e = GZLZ_WINDOW;
-    } else {
-        marks = 0;
-        const int end = 64 - (int)__builtin_clzll(vmask | 1ull);          // one behind the last valid lane
-        while (e < end) {
-            marks |= 1ull << e;
-            e += __builtin_amdgcn_readlane(blen, e);
-        }
-        if (e < GZLZ_WINDOW) e = GZLZ_WINDOW;                             // (the member ends inside this window)
-    }
-    skip = e - GZLZ_WINDOW;
-    return marks;
+    // (every lane takes part in the ballot: one behind the member's end keeps blen 1)
+    return gzw_parse(__ballot(valid), __ballot(blen > 1) != 0ull, blen, skip);
 }
 
 // ---- sampling pass: symbol counts of some members of every stream, tokenised by the search ---------------------------------------
 __global__ __launch_bounds__(WAVE) void gz_hist_lz_kernel(GzJob J, int depth) {
     __shared__ GzlzStage S;
     const int lane = (int)threadIdx.x;
-    // workgroup (q, k) samples piece k * stride of stream q, as gz_hist_kernel does
-    const int q = blockIdx.x / GZ_SAMPLES, k = blockIdx.x % GZ_SAMPLES;
-    const uint32_t nb = (uint32_t)((J.bytes[q] + GZ_TEXT - 1) / GZ_TEXT);
-    const uint32_t stride = nb > GZ_SAMPLES ? nb / GZ_SAMPLES : 1u;
-    if ((uint32_t)k * stride >= nb) return;
-    const uint64_t off = (uint64_t)((uint32_t)k * stride) * GZ_TEXT;
-    const int n = (int)min<uint64_t>(GZ_TEXT, J.bytes[q] - off);
+    int q, n; uint64_t off;
+    if (!gz_sample_of(J, q, off, n)) return;
     for (int i = lane; i < 320; i += WAVE) S.hist[i] = 0;
     gzlz_stage_member(S, J.text[q] + off, n, lane);
     __syncthreads();
-    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+    const unsigned long long lt = gzw_lanes_below(lane);
     const int n_win = (n + GZLZ_WINDOW - 1) / GZLZ_WINDOW;
     int skip = 0;
     for (int w = 0; w < n_win; ++w) {
@@ -236,7 +202,7 @@ __global__ __launch_bounds__(WAVE) void gz_hist_lz_kernel(GzJob J, int depth) {
         const unsigned long long marks = gzlz_window<false>(S, n, w, lane, lt, depth, skip, blen, dist);
         if ((marks >> lane) & 1ull) {
             if (blen == 1) atomicAdd(&S.hist[S.text[GZLZ_WINDOW * w + lane]], 1u);
-            else { atomicAdd(&S.hist[257 + gzlz_len_sym(blen)], 1u); atomicAdd(&S.hist[286 + gzlz_dist_sym(dist)], 1u); }
+            else { atomicAdd(&S.hist[257 + len_sym(blen)], 1u); atomicAdd(&S.hist[286 + dist_sym(dist)], 1u); }
         }
     }
     __syncthreads();
@@ -249,28 +215,19 @@ __global__ __launch_bounds__(WAVE) void gz_encode_lz_kernel(GzJob J, int depth) 
     __shared__ GzlzStage S;
     const int lane = (int)threadIdx.x;
     const uint32_t member = blockIdx.x;
-    const int q = gz_stream_of(J, member);
-    const uint32_t local = member - J.first_block[q];
-    const uint64_t off = (uint64_t)local * GZ_TEXT;
-    const int n = (int)min<uint64_t>(GZ_TEXT, J.bytes[q] - off);
+    int q, n; uint64_t off;
+    gz_member_of(J, member, GZ_TEXT, q, off, n);
     const GzCodebookDev& cb = J.code[q];
-    for (int i = lane; i < 286; i += WAVE) S.lc[i] = cb.lit[i];
-    if (lane < 30) S.dc[lane] = cb.dist[lane];
-    for (int i = lane; i < 256; i += WAVE) S.crc_tab[i] = J.crc->byte_table[i];
-    for (int i = lane; i < GZW_RING; i += WAVE) S.ring[i] = 0;
+    gz_load_code<WAVE>(cb, J.crc->byte_table, S.lc, S.dc, S.crc_tab);
     gzlz_stage_member(S, J.text[q] + off, n, lane);
     __syncthreads();
-    uint8_t* const mem = J.stage + (uint64_t)member * GZ_SLOT + 2;          // the member; its deflate data at +18 is 4-byte aligned
-    uint32_t* const dwords = reinterpret_cast<uint32_t*>(mem + 18);
-    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;     // bits of the lanes before this one
-    // ---- the block header: whole words straight to the member, the partial one opens the ring
-    const uint32_t hdr_bits = cb.hdr_bits;
-    uint32_t bitpos = hdr_bits;
-    for (uint32_t i = (uint32_t)lane; i < (hdr_bits >> 5); i += WAVE) dwords[i] = cb.hdr[i];
-    if (lane == 0 && (hdr_bits & 31u)) S.ring[0] = cb.hdr[hdr_bits >> 5] & ((1u << (hdr_bits & 31u)) - 1u);
+    uint8_t* const mem = gz_member_slot(J, member, GZ_SLOT);
+    uint32_t* const dwords = gz_member_data(mem);
+    const unsigned long long lt = gzw_lanes_below(lane);
+    uint32_t bitpos = gzw_open_block(cb, dwords, S.ring, lane);
     __syncthreads();
-    // beyond this a stored block is smaller: the window that would cross the limit is not written, so the deflate data never
-    // passes n + 5 bytes (+ the end-of-block word) of the GZ_SLOT - 20 the slot has for data and trailer
+    // beyond this a stored block is smaller; tested BEFORE a window is written: the window that would cross the limit is not, so the
+    // deflate data never passes n + 5 bytes (+ the end-of-block word) of the GZ_SLOT - 20 the slot has for data and trailer
     const uint32_t limit_bits = ((uint32_t)n + 5u) * 8u;
     bool stored = false;
     const int n_win = (n + GZLZ_WINDOW - 1) / GZLZ_WINDOW;
@@ -279,112 +236,17 @@ __global__ __launch_bounds__(WAVE) void gz_encode_lz_kernel(GzJob J, int depth) 
         int blen, dist;
         const unsigned long long marks = gzlz_window<true>(S, n, w, lane, lt, depth, skip, blen, dist);
         if (marks == 0ull) continue;
-        // ---- the tokens' bits
         const bool tok = (marks >> lane) & 1ull;
-        unsigned long long bits = 0;
-        uint32_t nb = 0;
-        if (tok) {
-            if (blen == 1) {
-                const uint32_t a = S.lc[S.text[GZLZ_WINDOW * w + lane]];
-                bits = a & 0xffffu; nb = a >> 16;
-            } else {
-                const int lsym = gzlz_len_sym(blen), dsym = gzlz_dist_sym(dist);
-                const uint32_t a = S.lc[257 + lsym], d = S.dc[dsym];
-                bits = a & 0xffffu; nb = a >> 16;
-                bits |= (unsigned long long)(uint32_t)(blen - gzlz_len_base(lsym)) << nb; nb += (uint32_t)gzlz_len_extra(lsym);
-                bits |= (unsigned long long)(d & 0xffffu) << nb; nb += d >> 16;
-                bits |= (unsigned long long)(uint32_t)(dist - gzlz_dist_base(dsym)) << nb; nb += (uint32_t)gzlz_dist_extra(dsym);
-            }
-        }
-        const uint32_t inc = wave_incl_sum_shfl(nb, lane);
-        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-        if (bitpos + total > limit_bits) { stored = true; break; }           // (before a bit of this window is written)
-        if (tok) {
-            const uint32_t at = bitpos + inc - nb;
-            const uint32_t wi = (at >> 5) - (bitpos >> 5), sh = at & 31u;
-            const unsigned long long lo = bits << sh;
-            atomicOr(&S.ring[wi], (uint32_t)lo);
-            if (sh + nb > 32u) atomicOr(&S.ring[wi + 1], (uint32_t)(lo >> 32));
-            if (sh + nb > 64u) atomicOr(&S.ring[wi + 2], (uint32_t)(bits >> (64u - sh)));
-        }
-        // whole words leave the ring, the open one moves to its front
-        const uint32_t w0 = bitpos >> 5, w1 = (bitpos + total) >> 5, nfull = w1 - w0;
-        __builtin_amdgcn_s_waitcnt(0xc07f);                                  // lgkmcnt(0): the ring's atomics are done
-        uint32_t keep[2] = {0, 0};
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const uint32_t j = (uint32_t)lane + 64u * (uint32_t)r;
-            keep[r] = S.ring[j];
-            if (j < nfull) dwords[w0 + j] = keep[r];
-        }
-        const uint32_t open = nfull < (uint32_t)GZW_RING ? (uint32_t)__builtin_amdgcn_readlane((int)keep[nfull >> 6], (int)(nfull & 63u)) : 0u;
-#pragma unroll
-        for (int r = 0; r < 2; ++r) S.ring[(uint32_t)lane + 64u * (uint32_t)r] = 0;
-        if (lane == 0) S.ring[0] = open;
-        bitpos += total;
+        const GzwBits t = gzw_token_bits(S.lc, S.dc, tok, S.text[GZLZ_WINDOW * w + lane], blen, dist, lane);
+        if (bitpos + t.total > limit_bits) { stored = true; break; }
+        gzw_ring_put(S.ring, dwords, bitpos, tok, t, lane);
     }
-    uint32_t dbytes = 0;
-    if (!stored) {
-        // end of block, then the open word
-        const uint32_t eob = S.lc[256];
-        if (lane == 0) {
-            const uint32_t sh = bitpos & 31u;
-            const unsigned long long v = (unsigned long long)S.ring[0] | ((unsigned long long)(eob & 0xffffu) << sh);
-            dwords[bitpos >> 5] = (uint32_t)v;
-            if (sh + (eob >> 16) > 32u) dwords[(bitpos >> 5) + 1] = (uint32_t)(v >> 32);
-        }
-        bitpos += eob >> 16;
-        dbytes = (bitpos + 7u) >> 3;
-        stored = dbytes >= (uint32_t)n + 5u;
-    }
-    if (stored) {
-        // incompressible with this code: one stored block (BFINAL = 1, BTYPE = 0, LEN, ~LEN, bytes)
-        dbytes = (uint32_t)n + 5u;
-        if (lane == 0) {
-            mem[18] = 1;
-            mem[19] = (uint8_t)n; mem[20] = (uint8_t)(n >> 8); mem[21] = (uint8_t)~n; mem[22] = (uint8_t)(~n >> 8);
-        }
-        for (int i = lane; i < n; i += WAVE) mem[23 + i] = S.text[i];
-    }
-    // ---- CRC-32 of the member's text: a lane takes four of the 256 grid segments of 255 bytes (the member right-aligned in the
-    // grid, its first four bytes complemented: see gz_encode_kernel), then the combine tree from "advance by 4 x 255 bytes" on
-    uint32_t crc;
-    {
-        const int pad = GZ_TEXT - n;
-        const int a = max(0, lane * 4 * GZ_SEG - pad), b = max(0, (lane + 1) * 4 * GZ_SEG - pad);
-        uint32_t c = 0;
-        for (int p = a; p < b; ++p) {
-            uint32_t x = S.text[p];
-            if (p < 4) x ^= 0xffu;
-            c = S.crc_tab[(c ^ x) & 0xffu] ^ (c >> 8);
-        }
-#pragma unroll 1
-        for (int k = 0; k < 6; ++k) {
-            const int step = 1 << k;
-            const uint32_t right = (uint32_t)__shfl_down((int)c, step);
-            if ((lane & (2 * step - 1)) == 0) {
-                const uint32_t* M = J.crc->shift[k + 2];
-                uint32_t r = right;
-                for (int j = 0; j < 32; ++j) r ^= ((c >> j) & 1u) ? M[j] : 0u;
-                c = r;
-            }
-        }
-        crc = ~c;
-    }
+    const uint32_t dbytes = gzw_close_block(S.ring, S.lc, mem, S.text, bitpos, n, lane, stored);
+    static_assert(GZ_TEXT == WAVE * 4 * GZ_SEG, "four segments of the CRC grid per lane");
+    uint32_t c = gzw_crc<2>(S.text, n, S.crc_tab, *J.crc, lane);
     if (lane == 0) {
-        if (n < 4) {
-            uint32_t c = 0xffffffffu;
-            for (int p = 0; p < n; ++p) c = S.crc_tab[(c ^ S.text[p]) & 0xffu] ^ (c >> 8);
-            crc = ~c;
-        }
-        const uint32_t bsize = 18u + dbytes + 8u;
-        static const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-        for (int i = 0; i < 16; ++i) mem[i] = hdr[i];
-        mem[16] = (uint8_t)((bsize - 1) & 0xffu);
-        mem[17] = (uint8_t)((bsize - 1) >> 8);
-        uint8_t* t = mem + 18 + dbytes;
-        for (int k = 0; k < 4; ++k) { t[k] = (uint8_t)(crc >> (8 * k)); t[4 + k] = (uint8_t)((uint32_t)n >> (8 * k)); }
-        J.sizes[member] = bsize;
+        if (n < 4) c = gz_crc_short(S.crc_tab, S.text, n);
+        J.sizes[member] = gz_frame_member(mem, dbytes, ~c, n);
     }
 }
 

@@ -484,9 +484,9 @@ int main(int argc, char** argv) {
         static const uint16_t DB[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
         static const uint8_t DX[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
         for (uint32_t i = 0; i < 29; ++i)
-            if (gzb_len_base(i) != LB[i] || gzb_len_extra(i) != LX[i]) { printf("length symbol %u: base / extra wrong\n", i); return 1; }
+            if (len_base(i) != LB[i] || len_extra(i) != LX[i]) { printf("length symbol %u: base / extra wrong\n", i); return 1; }
         for (uint32_t i = 0; i < 30; ++i)
-            if (gzb_dist_base(i) != DB[i] || gzb_dist_extra(i) != DX[i]) { printf("distance symbol %u: base / extra wrong\n", i); return 1; }
+            if (dist_base(i) != DB[i] || dist_extra(i) != DX[i]) { printf("distance symbol %u: base / extra wrong\n", i); return 1; }
     }
     if (argc > 2) {
         const std::vector<uint8_t> gz = slurp(argv[1]), text = slurp(argv[2]);

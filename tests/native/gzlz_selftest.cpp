@@ -92,11 +92,11 @@ static void encode(const aqcgz::GzCodebook& cb, const uint8_t* s, const std::vec
     }
     for (const Tok& k : t) {
         if (k.len == 1) { b.put(cb.lit[s[k.pos]] & 0xffffu, (int)(cb.lit[s[k.pos]] >> 16)); continue; }
-        const int ls = gzlz_len_sym(k.len), ds = gzlz_dist_sym(k.dist);
+        const int ls = len_sym(k.len), ds = dist_sym(k.dist);
         b.put(cb.lit[257 + ls] & 0xffffu, (int)(cb.lit[257 + ls] >> 16));
-        b.put((uint32_t)(k.len - gzlz_len_base(ls)), gzlz_len_extra(ls));
+        b.put((uint32_t)(k.len - len_base(ls)), len_extra(ls));
         b.put(cb.dist[ds] & 0xffffu, (int)(cb.dist[ds] >> 16));
-        b.put((uint32_t)(k.dist - gzlz_dist_base(ds)), gzlz_dist_extra(ds));
+        b.put((uint32_t)(k.dist - dist_base(ds)), dist_extra(ds));
     }
     b.put(cb.lit[256] & 0xffffu, (int)(cb.lit[256] >> 16));
     b.finish();
@@ -119,12 +119,12 @@ int main(int argc, char** argv) {
     int checks = 0;
     // the closed forms against RFC 1951's tables, every length and distance
     for (int len = 3; len <= 258; ++len) {
-        const int ls = gzlz_len_sym(len);
-        CHECK(ls >= 0 && ls < 29 && len >= gzlz_len_base(ls) && len - gzlz_len_base(ls) < (1 << gzlz_len_extra(ls)), "length %d -> symbol %d", len, ls);
+        const int ls = len_sym(len);
+        CHECK(ls >= 0 && ls < 29 && len >= len_base(ls) && len - len_base(ls) < (1 << len_extra(ls)), "length %d -> symbol %d", len, ls);
     }
     for (int d = 1; d <= 32768; ++d) {
-        const int ds = gzlz_dist_sym(d);
-        CHECK(ds >= 0 && ds < 30 && d >= gzlz_dist_base(ds) && d - gzlz_dist_base(ds) < (1 << gzlz_dist_extra(ds)), "distance %d -> symbol %d", d, ds);
+        const int ds = dist_sym(d);
+        CHECK(ds >= 0 && ds < 30 && d >= dist_base(ds) && d - dist_base(ds) < (1 << dist_extra(ds)), "distance %d -> symbol %d", d, ds);
     }
     int last_depth = 0;
     for (int level = 6; level <= 9; ++level) {
@@ -153,7 +153,7 @@ int main(int argc, char** argv) {
                 check_tokens(argv[a], level, (int)k, members[k].data(), (int)members[k].size(), t);
                 for (const Tok& x : t) {
                     if (x.len == 1) hist[members[k][x.pos]]++;
-                    else { hist[257 + gzlz_len_sym(x.len)]++; hist[286 + gzlz_dist_sym(x.dist)]++; }
+                    else { hist[257 + len_sym(x.len)]++; hist[286 + dist_sym(x.dist)]++; }
                 }
             }
             aqcgz::GzCodebook cb;

@@ -2,6 +2,9 @@
 """What `--compression 6 .. 9` costs and gains on the device (csrc/aqc_gzlz.hpp), measured; needs a GPU.
 
   python tools/gz_levels.py sizes                      # tests/golden/testdata: device bytes at levels 2, 6 - 9 beside zlib's members
+  python tools/gz_levels.py digest                     # SHA-256 of the .gz bytes of five texts at levels 2, 6, 9 and at 2 with
+                                                       # AQC_GZ_ENCODER=seg: the encoders are deterministic, so two builds that
+                                                       # encode alike print the same lines
   python tools/gz_levels.py compress --pairs 131072    # aqc_compress per chunk (text resident in HBM) at levels 2, 6, 9
   python tools/gz_levels.py pipe --pairs 500000        # plain -> .gz through the pipe at levels 6 and 9: the device against the host
                                                        # codec at the same level (AQC_GZ_DEVICE=0), interleaved, a fresh process each
@@ -9,6 +12,7 @@
 Every mode prints `gzlevels|` lines."""
 import argparse
 import gzip
+import hashlib
 import json
 import os
 import subprocess
@@ -44,6 +48,17 @@ def zlib_members(text, level):
     return total
 
 
+def formatted(eng, capi, text):
+    """a single-end text whose records all pass, formatted in slot 0: stream 0 is the text itself"""
+    eng.set_config(pass_all(capi, False))
+    eng.set_circles([])
+    eng.reset_stats()
+    info = eng.frame(0, pad(text), len(text), True)
+    eng.run(0)
+    got = eng.format(0, int(info.n))
+    assert got[0] == len(text), got
+
+
 def sizes(args):
     from afterqc_amd import capi
     eng = capi.Engine(0, 1)
@@ -51,18 +66,42 @@ def sizes(args):
         for mate in (1, 2):
             with gzip.open(os.path.join(ROOT, "tests", "golden", "testdata", "R%d.fq.gz" % mate), "rb") as f:
                 text = f.read()
-            eng.set_config(pass_all(capi, False))
-            eng.set_circles([])
-            eng.reset_stats()
-            info = eng.frame(0, pad(text), len(text), True)
-            eng.run(0)
-            got = eng.format(0, int(info.n))
-            assert got[0] == len(text), got
+            formatted(eng, capi, text)
             dev = {level: eng.compress(0, level)[0] for level in (2, 6, 7, 8, 9)}
             ref = {level: zlib_members(text, level) for level in (2, 3, 4, 6, 9)}
             print("gzlevels| sizes R%d text %d  device %s  zlib members of 0xff00 %s" % (mate, len(text), json.dumps(dev), json.dumps(ref)))
     finally:
         eng.close()
+
+
+def digest(args):
+    """tests/gzlz_cases.py's real reads and far_repeats, test_gpu_gzlz.py's stored_fallback text, one residue just above a member"""
+    from afterqc_amd import capi
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import gzlz_cases as cases
+    seg = args.mode == "digest-seg"
+    stored = cases.exact(np.random.default_rng(7950), 16 * MEMBER) + cases.noise_text(2 * MEMBER - 300)
+    texts = [("real_R1", cases.real(1)), ("real_R2", cases.real(2)), ("far_repeats", cases.far_repeats()), ("stored_fallback", stored),
+             ("residue_%d" % (MEMBER + 1), cases.exact(np.random.default_rng(7900 + (MEMBER + 1) % 89), MEMBER + 1))]
+    eng = capi.Engine(0, 1)
+    try:
+        for name, text in texts:
+            formatted(eng, capi, text)
+            for level in ((2,) if seg else (2, 6, 9)):
+                for q, zb in enumerate(eng.compress(0, level)):
+                    if zb:
+                        comp = np.zeros(zb + 64, dtype=np.uint8)
+                        eng.fetch_gz(0, q // 3, q % 3, comp, comp.size)
+                        print("gzlevels| digest %-16s level %d%s stream %d: text %8d  gz %8d  sha256 %s" % (
+                            name, level, " seg" if seg else "", q, len(text), zb, hashlib.sha256(comp[:zb].tobytes()).hexdigest()))
+    finally:
+        eng.close()
+    if seg:
+        return 0
+    sys.stdout.flush()
+    # the seg encoder is chosen when the library first compresses: a fresh process
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "digest-seg"], env=dict(os.environ, AQC_GZ_ENCODER="seg"), timeout=300)
+    return p.returncode
 
 
 def compress(args):
@@ -140,13 +179,13 @@ def pipe(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["sizes", "compress", "pipe", "pipe-child"])
+    ap.add_argument("mode", choices=["sizes", "digest", "digest-seg", "compress", "pipe", "pipe-child"])
     ap.add_argument("--pairs", type=int, default=131072)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--level", type=int, default=9)
     ap.add_argument("--dir", default="/tmp/aqc_gz_levels")
     args = ap.parse_args()
-    return {"sizes": sizes, "compress": compress, "pipe": pipe, "pipe-child": pipe_child}[args.mode](args) or 0
+    return {"sizes": sizes, "digest": digest, "digest-seg": digest, "compress": compress, "pipe": pipe, "pipe-child": pipe_child}[args.mode](args) or 0
 
 
 if __name__ == "__main__":
