@@ -87,6 +87,51 @@ static int up_offsets(Slot& s, DevBuf& d, const uint64_t* src, uint64_t n) {
     return 0;
 }
 
+// One mate of a batch up to the device, in this order on the stream: arena, quality arena, 32-bit offsets, quality offsets, lengths.
+// What is left in `mv` is the mate as the kernels see it.  `qual == seq` (one arena holds both strings): the view aliases, nothing more
+// goes up.  The caller says how long the quality arena is, and how many readable bytes the arena needs in front (see up()).
+struct MateSrc { const uint8_t *seq, *qual; const uint64_t *off, *qoff; const uint32_t* len; uint64_t bytes, qbytes; };
+static int upload_mate(Slot& s, int k, const MateSrc& b, uint64_t n, bool need_qual, size_t front, MateView& mv) {
+    Mate& m = s.m[k];
+    int rc;
+    if ((rc = up(m.seq, b.seq, b.bytes, s.stream, front))) return rc;
+    mv.seq = (const uint8_t*)m.seq.p + front;
+    if (b.qual && need_qual) {
+        if (b.qual == b.seq) mv.qual = mv.seq;
+        else {
+            if ((rc = up(m.qual, b.qual, b.qbytes, s.stream))) return rc;
+            mv.qual = (const uint8_t*)m.qual.p;
+        }
+    } else if (need_qual) return fail(AQC_ERR_ARG, "batch: qual%d is required", k + 1);
+    if ((rc = up_offsets(s, m.off, b.off, n))) return rc;
+    mv.off = (const uint32_t*)m.off.p;
+    if (b.qoff) {
+        if ((rc = up_offsets(s, m.qoff, b.qoff, n))) return rc;
+        mv.qoff = (const uint32_t*)m.qoff.p;
+    }
+    if ((rc = up(m.len, b.len, sizeof(uint32_t) * n, s.stream))) return rc;
+    mv.len = (const uint32_t*)m.len.p;
+    return 0;
+}
+
+// quality strings with lengths of their own: the mates that differ are marked in the device copy of their length words
+static int upload_quality_lengths(Slot& s, const aqc_batch* b, uint64_t n, int nm, MateView mv[2]) {
+    if (nm == 2 && !b->qlen2) return fail(AQC_ERR_ARG, "batch: qlen1 without qlen2");
+    const uint32_t* ql[2] = {b->qlen1, b->qlen2};
+    for (int k = 0; k < nm; ++k) {
+        Mate& m = s.m[k];
+        const int rc = up(m.qlen, ql[k], sizeof(uint32_t) * n, s.stream);
+        if (rc) return rc;
+        if (m.qview.reserve(sizeof(uint32_t) * (n ? n : 1))) return fail(AQC_ERR_HIP, "hipMalloc failed");
+        if (n) hipLaunchKernelGGL(mark_irregular_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream, (uint32_t*)m.len.p,
+                                  (const uint32_t*)m.qlen.p, n);
+        mv[k].qlen = (const uint32_t*)m.qlen.p;
+        mv[k].qview = (uint32_t*)m.qview.p;
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 static int fill_slot(aqc_ctx* c, Slot& s, const aqc_batch* b, bool need_qual, bool need_pair) {
     const uint64_t n = b->n;
     if (!b->seq1 || !b->off1 || !b->len1) return fail(AQC_ERR_ARG, "batch: seq1/off1/len1 are required");
@@ -99,45 +144,14 @@ static int fill_slot(aqc_ctx* c, Slot& s, const aqc_batch* b, bool need_qual, bo
     // make sure earlier work on this slot has drained before its buffers are overwritten / regrown
     HIP_TRY(slot_sync(s));
     int rc;
+    const int nm = paired ? 2 : 1;
+    MateView mv[2] = {};
+    // a quality arena without a size of its own is as long as the sequences'; read 2 alone gets TEXT_FRONT bytes in front of its arena
+    if ((rc = upload_mate(s, 0, MateSrc{b->seq1, b->qual1, b->off1, b->qoff1, b->len1, b->bytes1, b->qbytes1 ? b->qbytes1 : b->bytes1}, n, need_qual, 0, mv[0]))) return rc;
+    if (paired && (rc = upload_mate(s, 1, MateSrc{b->seq2, b->qual2, b->off2, b->qoff2, b->len2, b->bytes2, b->qbytes2 ? b->qbytes2 : b->bytes2}, n, need_qual, TEXT_FRONT, mv[1]))) return rc;
     DevBatch v{};
     v.n = n;
     v.first_index = b->first_index;
-    if ((rc = up(s.seq1, b->seq1, b->bytes1, s.stream))) return rc;
-    v.seq1 = (const uint8_t*)s.seq1.p;
-    if (b->qual1 && need_qual) {
-        if (b->qual1 == b->seq1) v.qual1 = v.seq1;
-        else {
-            if ((rc = up(s.qual1, b->qual1, b->qbytes1 ? b->qbytes1 : b->bytes1, s.stream))) return rc;
-            v.qual1 = (const uint8_t*)s.qual1.p;
-        }
-    } else if (need_qual) return fail(AQC_ERR_ARG, "batch: qual1 is required");
-    if ((rc = up_offsets(s, s.off1, b->off1, n))) return rc;
-    v.off1 = (const uint32_t*)s.off1.p;
-    if (b->qoff1) {
-        if ((rc = up_offsets(s, s.qoff1, b->qoff1, n))) return rc;
-        v.qoff1 = (const uint32_t*)s.qoff1.p;
-    }
-    if ((rc = up(s.len1, b->len1, sizeof(uint32_t) * n, s.stream))) return rc;
-    v.len1 = (const uint32_t*)s.len1.p;
-    if (paired) {
-        if ((rc = up(s.seq2, b->seq2, b->bytes2, s.stream, TEXT_FRONT))) return rc;
-        v.seq2 = (const uint8_t*)s.seq2.p + TEXT_FRONT;
-        if (b->qual2 && need_qual) {
-            if (b->qual2 == b->seq2) v.qual2 = v.seq2;
-            else {
-                if ((rc = up(s.qual2, b->qual2, b->qbytes2 ? b->qbytes2 : b->bytes2, s.stream))) return rc;
-                v.qual2 = (const uint8_t*)s.qual2.p;
-            }
-        } else if (need_qual) return fail(AQC_ERR_ARG, "batch: qual2 is required");
-        if ((rc = up_offsets(s, s.off2, b->off2, n))) return rc;
-        v.off2 = (const uint32_t*)s.off2.p;
-        if (b->qoff2) {
-            if ((rc = up_offsets(s, s.qoff2, b->qoff2, n))) return rc;
-            v.qoff2 = (const uint32_t*)s.qoff2.p;
-        }
-        if ((rc = up(s.len2, b->len2, sizeof(uint32_t) * n, s.stream))) return rc;
-        v.len2 = (const uint32_t*)s.len2.p;
-    }
     if (b->aux_ok && b->aux_lane && b->aux_tile && b->aux_x && b->aux_y) {
         const void* src[5] = {b->aux_lane, b->aux_tile, b->aux_x, b->aux_y, b->aux_ok};
         for (int k = 0; k < 5; k++)
@@ -150,22 +164,8 @@ static int fill_slot(aqc_ctx* c, Slot& s, const aqc_batch* b, bool need_qual, bo
     }
     if (s.results.reserve(sizeof(aqc_result) * (n ? n : 1))) return fail(AQC_ERR_HIP, "hipMalloc failed");
     s.has_irregular = b->qlen1 != nullptr && need_qual;
-    if (b->qlen1 && need_qual) {
-        // quality strings with lengths of their own: the mates that differ are marked in the device copy of their length words
-        if (paired && !b->qlen2) return fail(AQC_ERR_ARG, "batch: qlen1 without qlen2");
-        const uint32_t* ql[2] = {b->qlen1, b->qlen2};
-        DevBuf* lens[2] = {&s.len1, &s.len2};
-        for (int k = 0; k < (paired ? 2 : 1); ++k) {
-            if ((rc = up(s.qlen[k], ql[k], sizeof(uint32_t) * n, s.stream))) return rc;
-            if (s.qview[k].reserve(sizeof(uint32_t) * (n ? n : 1))) return fail(AQC_ERR_HIP, "hipMalloc failed");
-            if (n) hipLaunchKernelGGL(mark_irregular_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream, (uint32_t*)lens[k]->p,
-                                      (const uint32_t*)s.qlen[k].p, n);
-        }
-        HIP_TRY(hipGetLastError());
-        v.qlen1 = (const uint32_t*)s.qlen[0].p; v.qview1 = (uint32_t*)s.qview[0].p;
-        if (paired) { v.qlen2 = (const uint32_t*)s.qlen[1].p; v.qview2 = (uint32_t*)s.qview[1].p; }
-        else { v.qlen2 = v.qlen1; v.qview2 = v.qview1; }
-    }
+    if (s.has_irregular && (rc = upload_quality_lengths(s, b, n, nm, mv))) return rc;
+    for (int k = 0; k < nm; ++k) set_mate(v, k, mv[k]);
     uint32_t mx = 0;
     for (uint64_t i = 0; i < n; i++) {
         if (b->len1[i] > mx) mx = b->len1[i];
@@ -201,6 +201,49 @@ static int grid_for(const aqc_ctx* c, uint64_t n) {
     return (int)blocks;
 }
 
+// What aqc_run launches for the slot's records: the general wave-per-record kernel, or the lane-per-pair kernel whenever its
+// preconditions hold: one of its three tiers by the longest read, or its fused instance.
+enum class Verdict { GENERAL, TIER10, TIER16, TIER18, FUSED };
+static Verdict choose_verdict_kernel(const aqc_ctx* c, const Slot& s, const aqc_config& cfg) {
+    const int thr = cfg.qualified_quality_phred + 33;
+    // barcodes on that kernel: detectBarcode's three windows must lie in the first 32 bases and the verify sequence must
+    // be plain A/C/G/T (2-bit codes); anything else takes the general kernel
+    bool barcode_ok = true;
+    if (cfg.barcode) {
+        barcode_ok = cfg.barcode_verify_len >= 1 && cfg.barcode_length + 1 + cfg.barcode_verify_len <= 31;
+        for (int j = 0; j < cfg.barcode_verify_len && barcode_ok; ++j) {
+            const uint8_t ch = cfg.barcode_verify[j];
+            barcode_ok = ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T';
+        }
+    }
+    if (c->force_generic || !barcode_ok || thr < 0 || thr > 127 || s.max_len > 288 || s.max_len == 0) return Verdict::GENERAL;
+    // AQC_FUSED=1: pairs of device-framed text whose records are plain four-line text are placed in their output
+    // streams by the verdict kernel itself, which also copies the good records that go out as their own bytes
+    // (31-bit stream offsets; a bad record grows by its flag text)
+    if (c->fuse_opt && s.framed && cfg.paired && !cfg.barcode && s.max_len <= 160 && !s.has_irregular && s.m[0].consumed + 16 * s.n < (1ull << 31) &&
+        s.m[1].consumed + 16 * s.n < (1ull << 31))
+        return Verdict::FUSED;
+    // (TIER18, 257 .. 288 bases: 2x250 reads that still carry a barcode + verify prefix (BASELINE config 5: 267 bases))
+    return s.max_len <= 160 ? Verdict::TIER10 : s.max_len <= 256 ? Verdict::TIER16 : Verdict::TIER18;
+}
+
+// the fused placement's buffers: look-back words per batch, position words per record, ticket | abort | totals, the two good streams
+static int prepare_fuse(Slot& s, FuseArgs& fz) {
+    constexpr uint64_t PPW = FastWaveLds<10, true, true>::PPW;
+    const uint64_t n_batches = (s.n + PPW - 1) / PPW;
+    if (s.fz_state.reserve(16 * n_batches) || s.m[0].fz_rec.reserve(4 * s.n) || s.m[1].fz_rec.reserve(4 * s.n) || s.fz_misc.reserve(64) ||
+        s.f_out[0].reserve(s.m[0].consumed + 64) || s.f_out[3].reserve(s.m[1].consumed + 64))
+        return fail(AQC_ERR_HIP, "hipMalloc failed");
+    HIP_TRY(hipMemsetAsync(s.fz_state.p, 0, 16 * n_batches, s.stream));
+    HIP_TRY(hipMemsetAsync(s.fz_misc.p, 0, 64, s.stream));
+    fz.name_off1 = (const uint32_t*)s.m[0].name_off.p; fz.name_off2 = (const uint32_t*)s.m[1].name_off.p;
+    fz.out1 = (uint8_t*)s.f_out[0].p; fz.out2 = (uint8_t*)s.f_out[3].p;
+    fz.fstate1 = (uint32_t*)s.m[0].fz_rec.p; fz.fstate2 = (uint32_t*)s.m[1].fz_rec.p;
+    fz.state = (unsigned long long*)s.fz_state.p;
+    fz.ticket = (unsigned int*)s.fz_misc.p; fz.abort = (int*)s.fz_misc.p + 1; fz.totals = (unsigned long long*)s.fz_misc.p + 1;
+    return 0;
+}
+
 int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
     GET_SLOT(s);
     if (!c->has_cfg) return fail(AQC_ERR_STATE, "aqc_run before aqc_set_config");
@@ -214,53 +257,23 @@ int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
     s->err_record = UINT64_MAX;
     if (s->qc.pending()) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_qc, 0));      // (statRead of the previous run still reads the results)
     HIP_TRY(hipEventRecord(launch_event(*s, AQC_K_FILTER_OVERLAP, 0), s->stream));
-    // lane-per-pair kernel whenever its preconditions hold; the general wave-per-record kernel otherwise
-    const int thr = cfg.qualified_quality_phred + 33;
-    // barcodes on that kernel: detectBarcode's three windows must lie in the first 32 bases and the verify sequence must
-    // be plain A/C/G/T (2-bit codes); anything else takes the general kernel
-    bool barcode_ok = true;
-    if (cfg.barcode) {
-        barcode_ok = cfg.barcode_verify_len >= 1 && cfg.barcode_length + 1 + cfg.barcode_verify_len <= 31;
-        for (int j = 0; j < cfg.barcode_verify_len && barcode_ok; ++j) {
-            const uint8_t ch = cfg.barcode_verify[j];
-            barcode_ok = ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T';
-        }
-    }
-    const bool fast_ok = !c->force_generic && barcode_ok && thr >= 0 && thr <= 127 && s->max_len <= 288 && s->max_len > 0;
-    s->used_fast = fast_ok;
-    if (!fast_ok) {
+    const Verdict k = choose_verdict_kernel(c, *s, cfg);
+    s->used_fast = k != Verdict::GENERAL;
+    if (k == Verdict::GENERAL) {
         hipLaunchKernelGGL(filter_overlap_kernel, dim3(grid_for(c, s->n)), dim3(BLOCK), 0, s->stream, s->view, cfg, c->circles,
                            (aqc_result*)s->results.p, st, accum_limit);
     } else {
         if (s->deferred.reserve(sizeof(uint32_t) * (s->n + 1)) || s->n_deferred.reserve(sizeof(unsigned int)))
             return fail(AQC_ERR_HIP, "hipMalloc failed");
-        // AQC_FUSED=1: pairs of device-framed text whose records are plain four-line text are placed in their output
-        // streams by the verdict kernel itself, which also copies the good records that go out as their own bytes
-        const bool fuse_ok = c->fuse_opt && s->framed && cfg.paired && !cfg.barcode && s->max_len <= 160 && !s->has_irregular && s->consumed[0] + 16 * s->n < (1ull << 31) && s->consumed[1] + 16 * s->n < (1ull << 31);      // (31-bit stream offsets; a bad record grows by its flag text)
-        if (fuse_ok) {
-            constexpr uint64_t PPW = FastWaveLds<10, true, true>::PPW;
-            const uint64_t n_batches = (s->n + PPW - 1) / PPW;
-            if (s->fz_state.reserve(16 * n_batches) || s->fz_rec[0].reserve(4 * s->n) || s->fz_rec[1].reserve(4 * s->n) || s->fz_misc.reserve(64) ||
-                s->f_out[0].reserve(s->consumed[0] + 64) || s->f_out[3].reserve(s->consumed[1] + 64))
-                return fail(AQC_ERR_HIP, "hipMalloc failed");
-            HIP_TRY(hipMemsetAsync(s->fz_state.p, 0, 16 * n_batches, s->stream));
-            HIP_TRY(hipMemsetAsync(s->fz_misc.p, 0, 64, s->stream));
+        if (k == Verdict::FUSED) {
             FuseArgs fz{};
-            fz.name_off1 = (const uint32_t*)s->t_name_off[0].p; fz.name_off2 = (const uint32_t*)s->t_name_off[1].p;
-            fz.out1 = (uint8_t*)s->f_out[0].p; fz.out2 = (uint8_t*)s->f_out[3].p;
-            fz.fstate1 = (uint32_t*)s->fz_rec[0].p; fz.fstate2 = (uint32_t*)s->fz_rec[1].p;
-            fz.state = (unsigned long long*)s->fz_state.p;
-            fz.ticket = (unsigned int*)s->fz_misc.p; fz.abort = (int*)s->fz_misc.p + 1; fz.totals = (unsigned long long*)s->fz_misc.p + 1;
+            const int rc = prepare_fuse(*s, fz);
+            if (rc) return rc;
             launch_fast<10, true, FUSE_WPBT, false, true>(c, s, cfg, st, accum_limit, &fz);
             s->fused = true;
-        } else if (s->max_len <= 160) {
-            launch_fast_tier<10, 16, 12>(c, s, cfg, st, accum_limit);
-        } else if (s->max_len <= 256) {
-            launch_fast_tier<16, 12, 11>(c, s, cfg, st, accum_limit);
-        } else {
-            // 257 .. 288 bases: 2x250 reads that still carry a barcode + verify prefix (BASELINE config 5: 267 bases)
-            launch_fast_tier<18, 12, 10>(c, s, cfg, st, accum_limit);
-        }
+        } else if (k == Verdict::TIER10) launch_fast_tier<10, 16, 12>(c, s, cfg, st, accum_limit);
+        else if (k == Verdict::TIER16) launch_fast_tier<16, 12, 11>(c, s, cfg, st, accum_limit);
+        else launch_fast_tier<18, 12, 10>(c, s, cfg, st, accum_limit);
         hipLaunchKernelGGL(filter_overlap_list_kernel, dim3((unsigned)c->n_cu), dim3(BLOCK), 0, s->stream, s->view, cfg, c->circles,
                            (aqc_result*)s->results.p, st, accum_limit, (const uint32_t*)s->deferred.p,
                            (const unsigned int*)s->n_deferred.p);

@@ -13,6 +13,7 @@
 // of it is instantiated in this unit).
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
@@ -29,177 +30,214 @@ using namespace aqc;
 
 extern "C" {
 
+// t_scratch, one per slot: what the framing kernels and the formatter's sizing pass leave for each other and for the host.  aqc_frame
+// and aqc_format take turns on the slot's stream, so the FrameOut and the stream totals share their place.
+struct TextScratch {
+    alignas(64) FrameMeta meta[2];
+    alignas(64) unsigned long long lines[2];       // '\n' per file (text_index_kernel)
+    union alignas(64) { FrameOut frame; unsigned long long fmt_totals[FMT_STREAMS]; };
+};
+constexpr size_t TEXT_SCRATCH_BYTES = 256;
+static_assert(offsetof(TextScratch, lines) == 64 && offsetof(TextScratch, frame) == 128 && offsetof(TextScratch, fmt_totals) == 128 &&
+              sizeof(TextScratch) <= TEXT_SCRATCH_BYTES, "the kernels of both stages were measured with these places");
+
 // ---- text in -----------------------------------------------------------------------------------------------------
 struct FrameExtents { const aqc_text_extent* ext[2]; uint64_t n[2]; uint8_t last[2]; };
-static int frame_impl(aqc_ctx* c, int slot, const aqc_text_chunk* ch, aqc_frame_info* info, bool resident, const FrameExtents* fx = nullptr) {
-    GET_SLOT(s);
-    if (!ch || !info || !ch->text1) return fail(AQC_ERR_ARG, "aqc_frame: null argument");
-    const bool paired = ch->text2 != nullptr;
-    const int nf = paired ? 2 : 1;
-    const uint8_t* text[2] = {ch->text1, ch->text2};
-    const uint64_t bytes[2] = {ch->bytes1, paired ? ch->bytes2 : 0};
-    const int final_[2] = {ch->final1, ch->final2};
-    for (int k = 0; k < nf; k++)
-        if (bytes[k] >= (1ull << 31) - IDX_TILE) return fail(AQC_ERR_ARG, "aqc_frame: chunks must be < 2 GiB");
-    HIP_TRY(slot_sync(*s));
-    s->framed = s->formatted = false;
-    s->ran = false;
-    s->fused = false;
-    DevBuf* arena[2] = {&s->seq1, &s->seq2};
-    DevBuf* seq_off[2] = {&s->off1, &s->off2};
-    DevBuf* qual_off[2] = {&s->qoff1, &s->qoff2};
-    DevBuf* seq_len[2] = {&s->len1, &s->len2};
-    // scratch: FrameMeta[2] | line totals[2] | tail values[4]
-    if (s->t_scratch.reserve(256)) return fail(AQC_ERR_HIP, "hipMalloc failed");
-    FrameMeta* d_meta = (FrameMeta*)s->t_scratch.p;
-    unsigned long long* d_tot = (unsigned long long*)((uint8_t*)s->t_scratch.p + 64);
-    // 1. text to the device; line index in one pass (text_index_kernel): both files in one launch.  The text sits
-    //    TEXT_FRONT bytes into its buffer: the writer's 16-byte windows may start a few bytes before a piece's source.
-    uint64_t tiles[2] = {0, 0}, cap[2] = {0, 0};
-    uint8_t* tbase[2] = {nullptr, nullptr};
-    for (int k = 0; k < nf; k++) {
-        const size_t slack = IDX_TILE + 64;
-        if (arena[k]->reserve(TEXT_FRONT + bytes[k] + slack)) return fail(AQC_ERR_HIP, "hipMalloc of %llu bytes failed", (unsigned long long)bytes[k]);
-        tbase[k] = (uint8_t*)arena[k]->p + TEXT_FRONT;
-        if (!resident && fx && fx->n[k]) {
-            // parts of the chunk are in this device's memory already (aqc_frame_mixed): those move inside HBM, the rest comes up
-            uint64_t cur = 0;
-            for (uint64_t e = 0; e < fx->n[k]; ++e) {
-                const aqc_text_extent& x = fx->ext[k][e];
-                if (x.offset < cur || x.offset + x.bytes > bytes[k] || !x.device_text) return fail(AQC_ERR_ARG, "aqc_frame_mixed: extents must be sorted, disjoint and inside the chunk");
-                if (x.offset > cur) HIP_TRY(hipMemcpyAsync(tbase[k] + cur, text[k] + cur, x.offset - cur, hipMemcpyHostToDevice, s->stream));
-                if (x.bytes) HIP_TRY(hipMemcpyAsync(tbase[k] + x.offset, x.device_text, x.bytes, hipMemcpyDeviceToDevice, s->stream));
-                cur = x.offset + x.bytes;
-            }
-            if (bytes[k] > cur) HIP_TRY(hipMemcpyAsync(tbase[k] + cur, text[k] + cur, bytes[k] - cur, hipMemcpyHostToDevice, s->stream));
-            HIP_TRY(hipMemsetAsync(tbase[k] + bytes[k], 0, slack, s->stream));
-            s->last_byte[k] = bytes[k] ? fx->last[k] : (uint8_t)'\n';
-        } else if (!resident) {
-            if (bytes[k]) HIP_TRY(hipMemcpyAsync(tbase[k], text[k], bytes[k], hipMemcpyHostToDevice, s->stream));
-            HIP_TRY(hipMemsetAsync(tbase[k] + bytes[k], 0, slack, s->stream));
-            s->last_byte[k] = bytes[k] ? text[k][bytes[k] - 1] : (uint8_t)'\n';
-        }
-        tiles[k] = bytes[k] ? (bytes[k] + IDX_TILE - 1) / IDX_TILE : 1;
-        // FASTQ lines average ~90 bytes; a chunk with more lines than this guess is indexed again with the exact size
-        const uint64_t guess = bytes[k] / 16 + 4096;
-        cap[k] = s->t_line_end[k].cap / sizeof(uint32_t) > guess + 2 ? s->t_line_end[k].cap / sizeof(uint32_t) - 2 : guess;
-        if (s->t_line_end[k].reserve(sizeof(uint32_t) * (cap[k] + 2))) return fail(AQC_ERR_HIP, "hipMalloc failed");
+// one aqc_frame call as its steps see the chunk
+struct FrameJob {
+    const aqc_text_chunk* ch;
+    int nf;                        // files of the chunk: 2 when paired
+    const uint8_t* text[2];
+    uint64_t bytes[2];
+    uint8_t* tbase[2];             // where each file's text begins on the device
+    uint64_t tiles[2], cap[2];     // index tiles per file; entries its line table can take
+    uint32_t virt[2];              // the line end that stands in for the '\n' an unterminated last line lacks (0: none)
+    bool bubble;
+};
+constexpr size_t TEXT_SLACK = IDX_TILE + 64;
+
+// parts of the chunk are in this device's memory already (aqc_frame_mixed): those move inside HBM, the rest comes up
+static int put_extents(Slot* s, const FrameJob& j, int k, const FrameExtents& fx) {
+    uint64_t cur = 0;
+    for (uint64_t e = 0; e < fx.n[k]; ++e) {
+        const aqc_text_extent& x = fx.ext[k][e];
+        if (x.offset < cur || x.offset + x.bytes > j.bytes[k] || !x.device_text) return fail(AQC_ERR_ARG, "aqc_frame_mixed: extents must be sorted, disjoint and inside the chunk");
+        if (x.offset > cur) HIP_TRY(hipMemcpyAsync(j.tbase[k] + cur, j.text[k] + cur, x.offset - cur, hipMemcpyHostToDevice, s->stream));
+        if (x.bytes) HIP_TRY(hipMemcpyAsync(j.tbase[k] + x.offset, x.device_text, x.bytes, hipMemcpyDeviceToDevice, s->stream));
+        cur = x.offset + x.bytes;
     }
-    const uint64_t all_tiles = tiles[0] + (paired ? tiles[1] : 0);
-    if (s->t_tile[0].reserve(sizeof(unsigned long long) * (all_tiles + 1))) return fail(AQC_ERR_HIP, "hipMalloc failed");
-    // 2. ... the four lines of every complete group, the lock-step record count, the bytes consumed: all queued behind the index
-    //    pass without asking the host for anything — the kernels read the line totals where the index pass left them, their grids
-    //    are sized for the most lines the chunk could hold.  ONE copy back (FrameOut), ONE wait per chunk.
+    if (j.bytes[k] > cur) HIP_TRY(hipMemcpyAsync(j.tbase[k] + cur, j.text[k] + cur, j.bytes[k] - cur, hipMemcpyHostToDevice, s->stream));
+    return 0;
+}
+
+// 1. text to the device (`resident`: it is there already, aqc_reframe).  The text sits TEXT_FRONT bytes into its buffer: the writer's
+//    16-byte windows may start a few bytes before a piece's source.
+static int put_text(Slot* s, FrameJob& j, int k, bool resident, const FrameExtents* fx) {
+    Mate& m = s->m[k];
+    if (m.seq.reserve(TEXT_FRONT + j.bytes[k] + TEXT_SLACK)) return fail(AQC_ERR_HIP, "hipMalloc of %llu bytes failed", (unsigned long long)j.bytes[k]);
+    j.tbase[k] = (uint8_t*)m.seq.p + TEXT_FRONT;
+    if (resident) return 0;
+    const bool mixed = fx && fx->n[k];
+    if (mixed) {
+        const int rc = put_extents(s, j, k, *fx);
+        if (rc) return rc;
+    } else if (j.bytes[k]) HIP_TRY(hipMemcpyAsync(j.tbase[k], j.text[k], j.bytes[k], hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemsetAsync(j.tbase[k] + j.bytes[k], 0, TEXT_SLACK, s->stream));
+    m.last_byte = !j.bytes[k] ? (uint8_t)'\n' : mixed ? fx->last[k] : j.text[k][j.bytes[k] - 1];
+    return 0;
+}
+
+// 2. the file's share of the index launch and its line table
+static int size_line_table(Slot* s, FrameJob& j, int k) {
+    DevBuf& le = s->m[k].line_end;
+    j.tiles[k] = j.bytes[k] ? (j.bytes[k] + IDX_TILE - 1) / IDX_TILE : 1;
+    // FASTQ lines average ~90 bytes; a chunk with more lines than this guess is indexed again with the exact size
+    const uint64_t guess = j.bytes[k] / 16 + 4096;
+    j.cap[k] = le.cap / sizeof(uint32_t) > guess + 2 ? le.cap / sizeof(uint32_t) - 2 : guess;
+    if (le.reserve(sizeof(uint32_t) * (j.cap[k] + 2))) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    return 0;
+}
+
+// 3a. one attempt's launches: line index in one pass (text_index_kernel), both files in one launch; the four lines of every complete
+//     group, the lock-step record count, the bytes consumed: all queued behind the index pass without asking the host for anything —
+//     the kernels read the line totals where the index pass left them, their grids are sized for the most lines the chunk could hold
+static int launch_index_and_frame(Slot* s, const FrameJob& j, TextScratch* sc) {
+    const uint64_t all_tiles = j.tiles[0] + j.tiles[1];
+    HIP_TRY(hipMemsetAsync(s->t_tile.p, 0, sizeof(unsigned long long) * (all_tiles + 1), s->stream));
+    IndexFile f[2] = {};
+    uint32_t t0 = 0;
+    for (int k = 0; k < j.nf; k++) {
+        f[k] = IndexFile{(const uint8_t*)j.tbase[k], j.bytes[k], (uint32_t*)s->m[k].line_end.p, j.cap[k], sc->lines + k, t0, (uint32_t)j.tiles[k]};
+        t0 += (uint32_t)j.tiles[k];
+    }
+    hipLaunchKernelGGL(text_index_kernel, dim3((unsigned)all_tiles), dim3(TXT_BLOCK), 0, s->stream, f[0], f[1],
+                       (unsigned long long*)s->t_tile.p, (unsigned int*)((unsigned long long*)s->t_tile.p + all_tiles));
+    HIP_TRY(hipGetLastError());
     const FrameMeta init{0xffffffffu, 0u, 0xffffffffu, 0u};
-    FrameMeta h_meta[2] = {init, init};
-    FrameOut fo{};
-    FrameOut* d_out = (FrameOut*)((uint8_t*)s->t_scratch.p + 128);
-    uint32_t virt[2] = {0, 0};
-    for (int k = 0; k < nf; k++)      // an unterminated last line of the file is a line (readline() returns it); it may end in blanks
-        if (final_[k] && bytes[k] > 0 && s->last_byte[k] != '\n') virt[k] = (uint32_t)bytes[k] | LINE_WS;
-    const bool bubble = c->has_cfg && c->cfg.debubble;
+    const FrameMeta h_meta[2] = {init, init};
+    HIP_TRY(hipMemcpyAsync(sc->meta, h_meta, sizeof(h_meta), hipMemcpyHostToDevice, s->stream));
+    uint64_t rec_cap = 0;
+    for (int k = 0; k < j.nf; k++) {
+        Mate& m = s->m[k];
+        const uint64_t r = (j.cap[k] + 1) / 4 + 1;            // records the line table could describe
+        rec_cap = std::max(rec_cap, r);
+        if (m.off.reserve(4 * r) || m.qoff.reserve(4 * r) || m.len.reserve(4 * r) || m.name_off.reserve(4 * r) || m.name_len.reserve(4 * r) ||
+            m.plus_off.reserve(4 * r) || m.plus_len.reserve(4 * r) || m.qual_len.reserve(4 * r))
+            return fail(AQC_ERR_HIP, "hipMalloc failed");
+        FramedFile ff{(uint32_t*)m.off.p, (uint32_t*)m.qoff.p, (uint32_t*)m.len.p, (uint32_t*)m.name_off.p,
+                      (uint32_t*)m.name_len.p, (uint32_t*)m.plus_off.p, (uint32_t*)m.plus_len.p, (uint32_t*)m.qual_len.p};
+        hipLaunchKernelGGL(frame_records_kernel, dim3((unsigned)((r + TXT_BLOCK - 1) / TXT_BLOCK)), dim3(TXT_BLOCK), 0, s->stream,
+                           (const uint8_t*)j.tbase[k], (const uint32_t*)m.line_end.p, (const unsigned long long*)(sc->lines + k), j.virt[k], ff, sc->meta + k, (uint64_t)j.cap[k]);
+    }
+    // (a single-end chunk: line table 0 twice, see set_mate)
+    hipLaunchKernelGGL(frame_finish_kernel, dim3(1), dim3(1), 0, s->stream, (const unsigned long long*)sc->lines, (const FrameMeta*)sc->meta,
+                       (const uint32_t*)s->m[0].line_end.p, (const uint32_t*)s->m[j.nf - 1].line_end.p, (const uint32_t*)s->m[0].len.p,
+                       j.virt[0], j.virt[1], (unsigned long long)j.bytes[0], (unsigned long long)j.bytes[1], j.nf, (unsigned long long)j.ch->max_records, &sc->frame,
+                       (unsigned long long)j.cap[0], (unsigned long long)j.cap[1]);
+    if (j.bubble) {
+        // lane / tile / x / y out of the R1 names (preprocesser.py:180-192) for the bubble filter
+        for (int k = 0; k < 5; k++)
+            if (s->aux[k].reserve((k < 4 ? sizeof(int32_t) : 1) * rec_cap)) return fail(AQC_ERR_HIP, "hipMalloc failed");
+        hipLaunchKernelGGL(parse_names_kernel, dim3((unsigned)((rec_cap + TXT_BLOCK - 1) / TXT_BLOCK)), dim3(TXT_BLOCK), 0, s->stream,
+                           (const uint8_t*)j.tbase[0], (const uint32_t*)s->m[0].name_off.p, (const uint32_t*)s->m[0].name_len.p, (const unsigned long long*)&sc->frame.n,
+                           (int32_t*)s->aux[0].p, (int32_t*)s->aux[1].p, (int32_t*)s->aux[2].p, (int32_t*)s->aux[3].p,
+                           (uint8_t*)s->aux[4].p);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// 3b. index and frame: ONE copy back (FrameOut), ONE wait per chunk — and all of it once more for a chunk with more lines than its
+//     table was sized for (counted, not written)
+static int index_and_frame(Slot* s, FrameJob& j, FrameOut& fo) {
+    TextScratch* sc = (TextScratch*)s->t_scratch.p;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        HIP_TRY(hipMemsetAsync(s->t_tile[0].p, 0, sizeof(unsigned long long) * (all_tiles + 1), s->stream));
-        IndexFile f[2] = {};
-        uint32_t t0 = 0;
-        for (int k = 0; k < nf; k++) {
-            f[k] = IndexFile{(const uint8_t*)tbase[k], bytes[k], (uint32_t*)s->t_line_end[k].p, cap[k], d_tot + k, t0, (uint32_t)tiles[k]};
-            t0 += (uint32_t)tiles[k];
-        }
-        hipLaunchKernelGGL(text_index_kernel, dim3((unsigned)all_tiles), dim3(TXT_BLOCK), 0, s->stream, f[0], f[1],
-                           (unsigned long long*)s->t_tile[0].p, (unsigned int*)((unsigned long long*)s->t_tile[0].p + all_tiles));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(d_meta, h_meta, sizeof(h_meta), hipMemcpyHostToDevice, s->stream));
-        uint64_t rec_cap = 0;
-        for (int k = 0; k < nf; k++) {
-            const uint64_t m = (cap[k] + 1) / 4 + 1;            // records the line table could describe
-            rec_cap = std::max(rec_cap, m);
-            if (seq_off[k]->reserve(4 * m) || qual_off[k]->reserve(4 * m) || seq_len[k]->reserve(4 * m) || s->t_name_off[k].reserve(4 * m) ||
-                s->t_name_len[k].reserve(4 * m) || s->t_plus_off[k].reserve(4 * m) || s->t_plus_len[k].reserve(4 * m) ||
-                s->t_qual_len[k].reserve(4 * m))
-                return fail(AQC_ERR_HIP, "hipMalloc failed");
-            FramedFile ff{(uint32_t*)seq_off[k]->p, (uint32_t*)qual_off[k]->p, (uint32_t*)seq_len[k]->p, (uint32_t*)s->t_name_off[k].p,
-                          (uint32_t*)s->t_name_len[k].p, (uint32_t*)s->t_plus_off[k].p, (uint32_t*)s->t_plus_len[k].p,
-                          (uint32_t*)s->t_qual_len[k].p};
-            hipLaunchKernelGGL(frame_records_kernel, dim3((unsigned)((m + TXT_BLOCK - 1) / TXT_BLOCK)), dim3(TXT_BLOCK), 0, s->stream,
-                               (const uint8_t*)tbase[k], (const uint32_t*)s->t_line_end[k].p, (const unsigned long long*)(d_tot + k), virt[k], ff, d_meta + k, (uint64_t)cap[k]);
-        }
-        hipLaunchKernelGGL(frame_finish_kernel, dim3(1), dim3(1), 0, s->stream, (const unsigned long long*)d_tot, (const FrameMeta*)d_meta,
-                           (const uint32_t*)s->t_line_end[0].p, (const uint32_t*)(paired ? s->t_line_end[1].p : s->t_line_end[0].p), (const uint32_t*)s->len1.p,
-                           virt[0], virt[1], (unsigned long long)bytes[0], (unsigned long long)bytes[1], nf, (unsigned long long)ch->max_records, d_out,
-                           (unsigned long long)cap[0], (unsigned long long)cap[1]);
-        if (bubble) {
-            // lane / tile / x / y out of the R1 names (preprocesser.py:180-192) for the bubble filter
-            for (int k = 0; k < 5; k++)
-                if (s->aux[k].reserve((k < 4 ? sizeof(int32_t) : 1) * rec_cap)) return fail(AQC_ERR_HIP, "hipMalloc failed");
-            hipLaunchKernelGGL(parse_names_kernel, dim3((unsigned)((rec_cap + TXT_BLOCK - 1) / TXT_BLOCK)), dim3(TXT_BLOCK), 0, s->stream,
-                               (const uint8_t*)tbase[0], (const uint32_t*)s->t_name_off[0].p, (const uint32_t*)s->t_name_len[0].p, (const unsigned long long*)&d_out->n,
-                               (int32_t*)s->aux[0].p, (int32_t*)s->aux[1].p, (int32_t*)s->aux[2].p, (int32_t*)s->aux[3].p,
-                               (uint8_t*)s->aux[4].p);
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&fo, d_out, sizeof(fo), hipMemcpyDeviceToHost, s->stream));
+        const int rc = launch_index_and_frame(s, j, sc);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(&fo, &sc->frame, sizeof(fo), hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(slot_sync(*s));
-        // FASTQ lines average ~90 bytes; a chunk with more lines than the table was sized for (counted, not written) is done again
         bool fits = true;
-        for (int k = 0; k < nf; k++) {
-            const uint64_t real = fo.lines[k] - (virt[k] ? 1 : 0);
-            if (real > cap[k]) {
+        for (int k = 0; k < j.nf; k++) {
+            const uint64_t real = fo.lines[k] - (j.virt[k] ? 1 : 0);
+            if (real > j.cap[k]) {
                 fits = false;
-                cap[k] = real;
-                if (s->t_line_end[k].reserve(sizeof(uint32_t) * (cap[k] + 2))) return fail(AQC_ERR_HIP, "hipMalloc failed");
+                j.cap[k] = real;
+                if (s->m[k].line_end.reserve(sizeof(uint32_t) * (j.cap[k] + 2))) return fail(AQC_ERR_HIP, "hipMalloc failed");
             }
         }
         if (fits) break;
     }
-    // 3. lock-step record count (preprocesser.py:412-429)
-    // (a record whose quality line is not as long as its sequence line is a record like any other: fastq.py:37-49 does not look,
-    //  and every later stage keeps a view per string — LEN_IRR in aqc_batch.hpp)
+    return 0;
+}
+
+// 4. slot view: the text IS the arena, every kernel reads the records in place
+// (a record whose quality line is not as long as its sequence line is a record like any other: fastq.py:37-49 does not look,
+//  and every later stage keeps a view per string — LEN_IRR in aqc_batch.hpp)
+static int publish_view(Slot* s, const FrameJob& j, const FrameOut& fo) {
     const uint64_t n = fo.n;
-    memset(info, 0, sizeof(*info));
-    info->n = n;
-    info->avail1 = fo.avail[0];
-    info->avail2 = fo.avail[1];
-    info->eof1 = (int32_t)fo.eof[0];
-    info->eof2 = paired ? (int32_t)fo.eof[1] : 0;
-    info->max_len = fo.max_len;
-    // 4. slot view: the text IS the arena, every kernel reads the records in place
     DevBatch v{};
     v.n = n;
-    v.first_index = ch->first_index;
-    v.seq1 = v.qual1 = (const uint8_t*)tbase[0];
-    v.off1 = (const uint32_t*)s->off1.p; v.qoff1 = (const uint32_t*)s->qoff1.p; v.len1 = (const uint32_t*)s->len1.p;
-    if (paired) {
-        v.seq2 = v.qual2 = (const uint8_t*)tbase[1];
-        v.off2 = (const uint32_t*)s->off2.p; v.qoff2 = (const uint32_t*)s->qoff2.p; v.len2 = (const uint32_t*)s->len2.p;
-    }
+    v.first_index = j.ch->first_index;
     if (s->results.reserve(sizeof(aqc_result) * (n ? n : 1))) return fail(AQC_ERR_HIP, "hipMalloc failed");
-    {
-        // the quality lines' own lengths (frame_records_kernel) and room for the final quality views of the marked records
-        // (written by the verdict kernels for those records only: no traffic for a regular chunk)
-        const bool any_irr = fo.first_mismatch[0] < n || (paired && fo.first_mismatch[1] < n);
-        s->has_irregular = any_irr;
-        for (int k = 0; k < nf; k++)
-            if (any_irr && s->qview[k].reserve(sizeof(uint32_t) * (n ? n : 1))) return fail(AQC_ERR_HIP, "hipMalloc failed");
-        v.qlen1 = (const uint32_t*)s->t_qual_len[0].p; v.qview1 = (uint32_t*)s->qview[0].p;
-        v.qlen2 = paired ? (const uint32_t*)s->t_qual_len[1].p : v.qlen1; v.qview2 = paired ? (uint32_t*)s->qview[1].p : v.qview1;
+    // the quality lines' own lengths (frame_records_kernel) and room for the final quality views of the marked records
+    // (written by the verdict kernels for those records only: no traffic for a regular chunk)
+    s->has_irregular = fo.first_mismatch[0] < n || (j.nf == 2 && fo.first_mismatch[1] < n);
+    for (int k = 0; k < j.nf; k++) {
+        Mate& m = s->m[k];
+        if (s->has_irregular && m.qview.reserve(sizeof(uint32_t) * (n ? n : 1))) return fail(AQC_ERR_HIP, "hipMalloc failed");
+        set_mate(v, k, MateView{j.tbase[k], j.tbase[k], (const uint32_t*)m.off.p, (const uint32_t*)m.qoff.p, (const uint32_t*)m.len.p,
+                                (const uint32_t*)m.qual_len.p, (uint32_t*)m.qview.p});
     }
-    if (bubble) {
+    for (int k = 0; k < 2; k++) s->m[k].consumed = fo.consumed[k];      // (0 for the file a single-end chunk does not have)
+    if (j.bubble) {
         v.aux_lane = (const int32_t*)s->aux[0].p; v.aux_tile = (const int32_t*)s->aux[1].p;
         v.aux_x = (const int32_t*)s->aux[2].p; v.aux_y = (const int32_t*)s->aux[3].p; v.aux_ok = (const uint8_t*)s->aux[4].p;
     }
     s->view = v;
     s->n = n;
-    s->paired = paired;
-    s->raw_max_len = info->max_len;
-    s->max_len = info->max_len;
-    // 5. bytes consumed by the n records (+ R1's next sequence length for the TOTAL_BASES quirk)
-    const uint64_t consumed[2] = {fo.consumed[0], fo.consumed[1]};
-    const uint32_t h_next = fo.next_len1;
-    info->consumed1 = consumed[0];
-    info->consumed2 = consumed[1];
-    s->consumed[0] = consumed[0]; s->consumed[1] = consumed[1];
-    info->next_len1 = h_next;
+    s->paired = j.nf == 2;
+    s->raw_max_len = s->max_len = fo.max_len;
+    return 0;
+}
+
+// 5. what the caller learns: the lock-step record count (preprocesser.py:412-429), the bytes consumed by the n records (+ R1's next
+//    sequence length for the TOTAL_BASES quirk)
+static void fill_frame_info(aqc_frame_info* info, const FrameOut& fo, bool paired) {
+    memset(info, 0, sizeof(*info));
+    info->n = fo.n;
+    info->avail1 = fo.avail[0];
+    info->avail2 = fo.avail[1];
+    info->eof1 = (int32_t)fo.eof[0];
+    info->eof2 = paired ? (int32_t)fo.eof[1] : 0;
+    info->max_len = fo.max_len;
+    info->consumed1 = fo.consumed[0];
+    info->consumed2 = fo.consumed[1];
+    info->next_len1 = fo.next_len1;
+}
+
+static int frame_impl(aqc_ctx* c, int slot, const aqc_text_chunk* ch, aqc_frame_info* info, bool resident, const FrameExtents* fx = nullptr) {
+    GET_SLOT(s);
+    if (!ch || !info || !ch->text1) return fail(AQC_ERR_ARG, "aqc_frame: null argument");
+    const bool paired = ch->text2 != nullptr;
+    FrameJob j{ch, paired ? 2 : 1, {ch->text1, ch->text2}, {ch->bytes1, paired ? ch->bytes2 : 0}};
+    for (int k = 0; k < j.nf; k++)
+        if (j.bytes[k] >= (1ull << 31) - IDX_TILE) return fail(AQC_ERR_ARG, "aqc_frame: chunks must be < 2 GiB");
+    HIP_TRY(slot_sync(*s));
+    s->framed = s->formatted = false;
+    s->ran = false;
+    s->fused = false;
+    if (s->t_scratch.reserve(TEXT_SCRATCH_BYTES)) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    int rc;
+    for (int k = 0; k < j.nf; k++)
+        if ((rc = put_text(s, j, k, resident, fx)) || (rc = size_line_table(s, j, k))) return rc;
+    if (s->t_tile.reserve(sizeof(unsigned long long) * (j.tiles[0] + j.tiles[1] + 1))) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    const int final_[2] = {ch->final1, ch->final2};
+    for (int k = 0; k < j.nf; k++)      // an unterminated last line of the file is a line (readline() returns it); it may end in blanks
+        if (final_[k] && j.bytes[k] > 0 && s->m[k].last_byte != '\n') j.virt[k] = (uint32_t)j.bytes[k] | LINE_WS;
+    j.bubble = c->has_cfg && c->cfg.debubble;
+    FrameOut fo{};
+    if ((rc = index_and_frame(s, j, fo)) || (rc = publish_view(s, j, fo))) return rc;
+    fill_frame_info(info, fo, paired);
     s->framed = true;
     s->last_chunk = *ch;
     return 0;
@@ -222,6 +260,147 @@ int aqc_reframe(aqc_ctx* c, int slot, aqc_frame_info* info) {
 }
 
 // ---- text out ----------------------------------------------------------------------------------------------------
+static FormatView make_format_view(const aqc_ctx* c, const Slot* s, const Slot* vs, bool plain, int32_t store_overlap, bool spans) {
+    FormatView v{};
+    v.paired = s->paired ? 1 : 0;
+    v.results = (const aqc_result*)vs->results.p;
+    v.plain = plain ? 1 : 0;
+    v.verdict_paired = vs->paired ? 1 : 0;
+    v.barcode = c->cfg.barcode ? 1 : 0;
+    v.barcode_length = c->cfg.barcode_length;
+    v.store_overlap = (store_overlap && vs->paired) ? 1 : 0;
+    v.spans = (spans && !plain) ? 1 : 0;
+    v.n_framed = s->n;
+    v.consumed[0] = (uint32_t)s->m[0].consumed; v.consumed[1] = (uint32_t)s->m[1].consumed;
+    for (int k = 0; k < (s->paired ? 2 : 1); k++) {
+        const Mate& m = s->m[k];
+        v.f[k].text = (const uint8_t*)m.seq.p + TEXT_FRONT;
+        v.f[k].seq_off = (const uint32_t*)m.off.p;
+        v.f[k].qual_off = (const uint32_t*)m.qoff.p;
+        v.f[k].seq_len = (const uint32_t*)m.len.p;
+        v.f[k].name_off = (const uint32_t*)m.name_off.p;
+        v.f[k].name_len = (const uint32_t*)m.name_len.p;
+        v.f[k].plus_off = (const uint32_t*)m.plus_off.p;
+        v.f[k].plus_len = (const uint32_t*)m.plus_len.p;
+        v.f[k].qual_len = (const uint32_t*)m.qual_len.p;
+        v.f[k].qview = (const uint32_t*)m.qview.p;
+    }
+    return v;
+}
+
+// Stream sizes, the first way.  The verdict kernel may have done the placement already (AQC_FUSED=1, all n records of the slot, the
+// two-stream case): its totals stand in for the sums / bases passes — unless it gave the placement up (a deferred pair, a record that
+// is not plain text).  Taken: v.fused is set.
+static int sizes_from_fused(Slot* s, FormatView& v, unsigned long long h_tot[FMT_STREAMS]) {
+    unsigned long long misc[5];
+    HIP_TRY(hipMemcpyAsync(misc, s->fz_misc.p, sizeof(misc), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if ((misc[0] >> 32) != 0) return 0;
+    v.fused = 1;
+    v.fstate[0] = (const uint32_t*)s->m[0].fz_rec.p; v.fstate[1] = (const uint32_t*)s->m[1].fz_rec.p;
+    v.fbatch = (const unsigned long long*)s->fz_state.p;
+    v.fbatch_shift = 5;
+    static_assert(FastWaveLds<10, true, true>::PPW == 32, "fbatch_shift");
+    h_tot[0] = misc[1]; h_tot[3] = misc[2]; h_tot[1] = misc[3]; h_tot[4] = misc[4];
+    return 0;
+}
+
+// Stream sizes, the second way.  Streams q = file * 3 + {0 good, 1 bad, 2 overlap}: per-tile byte sums -> tile bases (one launch each),
+// the per-record offsets are formed inside the writer.
+// f_tile: [FMT_STREAMS x n_tiles] the tiles' prefixes inside their super-tiles | [FMT_STREAMS x n_super] the super-tiles' sums -> bases
+static int sizes_from_sums(Slot* s, const FormatView& v, uint64_t n, uint64_t n_tiles, uint64_t n_super, unsigned long long h_tot[FMT_STREAMS]) {
+    if (s->f_tile.reserve(sizeof(unsigned long long) * FMT_STREAMS * (n_tiles + n_super)) || s->t_scratch.reserve(TEXT_SCRATCH_BYTES))
+        return fail(AQC_ERR_HIP, "hipMalloc failed");
+    unsigned long long* d_tot = ((TextScratch*)s->t_scratch.p)->fmt_totals;
+    unsigned long long* d_super = (unsigned long long*)s->f_tile.p + FMT_STREAMS * n_tiles;
+    if (n) hipLaunchKernelGGL(fmt_tile_sums_kernel, dim3((unsigned)n_super), dim3(TXT_BLOCK), 0, s->stream, v, n, n_tiles, n_super, (unsigned long long*)s->f_tile.p, d_super);
+    else HIP_TRY(hipMemsetAsync(s->f_tile.p, 0, sizeof(unsigned long long) * FMT_STREAMS * (n_tiles + n_super), s->stream));
+    hipLaunchKernelGGL(fmt_tile_bases_kernel, dim3(v.spans ? FMT_STREAMS : 6), dim3(TXT_BLOCK), 0, s->stream, d_super, n_super, d_tot);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, sizeof(unsigned long long) * (v.spans ? FMT_STREAMS : 6), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+// The writers' working buffers, carved once per call:
+//   f_plan   one 16-byte plan word per (record, file), dense (`plan0`) | the six words of the records the general kernel takes, in list order (`listed`)
+//   f_patch  the patch words of the dense plans | the one-piece plans of a spans / fused format, two words each, in list order (`wplan`)
+//   f_pos    the general kernel's GEN_LISTS lists (`lists`) | their lengths (`n_gen`) | the lengths of the one-piece lists (`n_whole`)
+//   f_over   full piece lists for the records that do not fit a plan
+struct FormatLayout {
+    uint64_t n_tasks, gen_cap, per_list;
+    uint4 *plan0, *listed, *patch0, *wplan;
+    FmtTask* over;
+    uint32_t* lists;
+    unsigned int *n_gen, *n_whole;
+    unsigned list_blocks, copy_blocks;
+};
+static int carve_format_buffers(Slot* s, uint64_t n, uint64_t n_tiles, FormatLayout& L) {
+    const int nf = s->paired ? 2 : 1;
+    L.n_tasks = n * nf;
+    L.gen_cap = ((n_tiles + GEN_LISTS - 1) / GEN_LISTS) * FMT_TILE * nf;     // worst case: every record
+    const uint64_t plan0_bytes = (16 * L.n_tasks + 255) / 256 * 256;
+    if (s->f_plan.reserve(plan0_bytes + 16 * PLAN_Q * L.gen_cap * GEN_LISTS) || s->f_patch.reserve(16 * L.n_tasks + 32 * L.gen_cap * GEN_LISTS) || s->f_over.reserve(sizeof(FmtTask) * L.n_tasks) ||
+        s->f_pos.reserve(4 * L.gen_cap * GEN_LISTS + 2 * sizeof(unsigned int) * GEN_LISTS + 64))
+        return fail(AQC_ERR_HIP, "hipMalloc failed");
+    L.plan0 = (uint4*)s->f_plan.p;
+    L.listed = (uint4*)((uint8_t*)s->f_plan.p + plan0_bytes);
+    L.patch0 = (uint4*)s->f_patch.p;
+    L.wplan = (uint4*)((uint8_t*)s->f_patch.p + 16 * L.n_tasks);
+    L.over = (FmtTask*)s->f_over.p;
+    L.lists = (uint32_t*)s->f_pos.p;
+    L.n_gen = (unsigned int*)((uint8_t*)s->f_pos.p + 4 * L.gen_cap * GEN_LISTS);
+    L.n_whole = L.n_gen + GEN_LISTS;
+    // GEN_LISTS x k workgroups; k from the worst case, at most 32 per list
+    L.per_list = std::min<uint64_t>(std::max<uint64_t>((L.gen_cap + GEN_ROUND - 1) / GEN_ROUND, 1), 32);
+    L.list_blocks = (unsigned)(GEN_LISTS * L.per_list);
+    L.copy_blocks = (unsigned)((L.n_tasks + (COPY_BLOCK / 32) * FMT_UNROLL - 1) / ((COPY_BLOCK / 32) * FMT_UNROLL));
+    return 0;
+}
+
+// Which kernels write a pass (pass 1: the overlap streams of store_overlap).  The general copy kernel follows every one of them.
+enum class Writer {
+    PLACE_COPY,     // place + copy in one kernel, piece lists only for the listed records
+    PLAN_WHOLE,     // dense plans, then the whole-record copy walks them
+    PLAN_ONLY,      // dense-plan kernel alone: nothing for the whole-record copy to walk
+    PLAN_LISTED,    // listed one-piece plans, then the list copy
+};
+static Writer choose_writer(const FormatView& v, int pass) {
+    // text mode without barcodes, main pass (round 6): place + copy
+    // (AQC_PLACE_COPY=0: the plan / whole-copy pair of rounds 2 - 5, for A/B measurements)
+    static const bool place_copy = [] { const char* e = getenv("AQC_PLACE_COPY"); return !(e && e[0] == '0'); }();
+    // spans / fused mode: what stays in the caller's chunk / what the verdict kernel copied has no plan; the records that are their
+    // own bytes but for the walk's byte patches are still the plan kernel's, on a list
+    const bool sparse = v.spans || v.fused;
+    if (sparse) return Writer::PLAN_LISTED;
+    if (place_copy && pass == 0 && !v.plain && !v.barcode) return Writer::PLACE_COPY;
+    // a barcode run has no one-piece record: fmt_plan_kernel writes no dense plans and nothing walks them
+    return v.barcode && !v.plain ? Writer::PLAN_ONLY : Writer::PLAN_WHOLE;
+}
+
+static void write_pass(Slot* s, const FormatView& v, const FormatLayout& L, const FormatOut& outs, int pass, uint64_t n, uint64_t n_tiles, uint64_t n_super) {
+    const unsigned long long* tb = (const unsigned long long*)s->f_tile.p;
+    const Writer w = choose_writer(v, pass);
+    if (w == Writer::PLACE_COPY) {
+        hipLaunchKernelGGL(fmt_place_copy_kernel, dim3((unsigned)n_tiles), dim3(PC_BLOCK), 0, s->stream, v, n, n_tiles, n_super, tb, tb + FMT_STREAMS * n_tiles,
+                           L.listed, L.lists, L.n_gen, L.gen_cap, outs);
+        hipLaunchKernelGGL(fmt_plan_listed_kernel, dim3(L.list_blocks), dim3(FMT_TILE), 0, s->stream, v, L.listed, L.over,
+                           (const uint32_t*)L.lists, (const unsigned int*)L.n_gen, L.gen_cap, s->status);
+    } else {
+        hipLaunchKernelGGL(fmt_plan_kernel, dim3((unsigned)n_tiles), dim3(FMT_TILE), 0, s->stream, v, n, n_tiles, n_super,
+                           tb, tb + FMT_STREAMS * n_tiles, pass, s->status, L.plan0, L.patch0,
+                           L.listed, L.over, L.lists, L.n_gen, L.gen_cap, L.wplan, L.n_whole, outs.p[0], outs.p[3],
+                           (SpanEvent*)s->m[0].f_events.p, (SpanEvent*)s->m[1].f_events.p);
+        if (w == Writer::PLAN_WHOLE) hipLaunchKernelGGL(fmt_copy_whole_kernel, dim3(L.copy_blocks), dim3(COPY_BLOCK), 0, s->stream, v, L.n_tasks, (const uint4*)L.plan0,
+                                                        (const uint4*)L.patch0, outs);
+        if (w == Writer::PLAN_LISTED) hipLaunchKernelGGL(fmt_copy_whole_list_kernel, dim3(L.list_blocks), dim3(COPY_BLOCK), 0, s->stream, v, (const uint4*)L.wplan, outs,
+                                                         (const unsigned int*)L.n_whole, L.gen_cap);
+    }
+    hipLaunchKernelGGL(fmt_copy_kernel, dim3(L.list_blocks), dim3(COPY_BLOCK), 0, s->stream, v,
+                       (const uint4*)L.listed, (const FmtTask*)L.over, outs, (const uint32_t*)L.lists,
+                       (const unsigned int*)L.n_gen, L.gen_cap);
+}
+
 static int format_impl(aqc_ctx* c, int slot, int verdict_slot, uint64_t n, int32_t store_overlap, uint64_t bytes_out[6], bool spans = false) {
     GET_SLOT(s);
     int rc;
@@ -233,133 +412,34 @@ static int format_impl(aqc_ctx* c, int slot, int verdict_slot, uint64_t n, int32
     if (!vs->ran) return fail(AQC_ERR_STATE, "aqc_format before aqc_run");
     if (n > s->n || n > vs->n) return fail(AQC_ERR_ARG, "aqc_format: n exceeds the slot's records");
     if (plain) HIP_TRY(slot_sync(*vs));      // the verdicts come from another slot's stream
-    FormatView v{};
-    v.paired = s->paired ? 1 : 0;
-    v.results = (const aqc_result*)vs->results.p;
-    v.plain = plain ? 1 : 0;
-    v.verdict_paired = vs->paired ? 1 : 0;
-    v.barcode = c->cfg.barcode ? 1 : 0;
-    v.barcode_length = c->cfg.barcode_length;
-    v.store_overlap = (store_overlap && vs->paired) ? 1 : 0;
-    v.spans = (spans && !plain) ? 1 : 0;
-    v.consumed[0] = (uint32_t)s->consumed[0]; v.consumed[1] = (uint32_t)s->consumed[1];
-    v.n_framed = s->n;
-    s->n_events[0] = s->n_events[1] = 0;
-    const DevBuf* sl[2] = {&s->len1, &s->len2};
-    const DevBuf* arena[2] = {&s->seq1, &s->seq2};
-    const DevBuf* so[2] = {&s->off1, &s->off2};
-    const DevBuf* qo[2] = {&s->qoff1, &s->qoff2};
-    for (int k = 0; k < (s->paired ? 2 : 1); k++) {
-        v.f[k].text = (const uint8_t*)arena[k]->p + TEXT_FRONT;
-        v.f[k].seq_off = (const uint32_t*)so[k]->p;
-        v.f[k].qual_off = (const uint32_t*)qo[k]->p;
-        v.f[k].seq_len = (const uint32_t*)sl[k]->p;
-        v.f[k].name_off = (const uint32_t*)s->t_name_off[k].p;
-        v.f[k].name_len = (const uint32_t*)s->t_name_len[k].p;
-        v.f[k].plus_off = (const uint32_t*)s->t_plus_off[k].p;
-        v.f[k].plus_len = (const uint32_t*)s->t_plus_len[k].p;
-        v.f[k].qual_len = (const uint32_t*)s->t_qual_len[k].p;
-        v.f[k].qview = (const uint32_t*)s->qview[k].p;
-    }
-    // streams q = file * 3 + {0 good, 1 bad, 2 overlap}: per-tile byte sums -> tile bases (one launch each), the
-    // per-record offsets are formed inside the writer
+    FormatView v = make_format_view(c, s, vs, plain, store_overlap, spans);
+    s->m[0].n_events = s->m[1].n_events = 0;
     const uint64_t n_tiles = n ? (n + FMT_TILE - 1) / FMT_TILE : 1;
     const uint64_t n_super = (n_tiles + FMT_SUPER - 1) / FMT_SUPER;
-    bool live[6];
-    for (int q = 0; q < 6; q++) live[q] = (q < 3 || s->paired) && (q % 3 != 2 || v.store_overlap);
     unsigned long long h_tot[FMT_STREAMS] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // the verdict kernel may have done the placement already (AQC_FUSED=1, all n records of the slot, the two-stream case): its totals
-    // stand in for the sums / bases passes — unless it gave the placement up (a deferred pair, a record that is not plain text)
-    if (s->fused && !plain && !spans && !v.store_overlap && n == s->n && n > 0) {
-        unsigned long long misc[5];
-        HIP_TRY(hipMemcpyAsync(misc, s->fz_misc.p, sizeof(misc), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        if ((misc[0] >> 32) == 0) {
-            v.fused = 1;
-            v.fstate[0] = (const uint32_t*)s->fz_rec[0].p; v.fstate[1] = (const uint32_t*)s->fz_rec[1].p;
-            v.fbatch = (const unsigned long long*)s->fz_state.p;
-            v.fbatch_shift = 5;
-            static_assert(FastWaveLds<10, true, true>::PPW == 32, "fbatch_shift");
-            h_tot[0] = misc[1]; h_tot[3] = misc[2]; h_tot[1] = misc[3]; h_tot[4] = misc[4];
-        }
-    }
+    if (s->fused && !plain && !spans && !v.store_overlap && n == s->n && n > 0 && (rc = sizes_from_fused(s, v, h_tot))) return rc;
     if (!v.fused) {
         s->fused = false;          // (whatever this call writes into the good streams replaces what the verdict kernel left there)
-        // f_tile: [FMT_STREAMS x n_tiles] the tiles' prefixes inside their super-tiles | [FMT_STREAMS x n_super] the super-tiles' sums -> bases
-        if (s->f_tile.reserve(sizeof(unsigned long long) * FMT_STREAMS * (n_tiles + n_super)) || s->t_scratch.reserve(256))
-            return fail(AQC_ERR_HIP, "hipMalloc failed");
-        unsigned long long* d_tot = (unsigned long long*)((uint8_t*)s->t_scratch.p + 128);
-        unsigned long long* d_super = (unsigned long long*)s->f_tile.p + FMT_STREAMS * n_tiles;
-        if (n) hipLaunchKernelGGL(fmt_tile_sums_kernel, dim3((unsigned)n_super), dim3(TXT_BLOCK), 0, s->stream, v, n, n_tiles, n_super, (unsigned long long*)s->f_tile.p, d_super);
-        else HIP_TRY(hipMemsetAsync(s->f_tile.p, 0, sizeof(unsigned long long) * FMT_STREAMS * (n_tiles + n_super), s->stream));
-        hipLaunchKernelGGL(fmt_tile_bases_kernel, dim3(v.spans ? FMT_STREAMS : 6), dim3(TXT_BLOCK), 0, s->stream, d_super, n_super, d_tot);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_tot, d_tot, sizeof(unsigned long long) * (v.spans ? FMT_STREAMS : 6), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
+        if ((rc = sizes_from_sums(s, v, n, n_tiles, n_super, h_tot))) return rc;
     }
-    if (v.spans) {
-        for (int f = 0; f < (s->paired ? 2 : 1); ++f) {
-            s->n_events[f] = h_tot[FMT_EVENT_STREAM + f];
-            if (s->f_events[f].reserve(sizeof(SpanEvent) * (s->n_events[f] + 1))) return fail(AQC_ERR_HIP, "hipMalloc failed");
-        }
+    for (int f = 0; f < (v.spans ? (s->paired ? 2 : 1) : 0); ++f) {
+        s->m[f].n_events = h_tot[FMT_EVENT_STREAM + f];
+        if (s->m[f].f_events.reserve(sizeof(SpanEvent) * (s->m[f].n_events + 1))) return fail(AQC_ERR_HIP, "hipMalloc failed");
     }
     FormatOut outs{};
     for (int q = 0; q < 6; q++) {
-        s->f_bytes[q] = live[q] ? h_tot[q] : 0;
+        const bool live = (q < 3 || s->paired) && (q % 3 != 2 || v.store_overlap);
+        s->f_bytes[q] = live ? h_tot[q] : 0;
         bytes_out[q] = s->f_bytes[q];
         if (s->f_out[q].reserve(s->f_bytes[q] + 64)) return fail(AQC_ERR_HIP, "hipMalloc failed");
         outs.p[q] = (uint8_t*)s->f_out[q].p;
     }
     if (n) {
-        const uint64_t n_tasks = n * (s->paired ? 2 : 1);
-        // 48-byte plans, (sparse) full piece lists for the records that do not fit a plan, and the list of the records the
-        // general copy kernel takes (+ its length)
-        const uint64_t gen_cap = ((n_tiles + GEN_LISTS - 1) / GEN_LISTS) * FMT_TILE * (s->paired ? 2 : 1);     // worst case: every record
-        // plans: one 16-byte word per (record, file), dense; the six words of the records the general kernel takes, in list order
-        const uint64_t plan0_bytes = (16 * n_tasks + 255) / 256 * 256;
-        if (s->f_plan.reserve(plan0_bytes + 16 * PLAN_Q * gen_cap * GEN_LISTS) || s->f_patch.reserve(16 * n_tasks + 32 * gen_cap * GEN_LISTS) || s->f_over.reserve(sizeof(FmtTask) * n_tasks) ||
-            s->f_pos.reserve(4 * gen_cap * GEN_LISTS + 2 * sizeof(unsigned int) * GEN_LISTS + 64))
-            return fail(AQC_ERR_HIP, "hipMalloc failed");
-        // f_pos: the general kernel's lists | the lengths of those and of the lists of one-piece plans of a spans / fused format;
-        // f_patch: the patch words of the dense plan0 | those listed plans (two words each, in list order)
-        uint4* d_wplan = (uint4*)((uint8_t*)s->f_patch.p + 16 * n_tasks);
-        unsigned int* d_ngen = (unsigned int*)((uint8_t*)s->f_pos.p + 4 * gen_cap * GEN_LISTS);
-        unsigned int* d_nwhole = d_ngen + GEN_LISTS;
-        const bool sparse = v.spans || v.fused;
-        unsigned copy_blocks = (unsigned)((n_tasks + (COPY_BLOCK / 32) * FMT_UNROLL - 1) / ((COPY_BLOCK / 32) * FMT_UNROLL));
+        FormatLayout L;
+        if ((rc = carve_format_buffers(s, n, n_tiles, L))) return rc;
         for (int pass = 0; pass < (v.store_overlap ? 2 : 1); ++pass) {
-            HIP_TRY(hipMemsetAsync(d_ngen, 0, 2 * sizeof(unsigned int) * GEN_LISTS, s->stream));
-            // GEN_LISTS x k workgroups; k from the worst case, at most 32 per list
-            uint64_t per_list = (gen_cap + GEN_ROUND - 1) / GEN_ROUND;
-            if (per_list > 32) per_list = 32;
-            if (per_list < 1) per_list = 1;
-            // text mode without barcodes, main pass (round 6): place + copy in one kernel, piece lists only for the listed records
-            // (AQC_PLACE_COPY=0: the plan / whole-copy pair of rounds 2 - 5, for A/B measurements)
-            static const bool place_copy = [] { const char* e = getenv("AQC_PLACE_COPY"); return !(e && e[0] == '0'); }();
-            if (place_copy && !sparse && pass == 0 && !v.plain && !v.barcode) {
-                const unsigned long long* tb = (const unsigned long long*)s->f_tile.p;
-                uint4* const pg = (uint4*)((uint8_t*)s->f_plan.p + plan0_bytes);
-                hipLaunchKernelGGL(fmt_place_copy_kernel, dim3((unsigned)n_tiles), dim3(PC_BLOCK), 0, s->stream, v, n, n_tiles, n_super, tb, tb + FMT_STREAMS * n_tiles,
-                                   pg, (uint32_t*)s->f_pos.p, d_ngen, gen_cap, outs);
-                hipLaunchKernelGGL(fmt_plan_listed_kernel, dim3((unsigned)(GEN_LISTS * per_list)), dim3(FMT_TILE), 0, s->stream, v, pg, (FmtTask*)s->f_over.p,
-                                   (const uint32_t*)s->f_pos.p, (const unsigned int*)d_ngen, gen_cap, s->status);
-            } else {
-            hipLaunchKernelGGL(fmt_plan_kernel, dim3((unsigned)n_tiles), dim3(FMT_TILE), 0, s->stream, v, n, n_tiles, n_super,
-                               (const unsigned long long*)s->f_tile.p, (const unsigned long long*)s->f_tile.p + FMT_STREAMS * n_tiles, pass, s->status, (uint4*)s->f_plan.p, (uint4*)s->f_patch.p,
-                               (uint4*)((uint8_t*)s->f_plan.p + plan0_bytes), (FmtTask*)s->f_over.p, (uint32_t*)s->f_pos.p, d_ngen, gen_cap, d_wplan, d_nwhole, outs.p[0], outs.p[3],
-                               (SpanEvent*)s->f_events[0].p, (SpanEvent*)s->f_events[1].p);
-            // (spans / fused mode: what stays in the caller's chunk / what the verdict kernel copied has no plan; the records that are their
-            //  own bytes but for the walk's byte patches are still this kernel's)
-            // (a barcode run has no one-piece record: fmt_plan_kernel writes no dense plans and nothing walks them)
-            if (!sparse) {
-                if (!(v.barcode && !v.plain)) hipLaunchKernelGGL(fmt_copy_whole_kernel, dim3(copy_blocks), dim3(COPY_BLOCK), 0, s->stream, v, n_tasks, (const uint4*)s->f_plan.p,
-                                                                 (const uint4*)s->f_patch.p, outs);
-            } else hipLaunchKernelGGL(fmt_copy_whole_list_kernel, dim3((unsigned)(GEN_LISTS * per_list)), dim3(COPY_BLOCK), 0, s->stream, v, (const uint4*)d_wplan, outs,
-                                    (const unsigned int*)d_nwhole, gen_cap);
-            }
-            hipLaunchKernelGGL(fmt_copy_kernel, dim3((unsigned)(GEN_LISTS * per_list)), dim3(COPY_BLOCK), 0, s->stream, v,
-                               (const uint4*)((uint8_t*)s->f_plan.p + plan0_bytes), (const FmtTask*)s->f_over.p, outs, (const uint32_t*)s->f_pos.p,
-                               (const unsigned int*)d_ngen, gen_cap);
+            HIP_TRY(hipMemsetAsync(L.n_gen, 0, 2 * sizeof(unsigned int) * GEN_LISTS, s->stream));
+            write_pass(s, v, L, outs, pass, n, n_tiles, n_super);
         }
         HIP_TRY(hipGetLastError());
     }
@@ -377,8 +457,8 @@ int aqc_format_spans(aqc_ctx* c, int slot, uint64_t n, int32_t store_overlap, ui
     if (!n_events) return fail(AQC_ERR_ARG, "aqc_format_spans: null argument");
     const int rc = format_impl(c, slot, slot, n, store_overlap, bytes_out, true);
     if (rc) return rc;
-    n_events[0] = c->slots[slot].n_events[0];
-    n_events[1] = c->slots[slot].n_events[1];
+    n_events[0] = c->slots[slot].m[0].n_events;
+    n_events[1] = c->slots[slot].m[1].n_events;
     return 0;
 }
 
@@ -394,9 +474,9 @@ int aqc_span_end(aqc_ctx* c, int slot, uint64_t n, uint64_t end[2]) {
     for (int f = 0; f < 2; ++f) {
         end[f] = 0;
         if (f == 1 && !s->paired) break;
-        if (n == s->n) { end[f] = s->consumed[f]; continue; }
+        if (n == s->n) { end[f] = s->m[f].consumed; continue; }
         uint32_t off = 0;               // record n begins where record n - 1 ends
-        HIP_TRY(hipMemcpyAsync(&off, (const uint32_t*)s->t_name_off[f].p + n, sizeof(off), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(&off, (const uint32_t*)s->m[f].name_off.p + n, sizeof(off), hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(hipStreamSynchronize(s->stream));
         end[f] = off;
     }
@@ -436,10 +516,10 @@ int aqc_fetch_span_events(aqc_ctx* c, int slot, int file, aqc_span_event* dst, u
     if (!s->formatted) return fail(AQC_ERR_STATE, "aqc_fetch_span_events before aqc_format_spans");
     if (file < 0 || file > 1) return fail(AQC_ERR_ARG, "aqc_fetch_span_events: bad file");
     static_assert(sizeof(aqc_span_event) == sizeof(SpanEvent), "host and device event layouts must agree");
-    const uint64_t ne = s->n_events[file];
+    const uint64_t ne = s->m[file].n_events;
     // (this entry counts in events, not bytes, and says so)
     if (ne > cap) return fail(AQC_ERR_ARG, "aqc_fetch_span_events: %llu events do not fit %llu", (unsigned long long)ne, (unsigned long long)cap);
-    return fetch_out(*s, s->f_events[file].p, sizeof(SpanEvent) * ne, dst, sizeof(SpanEvent) * ne, "aqc_fetch_span_events");
+    return fetch_out(*s, s->m[file].f_events.p, sizeof(SpanEvent) * ne, dst, sizeof(SpanEvent) * ne, "aqc_fetch_span_events");
 }
 
 // ---- debubble pre-pass: polyX census (aqc_census.hpp) ------------------------------------------------------------
@@ -462,7 +542,7 @@ int aqc_poly_census(aqc_ctx* c, int slot, int32_t poly_max, uint64_t* n_hits) {
         HIP_TRY(hipEventRecord(s->census_ev[0], s->stream));
         const uint64_t per_block = (uint64_t)TXT_BLOCK * CENSUS_PER_THREAD;
         hipLaunchKernelGGL(poly_census_kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(TXT_BLOCK), 0, s->stream, v.seq1, v.off1,
-                           v.len1, (const uint32_t*)s->t_name_off[0].p, (const uint32_t*)s->t_name_len[0].p, n, (int)poly_max, v.first_index,
+                           v.len1, (const uint32_t*)s->m[0].name_off.p, (const uint32_t*)s->m[0].name_len.p, n, (int)poly_max, v.first_index,
                            (aqc_census_hit*)s->census_hits.p, (unsigned long long*)s->census_n.p, s->status);
         // (grid-strided over the hits, whose number only the device knows here: at most 4 workgroups per CU)
         const uint64_t name_blocks = std::min<uint64_t>((n + TXT_BLOCK - 1) / TXT_BLOCK, (uint64_t)c->n_cu * 4);

@@ -15,6 +15,29 @@
 
 namespace aqc {
 
+// What a slot holds once per input file (mate 0 = read 1, mate 1 = read 2), grouped like the slot itself by the unit that fills it.
+struct __attribute__((visibility("hidden"))) Mate {
+    // ---- upload and verdicts (aqc_capi_run.hip; aqc_frame fills the same arena and tables from text) ----
+    DevBuf seq, qual, off, qoff, len;    // arena (framed text sits TEXT_FRONT bytes in), quality arena, byte offsets, quality offsets, lengths
+    DevBuf qlen, qview;                  // quality-line lengths of an uploaded batch (aqc_batch::qlen*), final quality views of LEN_IRR records
+    DevBuf fz_rec;                       // AQC_FUSED=1: position words per record (see Slot::fz_state)
+    // ---- text in, text out (aqc_capi_text.hip) ----
+    DevBuf line_end, name_off, name_len, plus_off, plus_len, qual_len;   // the line table and the name / strand-line / quality-length descriptors
+    uint8_t last_byte = '\n';
+    uint64_t consumed = 0;               // bytes of the file's chunk that the framed records take
+    DevBuf f_events;                     // aqc_format_spans: the file's events ...
+    uint64_t n_events = 0;               // ... and how many
+};
+
+// One mate of a batch view, as pointers; set_mate writes it into a DevBatch.  The single-end rules are here and nowhere else:
+// mate 0 also stands in for mate 1's quality words (qlen2 = qlen1, qview2 = qview1) until a mate 1 is set, and a single-end
+// aqc_frame hands frame_finish_kernel line table 0 twice (the kernel takes two tables whatever the chunk holds).
+struct MateView { const uint8_t *seq, *qual; const uint32_t *off, *qoff, *len, *qlen; uint32_t* qview; };
+static inline void set_mate(DevBatch& v, int k, const MateView& m) {
+    if (k == 0) { v.seq1 = m.seq; v.qual1 = m.qual; v.off1 = m.off; v.qoff1 = m.qoff; v.len1 = m.len; v.qlen1 = v.qlen2 = m.qlen; v.qview1 = v.qview2 = m.qview; }
+    else { v.seq2 = m.seq; v.qual2 = m.qual; v.off2 = m.off; v.qoff2 = m.qoff; v.len2 = m.len; v.qlen2 = m.qlen; v.qview2 = m.qview; }
+}
+
 // One slot of a context.  A slot's fields are grouped by the unit whose entry points fill them; a later stage reads what an
 // earlier one left (aqc_format the verdicts and the framing, aqc_compress the formatted streams).
 struct __attribute__((visibility("hidden"))) Slot {
@@ -42,30 +65,27 @@ struct __attribute__((visibility("hidden"))) Slot {
 
     // ---- upload and verdicts (aqc_capi_run.hip; aqc_frame fills the same arenas and view from text) ----
     bool has_irregular = false;      // some record of the slot has a quality line that is not as long as its sequence line
-    DevBuf qlen[2], qview[2];        // quality-line lengths of an uploaded batch (aqc_batch::qlen*), final quality views of LEN_IRR records
-    DevBuf seq1, qual1, off1, qoff1, len1, seq2, qual2, off2, qoff2, len2, aux[5], results;
+    Mate m[2];                       // everything that exists once per input file
+    DevBuf aux[5], results;
     DevBuf deferred, n_deferred;     // records the lane-per-read kernel hands to the general kernel
     DevBuf off_stage;                // the caller's 64-bit offsets on their way to the 32-bit device form
     uint32_t max_len = 0;
     uint32_t raw_max_len = 0;      // longest read of the slot (both mates), 0 = unknown
     DevBatch view{};
     uint64_t n = 0;
-    bool paired = false, ran = false, used_fast = false, same_arena1 = false, same_arena2 = false;
+    bool paired = false, ran = false, used_fast = false;
     // AQC_FUSED=1: the verdict kernel placed the slot's records in their streams and copied the whole good ones (aqc_fast.hpp, FUSE)
-    DevBuf fz_state, fz_rec[2], fz_misc;      // look-back words per batch; position words per record; ticket | abort | totals[4]
+    DevBuf fz_state, fz_misc;                 // look-back words per batch (Mate::fz_rec: position words per record); ticket | abort | totals[4]
     bool fused = false;                       // ... for the records the slot holds now (aqc_format checks fz_misc's abort word)
 
     // ---- text in, text out, the census (aqc_capi_text.hip) ----
-    // text in / text out (aqc_frame, aqc_format): per file the line table and the name / strand-line descriptors
-    DevBuf t_line_end[2], t_tile[2], t_name_off[2], t_name_len[2], t_plus_off[2], t_plus_len[2], t_qual_len[2];
-    DevBuf t_scratch;              // FrameMeta[2] + scan totals
+    // text in / text out (aqc_frame, aqc_format): the per-file tables are in Mate
+    DevBuf t_tile;                 // the index pass's tile words, both files
+    DevBuf t_scratch;              // FrameMeta[2] + scan totals (the layout: aqc_capi_text.hip)
     aqc_text_chunk last_chunk{};   // what the slot's arenas hold (aqc_reframe)
-    uint8_t last_byte[2] = {'\n', '\n'};
-    uint64_t consumed[2] = {0, 0};    // bytes of each file's chunk that the framed records take
     bool framed = false, formatted = false;
-    DevBuf f_pos, f_tile, f_plan, f_patch, f_over, f_out[6], f_events[2];
+    DevBuf f_pos, f_tile, f_plan, f_patch, f_over, f_out[6];
     bool formatted_fused = false;             // the last aqc_format took that placement (aqc_format_fused)
-    uint64_t n_events[2] = {0, 0};    // aqc_format_spans: events per file
     uint64_t f_bytes[6] = {0, 0, 0, 0, 0, 0};
     // aqc_poly_census: the hits of the last census of the slot's records, and their counter
     DevBuf census_hits, census_n;
