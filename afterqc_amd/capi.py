@@ -388,6 +388,9 @@ def load_library():
     lib.aqc_gunzip_dev.argtypes = [C.c_int, P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint64), P, C.c_int, C.c_uint64, C.c_uint64]
     lib.aqc_bunzip2_dev.argtypes = [C.c_int, P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint64), P, C.c_int, C.c_uint64]
     lib.aqc_bunzip2_dev.restype = C.c_int
+    lib.aqc_gunzip_probe.argtypes = [C.c_int, C.c_int, P, C.c_uint64, C.c_int, P, P, P, C.c_uint32, C.c_uint32, C.c_uint32, P, C.c_uint64, P, P, P, P, C.c_uint64,
+                                     C.POINTER(C.c_uint64), P, C.c_uint64, C.POINTER(C.c_uint64), P, C.POINTER(C.c_uint64)]
+    lib.aqc_gunzip_probe.restype = C.c_int
     lib.aqc_compress.argtypes = [P, C.c_int, C.c_int32, P]
     lib.aqc_fetch_gz.argtypes = [P, C.c_int, C.c_int, C.c_int, P, C.c_uint64]
     lib.aqc_pipe_create.argtypes = [C.POINTER(P), C.c_int32, C.c_int32, C.c_int32, C.POINTER(P)]
@@ -448,7 +451,7 @@ EXPORTED_SYMBOLS = ["aqc_abi_version", "aqc_device_count", "aqc_device_index", "
                     "aqc_qc_stat", "aqc_fetch_results", "aqc_fetch_quality_views", "aqc_error_record", "aqc_sync", "aqc_last_deferred", "aqc_kernel_ms", "aqc_timing_reset",
                     "aqc_timing_mean", "aqc_get_counters",
                     "aqc_get_histograms", "aqc_get_qc", "aqc_get_kmers", "aqc_overlap", "aqc_read_stats",
-                    "aqc_edit_distance", "aqc_frame", "aqc_frame_mixed", "aqc_reframe", "aqc_format", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused", "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms", "aqc_format_plain", "aqc_fetch_text", "aqc_fetch_streams", "aqc_compress", "aqc_fetch_gz", "aqc_gunzip_dev", "aqc_bunzip2_dev", "aqc_host_alloc",
+                    "aqc_edit_distance", "aqc_frame", "aqc_frame_mixed", "aqc_reframe", "aqc_format", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused", "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms", "aqc_format_plain", "aqc_fetch_text", "aqc_fetch_streams", "aqc_compress", "aqc_fetch_gz", "aqc_gunzip_dev", "aqc_bunzip2_dev", "aqc_gunzip_probe", "aqc_host_alloc",
                     "aqc_host_free",
                     "aqc_pipe_create", "aqc_pipe_destroy", "aqc_pipe_run", "aqc_pipe_last_error",
                     "aqc_host_count_newlines", "aqc_bgzf_compress", "aqc_pipe_split",
@@ -843,6 +846,34 @@ def bunzip2_dev(data, cap, device=0, group_blocks=0, threads=1):
     if rc != 0:
         raise AqcError(rc, (lib.aqc_last_error() or b"").decode("utf-8", "replace"))
     return out[:n.value].tobytes(), stats
+
+
+def gunzip_probe(image, nominal, stop, exact, window=b"", ratio_cap=6, tok_ratio=1, overlap_tokens=512, text_cap=4 << 20, engine=1, device=0):
+    """aqc_gunzip_probe: ONE group (the sections nominal / stop / exact, in bits of `image`) and ONE resolve of the device gunzip, on the
+    kernels (engine 1) or on their CPU emulation (engine 0, no GPU needed) -> dict: found / start_bit / end_bit / n_sym per section;
+    run = (first section, sections) of the longest chained run, status = resolve()'s (0, or -1: a marker before the member's
+    start), and for status 0 the run's crc (per section), piece_nl, text and the tail window"""
+    lib = load_library()
+    n = len(nominal)
+    src = np.frombuffer(image, dtype=np.uint8)
+    a_nom, a_stop, a_exact = np.asarray(nominal, dtype=np.uint64), np.asarray(stop, dtype=np.uint64), np.asarray(exact, dtype=np.uint8)
+    assert n > 0 and a_stop.size == n and a_exact.size == n
+    win = np.frombuffer(window, dtype=np.uint8) if len(window) else np.zeros(1, dtype=np.uint8)
+    piece_cap = int(text_cap) // 65536 + n + 1
+    sec, run, crc = np.zeros(4 * n, dtype=np.uint64), np.zeros(3, dtype=np.int32), np.zeros(n, dtype=np.uint32)
+    piece_nl, text, tail = np.zeros(piece_cap, dtype=np.uint32), np.zeros(int(text_cap) + 64, dtype=np.uint8), np.zeros(32768, dtype=np.uint8)
+    n_pieces, n_text, tail_len = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = lib.aqc_gunzip_probe(int(engine), int(device), src.ctypes.data, len(image), n, a_nom.ctypes.data, a_stop.ctypes.data, a_exact.ctypes.data,
+                              int(ratio_cap), int(tok_ratio), int(overlap_tokens), win.ctypes.data, len(window), sec.ctypes.data, run.ctypes.data,
+                              crc.ctypes.data, piece_nl.ctypes.data, piece_cap, C.byref(n_pieces), text.ctypes.data, int(text_cap), C.byref(n_text),
+                              tail.ctypes.data, C.byref(tail_len))
+    if rc != 0:
+        raise AqcError(rc, (lib.aqc_last_error() or b"").decode("utf-8", "replace"))
+    sec = sec.reshape(n, 4)
+    return {"found": [bool(x) for x in sec[:, 0]], "start_bit": [int(x) for x in sec[:, 1]], "end_bit": [int(x) for x in sec[:, 2]],
+            "n_sym": [int(x) for x in sec[:, 3]], "run": (int(run[0]), int(run[1])), "status": int(run[2]),
+            "crc": [int(x) for x in crc[:int(run[1])]], "piece_nl": [int(x) for x in piece_nl[:n_pieces.value]],
+            "text": text[:n_text.value].tobytes(), "tail": tail[:tail_len.value].tobytes()}
 
 
 def bz2_input_stats():

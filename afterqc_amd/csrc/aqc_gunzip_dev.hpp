@@ -865,6 +865,7 @@ __global__ __launch_bounds__(GZB_SCAN_THREADS) void gzb_scan_kernel(GzbJob J) {
     __shared__ uint8_t s_kraft[512];
     __shared__ uint8_t s_cl[128 * GZB_SCAN_THREADS];
     __shared__ uint32_t s_found[GZB_TILE_CAND];
+    __shared__ uint32_t s_hits[GZB_SCAN_THREADS];
     __shared__ uint32_t s_n;
     const int tid = threadIdx.x;
     for (int i = tid; i < 512; i += GZB_SCAN_THREADS) s_kraft[i] = (uint8_t)gzb_kraft9((uint32_t)i);
@@ -906,6 +907,7 @@ __global__ __launch_bounds__(GZB_SCAN_THREADS) void gzb_scan_kernel(GzbJob J) {
             if (gzb_kraft_ok_v((v64 >> o) | (hi64 << (64u - o)), hclen, s_kraft)) k2[i] |= 1u << bit;
         }
     }
+    uint32_t k3[4] = {0, 0, 0, 0}, mine = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         uint32_t mm = k2[i];
@@ -914,21 +916,32 @@ __global__ __launch_bounds__(GZB_SCAN_THREADS) void gzb_scan_kernel(GzbJob J) {
             mm &= mm - 1;
             const uint32_t p = (byte0 + 4u * (uint32_t)i) * 8u + bit;
             uint32_t data_bit, hlit, hdist;
-            if (gzb_header(J.comp, limit_bit, p, s_cl + tid, GZB_SCAN_THREADS, nullptr, data_bit, hlit, hdist)) {
-                const uint32_t at = atomicAdd(&s_n, 1u);
-                if (at < (uint32_t)GZB_TILE_CAND) s_found[at] = p;
+            if (gzb_header(J.comp, limit_bit, p, s_cl + tid, GZB_SCAN_THREADS, nullptr, data_bit, hlit, hdist)) { k3[i] |= 1u << bit; ++mine; }
+        }
+    }
+    // A tile keeps its LOWEST GZB_TILE_CAND block starts, in order — whichever lanes get here first (taken in order of arrival,
+    // a tile of many small blocks lost its first ones, and the section that must start there with them).  The lanes own
+    // ascending bytes: a lane's hits go behind those of all lanes below it; the few lanes that have any count them.
+    s_hits[tid] = mine;
+    __syncthreads();
+    if (mine) {
+        uint32_t at = 0;
+        for (int t = 0; t < tid; ++t) at += s_hits[t];
+        atomicAdd(&s_n, mine);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            uint32_t mm = k3[i];
+            while (mm) {
+                const uint32_t bit = (uint32_t)__builtin_ctz(mm);
+                mm &= mm - 1;
+                if (at < (uint32_t)GZB_TILE_CAND) s_found[at] = (byte0 + 4u * (uint32_t)i) * 8u + bit;
+                ++at;
             }
         }
     }
     __syncthreads();
     if (tid == 0) {
         const uint32_t n = gzb_min(s_n, (uint32_t)GZB_TILE_CAND);
-        for (uint32_t a = 1; a < n; ++a) {                  // (a handful at most: insertion sort)
-            const uint32_t x = s_found[a];
-            uint32_t b = a;
-            while (b > 0 && s_found[b - 1] > x) { s_found[b] = s_found[b - 1]; --b; }
-            s_found[b] = x;
-        }
         J.tile_cnt[blockIdx.x] = n;
         for (uint32_t a = 0; a < n; ++a) J.tile_cand[blockIdx.x * (uint32_t)GZB_TILE_CAND + a] = s_found[a];
     }

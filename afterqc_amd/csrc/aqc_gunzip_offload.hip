@@ -1,7 +1,8 @@
 // aqc_gunzip_offload.hip — gzip INPUT on the device: the threaded host driver of the kernels in aqc_gunzip_dev.hpp.
 //
 // DeviceInflate is the SectionOffload of aqc_gz.hpp that the pipe's ParallelGunzip hands groups of sections to
-// (aqcgz::make_device_offload); aqc_gunzip_dev is the C entry that decodes one whole file with it.  A unit of its own: of the
+// (aqcgz::make_device_offload); aqc_gunzip_dev is the C entry that decodes one whole file with it, aqc_gunzip_probe the one that
+// runs ONE group and ONE resolve of it (or of its CPU emulation, aqc_gunzip_ref.hpp) for the tests.  A unit of its own: of the
 // C ABI it needs only the page-locked host memory (aqc_host_alloc) and the NUMA helpers, and aqc_gunzip_dev.hpp is the one
 // kernel header that includes no other, so its kernels are defined in this unit alone.
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 
 #include "aqc_dev.hpp"
 #include "aqc_gunzip_dev.hpp"
+#include "aqc_gunzip_ref.hpp"
 #include "aqc_gz.hpp"
 #include <zlib.h>
 
@@ -60,6 +62,13 @@ public:
         if (const char* e = getenv("AQC_GZ_RESIDENT")) resident_ = e[0] != '0';
         if (const char* e = getenv("AQC_GZ_RATIO")) ratio_ = (uint32_t)std::max(2, std::min(64, atoi(e)));
         if (const char* e = getenv("AQC_GZ_TOK_RATIO")) tok_ratio_ = (uint32_t)std::max(1, std::min(16, atoi(e)));
+    }
+    // the budgets given, not taken from the defaults and the environment, and kept: a group that comes back short is not decoded
+    // again with more room (aqc_gunzip_probe: what a test sees is then one pass of the kernels with the budgets it named)
+    DeviceInflate(int device, size_t group_bytes, uint32_t ratio_cap, uint32_t tok_ratio, uint32_t overlap_tokens, bool grow) : DeviceInflate(device, group_bytes) {
+        resident_ = true;
+        ratio_ = ratio_cap; tok_ratio_ = tok_ratio; overlap_tokens_ = overlap_tokens;
+        grow_ = grow;
     }
     ~DeviceInflate() override {
         {
@@ -576,7 +585,7 @@ private:
         // A group that comes back short on the lean budgets (symbols 6 x, one token per compressed byte) is decoded once more with
         // room to spare, and so is every group after it (once per decoder: an input that compresses 6 x and better, or is nearly
         // all literals, is rare — and says so here; what is still missing then is not a matter of space, and the host's)
-        if (live < n && !grown_) {
+        if (grow_ && live < n && !grown_) {
             grown_ = true;
             {
                 std::lock_guard<std::mutex> g(mu_);
@@ -651,7 +660,7 @@ private:
     size_t group_bytes_;
     bool resident_ = true;
     uint32_t ratio_ = 6, tok_ratio_ = 1, overlap_tokens_ = GZB_OVERLAP_TOKENS;
-    bool grown_ = false;
+    bool grow_ = true, grown_ = false;
     std::mutex mu_;
     std::condition_variable cv_;
     bool stop_ = false, broken_ = false;
@@ -735,6 +744,111 @@ int aqc_gunzip_dev(int device, const uint8_t* gz, uint64_t size, uint8_t* out, u
     aqcgz::device_offload_stats(after);
     for (int i = 0; i < 5; ++i) stats[3 + i] = after[i] - before[i];
     *n_out = produced;
+    return rc;
+}
+
+// One group and one resolve, through SectionOffload's public interface alone: what the tests hold the kernels to (engine 1:
+// DeviceInflate with the budgets given and no second attempt) and what they hold them against (engine 0: CpuOffload of
+// aqc_gunzip_ref.hpp, the same GZB_HD functions in plain loops, with the same budgets, DeviceInflate's sizing rules and the
+// kernels' slice budget).  The sections nominal / stop / exact [n] over gz[0, size) go in as ONE submit(); sec[4 * k ..] = found,
+// start_bit, end_bit, n_sym of section k.  The longest run of found sections that chain (end_bit == the next one's start_bit;
+// the first of equals) is resolved with win[0, wlen) in front of it: run[0] its first section, run[1] its length (0: nothing was
+// found), run[2] resolve()'s status — 0, or the data error of a marker that points before the member's start, after which
+// nothing below is filled in.  crc[j], j < run[1]; piece_nl[0, *n_pieces); text[0, *n_text) = the run's sections one after the
+// other; tail[0, *tail_len) = the window behind the run (tail: 32768 bytes).
+int aqc_gunzip_probe(int engine, int device, const uint8_t* gz, uint64_t size, int n, const uint64_t* nominal, const uint64_t* stop, const uint8_t* exact,
+                     uint32_t ratio_cap, uint32_t tok_ratio, uint32_t overlap_tokens, const uint8_t* win, uint64_t wlen, uint64_t* sec, int32_t* run,
+                     uint32_t* crc, uint32_t* piece_nl, uint64_t piece_cap, uint64_t* n_pieces, uint8_t* text, uint64_t text_cap, uint64_t* n_text,
+                     uint8_t* tail, uint64_t* tail_len) {
+    if (!gz || !nominal || !stop || !exact || !sec || !run || !crc || !piece_nl || !n_pieces || !text || !n_text || !tail || !tail_len || (wlen && !win))
+        return fail(AQC_ERR_ARG, "null argument");
+    if (n <= 0 || wlen > GZB_WINDOW || ratio_cap < 1 || ratio_cap > 4096 || tok_ratio < 1 || tok_ratio > 16 || overlap_tokens < 1 || overlap_tokens > 65536 || (engine != 0 && engine != 1))
+        return fail(AQC_ERR_ARG, "gunzip probe: bad argument");
+    for (int k = 0; k < n; ++k)
+        if (nominal[k] > stop[k] || (stop[k] >> 3) >= size || (k > 0 && nominal[k] < nominal[k - 1])) return fail(AQC_ERR_ARG, "gunzip probe: section %d is not inside the image, or out of order", k);
+    static std::mutex mu;       // (one probe at a time: a decoder takes two groups at most, and the done callbacks below are this call's)
+    std::lock_guard<std::mutex> lock(mu);
+    struct Key { int device; uint32_t ratio, tok, overlap; };
+    static std::vector<std::pair<Key, std::unique_ptr<aqcgz::SectionOffload>>> cache;       // (as aqc_gunzip_dev keeps its decoders: buffers are set up once)
+    std::unique_ptr<CpuOffload> cpu;
+    aqcgz::SectionOffload* off = nullptr;
+    if (engine == 0) {
+        cpu.reset(new CpuOffload(1u << 20));
+        cpu->resident = true;
+        cpu->ratio_cap = ratio_cap; cpu->tok_ratio = tok_ratio; cpu->overlap_tokens = overlap_tokens;
+        cpu->slice_tokens = 2048; cpu->max_slices = 6;
+        cpu->slack = GZB_SLACK; cpu->sec_ratio = 2 * ratio_cap; cpu->total_unbounded = true;
+        off = cpu.get();
+    } else {
+        for (auto& e : cache)
+            if (e.first.device == device && e.first.ratio == ratio_cap && e.first.tok == tok_ratio && e.first.overlap == overlap_tokens) off = e.second.get();
+        if (!off) {
+            std::unique_ptr<DeviceInflate> made(new DeviceInflate(device, 1u << 20, ratio_cap, tok_ratio, overlap_tokens, false));
+            if (!made->start()) { (void)hipGetLastError(); return fail(AQC_ERR_HIP, "gunzip probe: cannot set up device %d", device); }
+            off = made.get();
+            cache.emplace_back(Key{device, ratio_cap, tok_ratio, overlap_tokens}, std::move(made));
+        }
+    }
+    // (1) one group, (2) its done callbacks
+    std::vector<aqcgz::OffloadResult> res((size_t)n);
+    {
+        std::mutex dmu;
+        std::condition_variable dcv;
+        int pending = n;
+        if (!off->submit(gz, (size_t)size, n, nominal, stop, exact, [&](int k, const aqcgz::OffloadResult& r) {
+                std::lock_guard<std::mutex> g(dmu);
+                res[(size_t)k] = r;
+                if (--pending == 0) dcv.notify_all();
+            }))
+            return fail(AQC_ERR_ARG, "gunzip probe: the decoder does not take the group");
+        std::unique_lock<std::mutex> lk(dmu);
+        dcv.wait(lk, [&] { return pending == 0; });
+    }
+    for (int k = 0; k < n; ++k) { sec[4 * k] = res[(size_t)k].found; sec[4 * k + 1] = res[(size_t)k].start_bit; sec[4 * k + 2] = res[(size_t)k].end_bit; sec[4 * k + 3] = res[(size_t)k].n_sym; }
+    int best0 = 0, best_n = 0;
+    for (int k = 0; k < n;) {
+        if (!res[(size_t)k].found) { ++k; continue; }
+        int e = k + 1;
+        while (e < n && res[(size_t)e].found && res[(size_t)e].start_bit == res[(size_t)e - 1].end_bit) ++e;
+        if (e - k > best_n) { best0 = k; best_n = e - k; }
+        k = e;
+    }
+    run[0] = best0; run[1] = best_n; run[2] = 0;
+    *n_pieces = 0; *n_text = 0; *tail_len = 0;
+    int rc = 0;
+    // (3) one resolve over that run, (4) its text
+    if (best_n > 0) {
+        std::vector<void*> tokens;
+        uint64_t total = 0, pieces = 0;
+        for (int j = 0; j < best_n; ++j) {
+            const aqcgz::OffloadResult& r = res[(size_t)(best0 + j)];
+            if (!r.resident || !r.token) { rc = fail(AQC_ERR_ARG, "gunzip probe: the decoder's results are not resident"); break; }
+            tokens.push_back(r.token);
+            total += r.n_sym;
+            pieces += (r.n_sym + GZB_CRC_PIECE - 1u) / GZB_CRC_PIECE;
+        }
+        if (!rc && (total > text_cap || pieces > piece_cap)) rc = fail(AQC_ERR_ARG, "gunzip probe: %llu bytes of text in %llu pieces do not fit", (unsigned long long)total, (unsigned long long)pieces);
+        if (!rc) {
+            size_t tl = 0;
+            const int st = off->resolve(tokens.data(), best_n, win, (size_t)wlen, crc, tail, &tl, piece_nl);
+            run[2] = st;
+            if (st == -2) rc = fail(AQC_ERR_HIP, "gunzip probe: resolve() failed");
+            else if (st == 0) {
+                *tail_len = tl; *n_pieces = pieces;
+                uint64_t at = 0;
+                bool ok = true;
+                for (int j = 0; j < best_n && ok; ++j) {
+                    const aqcgz::OffloadResult& r = res[(size_t)(best0 + j)];
+                    ok = off->fetch(r.token, 0, r.n_sym, text + at);
+                    at += r.n_sym;
+                }
+                ok = off->fetch_wait() && ok;
+                if (!ok) rc = fail(AQC_ERR_HIP, "gunzip probe: fetch() failed");
+                *n_text = at;
+            }
+        }
+    }
+    for (auto& r : res) if (r.token) off->release(r.token);
     return rc;
 }
 

@@ -436,6 +436,21 @@ int aqc_gunzip_dev(int device, const uint8_t* gz, uint64_t size, uint8_t* out, u
  * and expand kernels and in the copies.  `threads` is reserved (the host's share is one libbz2 thread). */
 int aqc_bunzip2_dev(int device, const uint8_t* bz, uint64_t size, uint8_t* out, uint64_t cap, uint64_t* n_out, uint64_t stats[8], int threads,
                     uint64_t group_blocks);
+/* The device gunzip's kernels held still for a test: ONE group and ONE resolve through the decoder's own launch sequence
+ * (csrc/aqc_gunzip_offload.hip: submit -> done -> resolve -> fetch), with the budgets given and no second attempt.
+ * engine 1: the kernels on GPU `device`; engine 0: the same per-lane functions in plain loops on the CPU
+ * (csrc/aqc_gunzip_ref.hpp; needs no GPU), same budgets, same sizing, the kernels' slice budget (6 x 2048 tokens per lane).
+ * Sections k < n of gz[0, size): searched from bit nominal[k] (exact[k]: the section must start AT it) up to the first block
+ * boundary at or behind bit stop[k].  sec[4 * k ..]: found, start_bit, end_bit, n_sym.  The longest run of found sections that
+ * chain (end_bit == the next one's start_bit; the first of equals) is resolved with win[0, wlen <= 32768) as the text in front
+ * of it: run[0] its first section, run[1] its length (0: nothing found), run[2] = 0 or -1 (a marker points before the member's
+ * start: invalid data; nothing below is filled in then).  crc[j]: CRC-32 of the run's j-th section; piece_nl[0, *n_pieces): line
+ * feeds of every 64 KiB piece (right-aligned in its section) of every section; text[0, *n_text): the run's text; tail[0, *tail_len):
+ * the last <= 32 KiB of win ++ text (tail holds 32768 bytes). */
+int aqc_gunzip_probe(int engine, int device, const uint8_t* gz, uint64_t size, int n, const uint64_t* nominal, const uint64_t* stop, const uint8_t* exact,
+                     uint32_t ratio_cap, uint32_t tok_ratio, uint32_t overlap_tokens, const uint8_t* win, uint64_t wlen, uint64_t* sec, int32_t* run,
+                     uint32_t* crc, uint32_t* piece_nl, uint64_t piece_cap, uint64_t* n_pieces, uint8_t* text, uint64_t text_cap, uint64_t* n_text,
+                     uint8_t* tail, uint64_t* tail_len);
 /* page-locked host memory for text chunks and fetched streams (hipHostMalloc): full-rate DMA */
 void* aqc_host_alloc(uint64_t bytes);
 void aqc_host_free(void* p);
