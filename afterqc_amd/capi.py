@@ -365,6 +365,8 @@ def load_library():
     lib.aqc_sync.argtypes = [P, C.c_int]
     lib.aqc_last_deferred.argtypes = [P, C.c_int, P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.aqc_last_deferred.restype = C.c_int
+    lib.aqc_last_verdict_words.argtypes = [P, C.c_int]
+    lib.aqc_last_verdict_words.restype = C.c_int
     lib.aqc_kernel_ms.argtypes = [P, C.c_int, P]
     lib.aqc_timing_reset.argtypes = [P, C.c_int]
     lib.aqc_timing_mean.argtypes = [P, C.c_int, P, P]
@@ -448,7 +450,7 @@ def load_library():
 
 EXPORTED_SYMBOLS = ["aqc_abi_version", "aqc_device_count", "aqc_device_index", "aqc_device_numa_node", "aqc_device_numa_node_of", "aqc_bind_thread_to_node", "aqc_last_error", "aqc_create", "aqc_destroy",
                     "aqc_device_name", "aqc_set_config", "aqc_set_circles", "aqc_reset_stats", "aqc_upload", "aqc_run",
-                    "aqc_qc_stat", "aqc_fetch_results", "aqc_fetch_quality_views", "aqc_error_record", "aqc_sync", "aqc_last_deferred", "aqc_kernel_ms", "aqc_timing_reset",
+                    "aqc_qc_stat", "aqc_fetch_results", "aqc_fetch_quality_views", "aqc_error_record", "aqc_sync", "aqc_last_deferred", "aqc_last_verdict_words", "aqc_kernel_ms", "aqc_timing_reset",
                     "aqc_timing_mean", "aqc_get_counters",
                     "aqc_get_histograms", "aqc_get_qc", "aqc_get_kmers", "aqc_overlap", "aqc_read_stats",
                     "aqc_edit_distance", "aqc_frame", "aqc_frame_mixed", "aqc_reframe", "aqc_format", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused", "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms", "aqc_format_plain", "aqc_fetch_text", "aqc_fetch_streams", "aqc_compress", "aqc_fetch_gz", "aqc_gunzip_dev", "aqc_bunzip2_dev", "aqc_gunzip_probe", "aqc_host_alloc",
@@ -550,6 +552,14 @@ class Engine:
         idx = np.zeros(max(cap, 1), dtype=np.uint32)
         self._check(self.lib.aqc_last_deferred(self.h, slot, _ptr(idx), cap, C.byref(n)))
         return (int(n.value), idx[:min(int(n.value), cap)]) if want_indices else int(n.value)
+
+    def last_verdict_words(self, slot):
+        """which verdict kernel the slot's last run() launched: 0 the general kernel, else the words per read (10, 16, 18, 20) of
+        the lane-per-pair instance"""
+        w = self.lib.aqc_last_verdict_words(self.h, slot)
+        if w < 0:
+            self._check(w)
+        return int(w)
 
     def kernel_ms(self, slot):
         ms = np.zeros(N_KERNELS, dtype=np.float32)

@@ -1,5 +1,5 @@
 // aqc_capi_run.hip — the C API's verdict stage: a batch up to the device (aqc_upload), the verdict kernels (aqc_run), the results
-// back (aqc_fetch_results, aqc_fetch_quality_views, aqc_last_deferred), the three function seams and the libed.so pair; and the
+// back (aqc_fetch_results, aqc_fetch_quality_views, aqc_last_deferred, aqc_last_verdict_words), the three function seams and the libed.so pair; and the
 // .gz output stage (aqc_compress, aqc_fetch_gz).  The context, its slots and the shared helpers: aqc_ctx.hpp.
 //
 // Why .gz out is here and not in a unit of its own: gz_encode_kernel does not compile to the same instructions there.  In a unit
@@ -38,6 +38,14 @@
 using namespace aqc;
 
 constexpr int FUSE_WPBT = 12;      // waves per workgroup of the fused verdict kernel
+// waves per workgroup of the 20-word tier's paired instances: 10 or 11 fit the CU's 160 KiB of LDS (144,048 / 157,568 bytes).  11 by
+// measurement: 3 - 4 % faster than 10 at 2 x 300 and 2 x 317, interleaved builds (profiles/r14_tier20.txt); -DAQC_TIER20_WPBT=10
+// builds the other one to repeat it
+#ifndef AQC_TIER20_WPBT
+#define AQC_TIER20_WPBT 11
+#endif
+constexpr int TIER20_WPBT_PAIRED = AQC_TIER20_WPBT;
+static_assert(TIER20_WPBT_PAIRED == 10 || TIER20_WPBT_PAIRED == 11, "the 20-word rows of 10 or 11 waves fit a CU's LDS");
 template <int NW, bool PAIRED, int WPBT, bool BARCODE, bool FUSE = false>
 static void launch_fast(aqc_ctx* c, Slot* s, const aqc_config& cfg, const DevStats& st, uint64_t accum_limit, const FuseArgs* fz = nullptr) {
     constexpr uint64_t per_block = (uint64_t)WPBT * FastWaveLds<NW, PAIRED, FUSE>::PPW;
@@ -139,7 +147,7 @@ static int fill_slot(aqc_ctx* c, Slot& s, const aqc_batch* b, bool need_qual, bo
     if (need_pair && !paired) return fail(AQC_ERR_ARG, "batch: this call needs seq2/off2/len2");
     if (paired && (!b->off2 || !b->len2)) return fail(AQC_ERR_ARG, "batch: off2/len2 missing");
     if (n >= (1ull << 31)) return fail(AQC_ERR_ARG, "batch: more than 2^31 records (split the batch)");
-    const uint64_t lim = (1ull << 32) - 4096;      // 32-bit byte offsets on the device, chunk loads may run 288 bytes past a read's start
+    const uint64_t lim = (1ull << 32) - 4096;      // 32-bit byte offsets on the device, chunk loads may run 320 bytes (16 x the widest tier's 20 words) past a read's start
     if (b->bytes1 >= lim || b->qbytes1 >= lim || b->bytes2 >= lim || b->qbytes2 >= lim) return fail(AQC_ERR_ARG, "batch: an arena must be smaller than 4 GiB (split the batch)");
     // make sure earlier work on this slot has drained before its buffers are overwritten / regrown
     HIP_TRY(slot_sync(s));
@@ -202,8 +210,10 @@ static int grid_for(const aqc_ctx* c, uint64_t n) {
 }
 
 // What aqc_run launches for the slot's records: the general wave-per-record kernel, or the lane-per-pair kernel whenever its
-// preconditions hold: one of its three tiers by the longest read, or its fused instance.
-enum class Verdict { GENERAL, TIER10, TIER16, TIER18, FUSED };
+// preconditions hold: one of its four tiers by the longest read, or its fused instance.
+enum class Verdict { GENERAL, TIER10, TIER16, TIER18, TIER20, FUSED };
+// words per read of the lane-per-pair instance (aqc_last_verdict_words); 0: the general kernel
+static int verdict_words(Verdict k) { return k == Verdict::GENERAL ? 0 : k == Verdict::TIER16 ? 16 : k == Verdict::TIER18 ? 18 : k == Verdict::TIER20 ? 20 : 10; }
 static Verdict choose_verdict_kernel(const aqc_ctx* c, const Slot& s, const aqc_config& cfg) {
     const int thr = cfg.qualified_quality_phred + 33;
     // barcodes on that kernel: detectBarcode's three windows must lie in the first 32 bases and the verify sequence must
@@ -216,7 +226,7 @@ static Verdict choose_verdict_kernel(const aqc_ctx* c, const Slot& s, const aqc_
             barcode_ok = ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T';
         }
     }
-    if (c->force_generic || !barcode_ok || thr < 0 || thr > 127 || s.max_len > 288 || s.max_len == 0) return Verdict::GENERAL;
+    if (c->force_generic || !barcode_ok || thr < 0 || thr > 127 || s.max_len > 320 || s.max_len == 0) return Verdict::GENERAL;
     // AQC_FUSED=1: pairs of device-framed text whose records are plain four-line text are placed in their output
     // streams by the verdict kernel itself, which also copies the good records that go out as their own bytes
     // (31-bit stream offsets; a bad record grows by its flag text)
@@ -224,7 +234,8 @@ static Verdict choose_verdict_kernel(const aqc_ctx* c, const Slot& s, const aqc_
         s.m[1].consumed + 16 * s.n < (1ull << 31))
         return Verdict::FUSED;
     // (TIER18, 257 .. 288 bases: 2x250 reads that still carry a barcode + verify prefix (BASELINE config 5: 267 bases))
-    return s.max_len <= 160 ? Verdict::TIER10 : s.max_len <= 256 ? Verdict::TIER16 : Verdict::TIER18;
+    // (TIER20, 289 .. 320 bases: the 2x300 kit, written as 300 or 301 cycles, with or without that prefix (317 bases))
+    return s.max_len <= 160 ? Verdict::TIER10 : s.max_len <= 256 ? Verdict::TIER16 : s.max_len <= 288 ? Verdict::TIER18 : Verdict::TIER20;
 }
 
 // the fused placement's buffers: look-back words per batch, position words per record, ticket | abort | totals, the two good streams
@@ -250,6 +261,7 @@ int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
     if (c->cfg.paired && !s->paired) return fail(AQC_ERR_STATE, "config says paired but the slot holds single-end records");
     if (c->cfg.debubble && c->circles.n > 0 && !s->view.aux_ok) return fail(AQC_ERR_ARG, "debubble needs the aux_* arrays");
     s->fused = false;
+    s->verdict_words = 0;
     if (s->n == 0) { s->ran = true; return 0; }
     aqc_config cfg = c->cfg;
     if (!cfg.paired) cfg.no_overlap = 1;
@@ -259,6 +271,7 @@ int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
     HIP_TRY(hipEventRecord(launch_event(*s, AQC_K_FILTER_OVERLAP, 0), s->stream));
     const Verdict k = choose_verdict_kernel(c, *s, cfg);
     s->used_fast = k != Verdict::GENERAL;
+    s->verdict_words = verdict_words(k);
     if (k == Verdict::GENERAL) {
         hipLaunchKernelGGL(filter_overlap_kernel, dim3(grid_for(c, s->n)), dim3(BLOCK), 0, s->stream, s->view, cfg, c->circles,
                            (aqc_result*)s->results.p, st, accum_limit);
@@ -273,7 +286,8 @@ int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
             s->fused = true;
         } else if (k == Verdict::TIER10) launch_fast_tier<10, 16, 12>(c, s, cfg, st, accum_limit);
         else if (k == Verdict::TIER16) launch_fast_tier<16, 12, 11>(c, s, cfg, st, accum_limit);
-        else launch_fast_tier<18, 12, 10>(c, s, cfg, st, accum_limit);
+        else if (k == Verdict::TIER18) launch_fast_tier<18, 12, 10>(c, s, cfg, st, accum_limit);
+        else launch_fast_tier<20, TIER20_WPBT_PAIRED, 9>(c, s, cfg, st, accum_limit);
         hipLaunchKernelGGL(filter_overlap_list_kernel, dim3((unsigned)c->n_cu), dim3(BLOCK), 0, s->stream, s->view, cfg, c->circles,
                            (aqc_result*)s->results.p, st, accum_limit, (const uint32_t*)s->deferred.p,
                            (const unsigned int*)s->n_deferred.p);
@@ -307,6 +321,13 @@ int aqc_fetch_quality_views(aqc_ctx* c, int slot, int mate, uint32_t* out, uint6
     HIP_TRY(hipMemcpyAsync(out, s->off_stage.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(slot_sync(*s));
     return 0;
+}
+
+// (host state only: set by aqc_run when it chose the kernel, so there is nothing to wait for)
+int aqc_last_verdict_words(aqc_ctx* c, int slot) {
+    GET_SLOT(s);
+    if (!s->ran) return fail(AQC_ERR_STATE, "aqc_last_verdict_words before aqc_run");
+    return s->verdict_words;
 }
 
 int aqc_last_deferred(aqc_ctx* c, int slot, uint32_t* idx, uint64_t cap, uint64_t* n) {

@@ -74,6 +74,7 @@ struct __attribute__((visibility("hidden"))) Slot {
     DevBatch view{};
     uint64_t n = 0;
     bool paired = false, ran = false, used_fast = false;
+    int verdict_words = 0;         // words per read of the lane-per-pair instance the last aqc_run launched, 0: the general kernel
     // AQC_FUSED=1: the verdict kernel placed the slot's records in their streams and copied the whole good ones (aqc_fast.hpp, FUSE)
     DevBuf fz_state, fz_misc;                 // look-back words per batch (Mate::fz_rec: position words per record); ticket | abort | totals[4]
     bool fused = false;                       // ... for the records the slot holds now (aqc_format checks fz_misc's abort word)
@@ -143,7 +144,7 @@ static const StatusWords STATUS_CLEAR{0, 0, ~0ull};
 static unsigned long long* err_key_of(const Slot& sl) { return reinterpret_cast<unsigned long long*>(sl.status + 2); }
 
 // (ARENA_SLACK readable bytes behind every arena: the lane-per-read kernel always loads whole 16-byte chunks, up to
-// 256 bytes from the start of a read whatever its length)
+// 320 bytes — 16 x the widest tier's 20 words — from the start of a read whatever its length)
 constexpr size_t ARENA_SLACK = 1024;
 constexpr size_t TEXT_FRONT = 64;
 

@@ -309,7 +309,8 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < FAST_MIN_WAVES ? (WPB
     // per-lane running totals, reduced once at the end of the kernel
     // (packed: R0 = records | good | adapter reads | overlapped, 8 bits each; R1 = total bases | good bases, R2 = adapter bases |
     //  overlap length, 16 bits each; R3 = distance | corrected reads | corrected bases | masked, R4 = skipped, 8 bits each.  A
-    //  lane adds at most 1 / 576 / 3 to a field per batch, so the wave flushes every 64 batches — five live registers, not 13)
+    //  lane adds at most 1 / 640 (two reads of the widest tier's 320 bases) / 3 to a field per batch, so the wave flushes every 64
+    //  batches, at 40,960 < 2^16 — five live registers, not 13)
     uint32_t R0 = 0, R1 = 0, R2 = 0, R3 = 0, R4 = 0;
     int since_flush = 0;
     auto flush_totals = [&]() {

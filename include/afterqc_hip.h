@@ -246,6 +246,12 @@ int aqc_qc_stat(aqc_ctx* ctx, int slot, int which, int mate, uint64_t first, uin
  * general wave-per-record kernel (bytes outside A C G T N, reads under 16 bases, the second-scan corner of the adapter
  * cut, ...).  *n = their number; up to `cap` record indices go to idx (may be NULL).  Results are identical either way. */
 int aqc_last_deferred(aqc_ctx* ctx, int slot, uint32_t* idx, uint64_t cap, uint64_t* n);
+/* diagnostics: which verdict kernel the slot's last aqc_run launched.  0: the general wave-per-record kernel decided every record
+ * (a read over 320 bases, options the lane-per-pair kernel does not take, AQC_FORCE_GENERIC=1, an empty batch); otherwise the
+ * words of 16 bases per read of the lane-per-pair instance: 10 (reads <= 160 bases, the fused instance included), 16 (<= 256),
+ * 18 (<= 288) or 20 (<= 320).  AQC_ERR_STATE before the slot's first aqc_run and after a new upload / frame.  Host state only:
+ * the call never waits for the device. */
+int aqc_last_verdict_words(aqc_ctx* ctx, int slot);
 /* wait for the slot and copy its n result records to `out` */
 int aqc_fetch_results(aqc_ctx* ctx, int slot, aqc_result* out, uint64_t n);
 int aqc_sync(aqc_ctx* ctx, int slot);
