@@ -52,6 +52,8 @@ OPTIONS = [
     ("", "--barcode_verify", dict(default="CAGTA", help="specify the verify sequence of a barcode which is adjunct to the barcode")),
     ("", "--store_overlap", dict(default="off", help="specify whether store only overlapped bases of the good reads")),
     ("", "--overlap_output_folder", dict(default=None, help="the folder to store only overlapped bases of the good reads")),
+    ("", "--store_merged", dict(default="off", help="specify whether to write every good pair whose overlap came out clean (the pairs --store_overlap selects) once, as a merged read: read 1 followed by the reverse complement of the part of read 2 that lies outside the overlap; paired input only, not together with --store_overlap on")),
+    ("", "--merged_output_folder", dict(default=None, help="the folder to store the merged reads, by default it is named 'merged', in the same folder as good_output_folder")),
     ("", "--qc_only", dict(action="store_true", default=False, help="if qconly is true, only QC result will be output, this can be much fast")),
     ("", "--qc_sample", dict(default=200000, type="int", help="sample up to qc_sample reads when do QC, 0 means sample all reads. Default is 200,000")),
     ("", "--qc_kmer", dict(default=8, type="int", help="specify the kmer length for KMER statistics for QC, default is 8")),
@@ -82,6 +84,11 @@ def finalize_options(options):
     options.trim_pair_same = parseBool(options.trim_pair_same)
     options.draw = parseBool(options.draw)
     options.store_overlap = parseBool(options.store_overlap)
+    options.store_merged = parseBool(options.store_merged)
+    if options.store_merged and options.store_overlap:
+        # (both are the device writer's third stream: one of them per run)
+        raise SystemExit("afterqc_amd: --store_merged on and --store_overlap on exclude each other (the writer has one third "
+                         "output stream per file); run them separately")
     options.trim_front2 = options.trim_front
     options.trim_tail2 = options.trim_tail
     return options

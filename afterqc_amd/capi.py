@@ -21,6 +21,9 @@ FLAG_NAMES = ["GOOD", "BADBCD1", "BADBCD2", "BADTRIM1", "BADTRIM2", "BADBBL", "B
  BADMISMATCH) = range(12)
 N_FLAGS = 12
 EDIT_FIX_R2, EDIT_FIX_R1, EDIT_MASK = 1, 2, 3
+# the `store_overlap` argument of the format calls and the pipe is a mode: off, the overlap tails (--store_overlap; True), or the same
+# pairs written once as merged reads in file 0's third stream (--store_merged)
+STORE_OFF, STORE_OVERLAP, STORE_MERGED = 0, 1, 2
 
 # enum aqc_counter
 C_TOTAL_READS, C_TOTAL_BASES, C_GOOD_READS, C_GOOD_BASES, C_FLAG0 = 0, 1, 2, 3, 4
@@ -466,6 +469,8 @@ EXPORTED_SYMBOLS = ["aqc_abi_version", "aqc_device_count", "aqc_device_index", "
 class Engine:
     """One GPU context (struct aqc_ctx).  Thin, 1:1 with the C ABI."""
 
+    formats_merged = True        # format(..., STORE_MERGED) writes merged reads (an engine without this takes the host-side writer)
+
     def __init__(self, device=0, n_slots=2):
         self.lib = load_library()
         if self.lib.aqc_device_count() <= 0:
@@ -624,9 +629,10 @@ class Engine:
         return info
 
     def format(self, slot, n, store_overlap=False):
-        """sizes[file * 3 + stream], stream 0 good / 1 bad / 2 overlap"""
+        """sizes[file * 3 + stream], stream 0 good / 1 bad / 2 overlap; store_overlap: STORE_OFF / STORE_OVERLAP (or True) /
+        STORE_MERGED (stream 2 of file 0 holds the merged reads, of file 1 nothing)"""
         sizes = np.zeros(6, dtype=np.uint64)
-        self._check(self.lib.aqc_format(self.h, slot, int(n), 1 if store_overlap else 0, _ptr(sizes)))
+        self._check(self.lib.aqc_format(self.h, slot, int(n), int(store_overlap), _ptr(sizes)))
         return [int(x) for x in sizes]
 
     def format_spans(self, slot, n, store_overlap=False):
@@ -634,7 +640,7 @@ class Engine:
         -> (bytes per stream, events per file)"""
         sizes = (C.c_uint64 * 6)()
         n_ev = (C.c_uint64 * 2)()
-        self._check(self.lib.aqc_format_spans(self.h, slot, n, 1 if store_overlap else 0, sizes, n_ev))
+        self._check(self.lib.aqc_format_spans(self.h, slot, n, int(store_overlap), sizes, n_ev))
         return [int(x) for x in sizes], [int(x) for x in n_ev]
 
     def fetch_span_events(self, slot, file, n_events):
@@ -675,7 +681,7 @@ class Engine:
     def format_plain(self, slot, verdict_slot, n, store_overlap=False):
         """index files: whole records of `slot`, routed / renamed by the verdicts of `verdict_slot`"""
         sizes = np.zeros(6, dtype=np.uint64)
-        self._check(self.lib.aqc_format_plain(self.h, slot, verdict_slot, int(n), 1 if store_overlap else 0, _ptr(sizes)))
+        self._check(self.lib.aqc_format_plain(self.h, slot, verdict_slot, int(n), int(store_overlap), _ptr(sizes)))
         return [int(x) for x in sizes]
 
     def compress(self, slot, level=2):
@@ -743,7 +749,8 @@ class Pipe:
     def run(self, inputs, outputs=None, gzip_in=(False, False), gzip_out=False, gzip_level=2, chunk_records=0, qc_sample=200000,
             store_overlap=False, no_output=False, chunk_index0=0, chunk_index_stride=1):
         """inputs: list of 1-2 file names, or of (numpy uint8 array / HostBuffer.array, nbytes) tuples (text in memory);
-        outputs: per input (good, bad, overlap) file names or None.  gzip_level 1 - 9 goes to aqc_compress as it is (1 - 5: the fast
+        outputs: per input (good, bad, overlap) file names or None; store_overlap: the mode of Engine.format (STORE_MERGED: the third
+        name of input 0 is the merged file, of input 1 None).  gzip_level 1 - 9 goes to aqc_compress as it is (1 - 5: the fast
         device encoder, 6 - 9: its hash-chain search), 0 writes stored members on the host.  Returns a PipeResult."""
         io = PipeIO()
         keep = []
@@ -769,7 +776,7 @@ class Pipe:
                         io.out_path[k][st] = b
         io.gzip_out = 1 if gzip_out else 0
         io.gzip_level = int(gzip_level)
-        opts = PipeOpts(int(chunk_records), int(qc_sample), 1 if store_overlap else 0, 1 if no_output else 0, int(chunk_index0),
+        opts = PipeOpts(int(chunk_records), int(qc_sample), int(store_overlap), 1 if no_output else 0, int(chunk_index0),
                         int(chunk_index_stride))
         res = PipeResult()
         rc = self.lib.aqc_pipe_run(self.h, C.byref(io), C.byref(opts), C.byref(res))

@@ -268,7 +268,8 @@ static FormatView make_format_view(const aqc_ctx* c, const Slot* s, const Slot* 
     v.verdict_paired = vs->paired ? 1 : 0;
     v.barcode = c->cfg.barcode ? 1 : 0;
     v.barcode_length = c->cfg.barcode_length;
-    v.store_overlap = (store_overlap && vs->paired) ? 1 : 0;
+    // the third stream's mode: off, the merged reads of --store_merged, or (any other value) the overlap tails
+    v.store_overlap = !(store_overlap && vs->paired) ? 0 : store_overlap == AQC_STORE_MERGED ? AQC_STORE_MERGED : AQC_STORE_OVERLAP;
     v.spans = (spans && !plain) ? 1 : 0;
     v.n_framed = s->n;
     v.consumed[0] = (uint32_t)s->m[0].consumed; v.consumed[1] = (uint32_t)s->m[1].consumed;
@@ -438,6 +439,15 @@ static int format_impl(aqc_ctx* c, int slot, int verdict_slot, uint64_t n, int32
         FormatLayout L;
         if ((rc = carve_format_buffers(s, n, n_tiles, L))) return rc;
         for (int pass = 0; pass < (v.store_overlap ? 2 : 1); ++pass) {
+            if (pass == 1 && v.store_overlap == AQC_STORE_MERGED) {
+                // the merged reads: a kernel of its own, file 0's third stream (index records have none)
+                if (!plain) {
+                    const unsigned long long* tb = (const unsigned long long*)s->f_tile.p;
+                    hipLaunchKernelGGL(fmt_merged_kernel, dim3((unsigned)n_tiles), dim3(FMT_TILE), 0, s->stream, v, n, n_tiles, n_super, tb, tb + FMT_STREAMS * n_tiles,
+                                       s->status, outs.p[2]);
+                }
+                continue;
+            }
             HIP_TRY(hipMemsetAsync(L.n_gen, 0, 2 * sizeof(unsigned int) * GEN_LISTS, s->stream));
             write_pass(s, v, L, outs, pass, n, n_tiles, n_super);
         }

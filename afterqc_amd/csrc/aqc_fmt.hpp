@@ -52,7 +52,8 @@ struct FormatView {
     int paired;
     int barcode;          // options.barcode: moveBarcodeToName (barcodeprocesser.py:34-45) rewrites the names
     int barcode_length;
-    int store_overlap;    // --store_overlap: third stream with the overlapped tails of good pairs (preprocesser.py:78-84,614-616)
+    int store_overlap;    // --store_overlap: third stream with the overlapped tails of good pairs (preprocesser.py:78-84,614-616);
+                          // AQC_STORE_MERGED (--store_merged): the same pairs as merged reads in file 0's third stream, file 1's empty
     int plain;            // index files (-7 / -5): records are written whole (no trim, no edits, no barcode move); only
                           // the verdicts — of the read pairs in `results` — route them and rename the bad ones
     int verdict_paired;   // the verdicts belong to read PAIRS (overlap stream exists)
@@ -116,6 +117,21 @@ __device__ __forceinline__ bool in_overlap_stream(const FormatView& v, const uin
         }
     }
     return dist == 0 || dist == corrected;
+}
+
+// ---- --store_merged (store_overlap == AQC_STORE_MERGED): the pairs of the overlap stream, each written ONCE ---------------------------
+//     name 1 | s1 + reverseComplement(s2[0:p]) | strand line 1 | q1 + reversed(q2[0:p])          p = len(s2) - overlap_len
+// with s, q as the good streams hold them.  The walk's edits all lie inside the overlap: s2[0:p] and q2[0:p] are raw text.
+__device__ __forceinline__ uint32_t merged_tail_len(const uint4& w0) {
+    const int p = (int)(w0.z & 0xffffu) - (int)(w0.w & 0xffffu);
+    return (uint32_t)max(p, 0);
+}
+// read 2's quality line, as written to good, is as long as its sequence line (else the pair has no merged read: DESIGN §7)
+__device__ __forceinline__ bool merged_mate2_regular(const TextFile& t2, uint64_t r, uint32_t len2) {
+    if (!(t2.plus_len[r] & LEN_IRR)) return true;
+    int qs_, ql_;
+    irregular_quality_slice(t2, r, 0, 0, 0, qs_, ql_);
+    return (uint32_t)ql_ == len2;
 }
 
 
@@ -189,7 +205,11 @@ __device__ __forceinline__ void fmt_sizes(const FormatView& v, uint64_t r, int f
     sz[2] = 0u;
     if (v.store_overlap) {
         const uint4 w1 = *(reinterpret_cast<const uint4*>(v.results + r) + 1);
-        if (in_overlap_stream(v, w0, w1)) {
+        if (v.store_overlap == AQC_STORE_MERGED) {
+            // the pair written once: read 1's good record with p = len2 - overlap_len bytes more in each of its two lines
+            if (file == 0 && !v.plain && qlen == len && in_overlap_stream(v, w0, w1) && merged_mate2_regular(v.f[1], r, w0.z & 0xffffu))
+                sz[2] = body + len + qlen + 2u * merged_tail_len(w0);
+        } else if (in_overlap_stream(v, w0, w1)) {
             const uint32_t olen = v.plain ? len : (w0.w & 0xffffu);                                   // getOverlap: the last overlap_len bases
             uint32_t oq = v.plain ? qlen : olen;
             if ((slw & LEN_IRR) && !v.plain) {

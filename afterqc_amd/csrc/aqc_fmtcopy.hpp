@@ -8,6 +8,7 @@
 #include "aqc_prim.hpp"       // WAVE, lane_id, gload_* / gstore_*, load16u / store16u, wave_incl_sum, block_excl_scan
 #include "aqc_batch.hpp"      // the marks in a framed chunk's length words: LEN_IRR, LEN_MASK, QLEN_CONTIG
 #include "aqc_fmt.hpp"        // the format model: FormatView, fmt_sizes, FmtTask, fmt_build, FormatOut, the FMT_* tile sizes
+#include "aqc_revcopy.hpp"    // the reversed 16-byte windows of the merged-read pass
 
 namespace aqc {
 
@@ -706,6 +707,128 @@ __global__ __launch_bounds__(FMT_TILE) void fmt_plan_listed_kernel(FormatView v,
         }
         uint4* const pg = plan_gen + slot * PLAN_Q;
         pg[0] = q0; pg[1] = q1; pg[2] = q2; pg[3] = q3; pg[4] = q4; pg[5] = q5;
+    }
+}
+
+// ---- --store_merged: the second pass of a format in mode AQC_STORE_MERGED, a kernel of its own ---------------------------------------
+// The merged read of a pair is read 1's GOOD record G (fmt_build's piece list of the main pass, the walk's patches included) with
+// p bytes put in behind its bases (at G's offset i1) and p behind its qualities (at i2):
+//     G[0:i1] | reverseComplement(s2[0:p]) | G[i1:i2] | reversed(q2[0:p]) | G[i2:]
+// A workgroup takes a tile of FMT_TILE records.  Thread = record: its bytes (fmt_sizes — the sizing pass's routine), its place (one
+// block scan + the tile's base), read 1's piece list into LDS.  Then a half-wave per merged record: every piece of G is cut at i1
+// and i2 and copied 16 bytes per lane (the pieces' last windows end-aligned, pieces of < 16 bytes a byte per lane), the two tails
+// go out through the reversed windows of aqc_revcopy.hpp — seq and quality windows side by side in one round of the 32 lanes
+// up to p = 240 —, the walk's patches go on top, moved by p where they lie in G's quality line.
+struct MergedRec {
+    uint32_t pos;          // offset of the merged read in stream [0][2]; the record has none: total == 0
+    uint32_t total;        // bytes of G
+    uint32_t i1, i2, p;
+    uint32_t src_s2, src_q2;      // text offsets (file 1) of s2[0], q2[0]
+};
+
+__device__ __forceinline__ void merged_store_low(uint8_t* d, const RevWin& v, uint32_t n) {      // the low n < 16 bytes of v: 8 + 4 + 2 + 1
+    uint32_t vx = v.x, vy = v.y, vz = v.z, vw = v.w;
+    asm volatile("" : "+v"(vx), "+v"(vy), "+v"(vz), "+v"(vw));      // (values, not addresses: a select of loads would put v into scratch)
+    const uint32_t i2 = (n >> 2) & 3u;
+    const uint32_t pick = i2 == 0u ? vx : i2 == 1u ? vy : i2 == 2u ? vz : vw;                     // the word of byte (n & 12)
+    if (n & 8u) gstore_u64(d, vx, vy);
+    if (n & 4u) gstore_u32(d + (n & 8u), (n & 8u) ? vz : vx);
+    if (n & 2u) gstore_u16(d + (n & 12u), (uint16_t)pick);
+    if (n & 1u) gstore_u8(d + (n & 14u), (uint8_t)(pick >> ((n & 2u) * 8u)));
+}
+
+__global__ __launch_bounds__(FMT_TILE) void fmt_merged_kernel(FormatView v, uint64_t n, uint64_t n_tiles, uint64_t n_super,
+                                                              const unsigned long long* __restrict__ tile_base, const unsigned long long* __restrict__ super_base,
+                                                              int* __restrict__ status, uint8_t* __restrict__ out) {
+    __shared__ unsigned long long lds[4];
+    __shared__ FmtTask tasks[FMT_TILE];
+    __shared__ MergedRec recs[FMT_TILE];
+    const uint64_t r = (uint64_t)blockIdx.x * FMT_TILE + threadIdx.x;
+    uint32_t sz[3] = {0, 0, 0}, ev = 0;
+    MergedRec m{0, 0, 0, 0, 0, 0, 0};
+    if (r < n) {
+        fmt_sizes(v, r, 0, sz, ev);
+        if (sz[2]) {
+            FmtTask& t = tasks[threadIdx.x];
+            fmt_build(v, r, 0, 0, t, status);
+            const uint4 w0 = *reinterpret_cast<const uint4*>(v.results + r);
+            const uint32_t len1 = w0.y & 0xffffu;
+            m.p = merged_tail_len(w0);
+            m.total = t.stream == 0 ? (uint32_t)t.total : 0u;                      // (0xff: a 64 KiB record, the status says so)
+            // G = name | \n | bases | \n | strand line | \n | qualities | \n, bases and qualities len1 bytes each (a regular pair)
+            m.i2 = m.total - 1u;
+            m.i1 = m.total - 1u - len1 - 1u - (v.f[0].plus_len[r] & LEN_MASK) - 1u;
+            const TextFile& t2 = v.f[1];
+            const uint32_t st2 = w0.y >> 16;
+            int qst = (int)st2, ql_ = 0;
+            if (t2.plus_len[r] & LEN_IRR) irregular_quality_slice(t2, r, 0, 0, 0, qst, ql_);
+            m.src_s2 = t2.seq_off[r] + st2;
+            m.src_q2 = t2.qual_off[r] + (uint32_t)qst;
+            if (!m.total) sz[2] = 0u;
+        }
+    }
+    unsigned long long to;
+    const unsigned long long eo = block_excl_scan((unsigned long long)sz[2], lds, to);
+    m.pos = (uint32_t)(super_base[(uint64_t)2 * n_super + blockIdx.x / FMT_SUPER] + tile_base[(uint64_t)2 * n_tiles + blockIdx.x] + eo);
+    recs[threadIdx.x] = m;
+    __syncthreads();
+    const uint32_t lane32 = threadIdx.x & 31u, hwi = threadIdx.x >> 5;
+    const uint8_t* const text1 = v.f[0].text;
+    const uint8_t* const text2 = v.f[1].text;
+#pragma unroll 1
+    for (int i = (int)hwi; i < FMT_TILE; i += FMT_TILE / 32) {
+        const MergedRec& mr = recs[i];
+        if (!mr.total) continue;
+        const FmtTask& t = tasks[i];
+        uint8_t* const out0 = out + mr.pos;
+        const uint32_t p = mr.p;
+        // read 1's record, cut at i1 and i2: part g goes out g * p bytes further on
+        const int np = (int)t.np;
+        for (int k = 0; k < np; ++k) {
+            const uint32_t sk = t.p[k].src, d0 = t.p[k].dst, d1 = d0 + t.p[k].len;
+            const uint8_t* const src = (sk & FMT_LIT_BIT) ? &FMT_LIT[0][0] + (sk & ~FMT_LIT_BIT) : text1 + sk;
+            auto part = [&](uint32_t from, uint32_t to, uint32_t shift) {
+                const uint32_t lo = max(d0, from), hi = min(d1, to);
+                if (hi <= lo) return;
+                const uint32_t len = hi - lo;
+                const uint8_t* const s = src + (lo - d0);
+                uint8_t* const d = out0 + lo + shift;
+                if (len >= 16u) {
+                    for (uint32_t w0 = 16u * lane32; w0 < len; w0 += 16u * 32u) {
+                        const uint32_t off = min(w0, len - 16u);
+                        store16u(d + off, load16u(s + off));
+                    }
+                } else if (lane32 < len) d[lane32] = s[lane32];
+            };
+            part(0u, mr.i1, 0u);
+            part(mr.i1, mr.i2, p);
+            part(mr.i2, mr.total, 2u * p);
+        }
+        // the two tails: work items [0, ni) the bases, [ni, 2 ni) the qualities
+        if (p) {
+            const uint32_t a_s = (0u - (uint32_t)(uintptr_t)(text2 + mr.src_s2)) & 15u, a_q = (0u - (uint32_t)(uintptr_t)(text2 + mr.src_q2)) & 15u;
+            const uint32_t ni_s = revc_items(p, a_s), ni_q = revc_items(p, a_q);
+            for (uint32_t it = lane32; it < ni_s + ni_q; it += 32u) {
+                const bool qual = it >= ni_s;
+                const int off = revc_src_off(p, qual ? a_q : a_s, qual ? it - ni_s : it);
+                const uint4 ld = load16u(text2 + (qual ? mr.src_q2 : mr.src_s2) + off);
+                RevWin wv = revc_reverse(RevWin{ld.x, ld.y, ld.z, ld.w});
+                const RevWin cv = revc_comp16(wv);
+                if (!qual) wv = cv;
+                uint8_t* const d = out0 + (qual ? mr.i2 + p : mr.i1) + revc_dst_off(p, off);
+                if (p >= 16u) store16u(d, make_uint4(wv.x, wv.y, wv.z, wv.w));
+                else merged_store_low(d, wv, p);
+            }
+        }
+        if (t.n_patch) {
+            // byte patches on top of the copies (the copies of this wave are complete first)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_s_waitcnt(0);
+            if (lane32 < (uint32_t)t.n_patch) {
+                const uint32_t pt = t.patch[lane32], at = pt & 0xffffu;
+                out0[at + (at >= mr.i1 ? p : 0u)] = (uint8_t)(pt >> 16);
+            }
+        }
     }
 }
 

@@ -60,6 +60,28 @@ def input_files(opt):
     return [opt.read1_file, opt.read2_file, opt.index1_file, opt.index2_file]
 
 
+def third_stream_mode(opt, paired):
+    """What the writers' third stream per file holds (capi.STORE_*): nothing, the overlap tails of --store_overlap, or — pairs
+    only — the merged reads of --store_merged (after.finalize_options refuses the two together)."""
+    if getattr(opt, "store_merged", False):
+        return capi.STORE_MERGED if paired else capi.STORE_OFF
+    return capi.STORE_OVERLAP if opt.store_overlap else capi.STORE_OFF
+
+
+def merged_record(name1, s1, p1, q1, s2, q2, ov):
+    """The merged read of a pair whose mates go to the good files as (name1, s1, p1, q1) and (.., s2, .., q2) with overlap_len
+    `ov`: read 1, then the part of read 2 outside the overlap — reverse complement (util.reverseComplement: COMP, anything
+    else 'N') and reversed qualities.  None: a mate's quality line is not as long as its sequence line, no merged read."""
+    if len(q1) != len(s1) or len(q2) != len(s2):
+        return None
+    p = len(s2) - ov
+    return (name1 + b"\n" + bytes(s1) + bytes(s2[0:p]).translate(REVCOMP_TABLE)[::-1] + b"\n" + p1 + b"\n"
+            + bytes(q1) + bytes(q2[0:p])[::-1] + b"\n")
+
+
+REVCOMP_TABLE = bytes(b"TGCAtgcaN"[b"ACGTacgtN".index(bytes([c]))] if bytes([c]) in b"ACGTacgtN" else ord("N") for c in range(256))
+
+
 def makeDict(opt):
     return {k: getattr(opt, k) for k in COMMAND_KEYS}
 
@@ -528,6 +550,11 @@ class seqFilter:
             os.makedirs(d, exist_ok=True)          # (directory mode runs several files at once)
         if opt.store_overlap and (self.paired or not opt.qc_only):
             os.makedirs(overlap_dir, exist_ok=True)   # (single-end + store_overlap: upstream opens the writer without the dir)
+        # --store_merged: read 1's third output is the merged file, read 2 and the index files have none
+        merged = third_stream_mode(opt, self.paired) == capi.STORE_MERGED and not opt.qc_only
+        if merged:
+            merged_dir = opt.merged_output_folder if getattr(opt, "merged_output_folder", None) is not None else os.path.join(parent, "merged")
+            os.makedirs(merged_dir, exist_ok=True)
         gzip_out = bool(opt.gzip) or opt.read1_file.endswith(".gz")
         ext = ".gz" if gzip_out else ""
         paths = []
@@ -538,8 +565,10 @@ class seqFilter:
             main = getMainName(f)
             # upstream opens the R1 overlap writer whenever store_overlap is on, the others only when paired
             ovl = opt.store_overlap and (k == 0 or self.paired)
-            paths.append((os.path.join(good_dir, main + ".good.fq" + ext), os.path.join(bad_dir, main + ".bad.fq" + ext),
-                          os.path.join(overlap_dir, main + ".overlap.fq" + ext) if ovl else None))
+            third = os.path.join(overlap_dir, main + ".overlap.fq" + ext) if ovl else None
+            if merged:
+                third = os.path.join(merged_dir, main + ".merged.fq" + ext) if k == 0 else None
+            paths.append((os.path.join(good_dir, main + ".good.fq" + ext), os.path.join(bad_dir, main + ".bad.fq" + ext), third))
         return qc_dir, gzip_out, paths
 
     def _pass2(self, eng, paths, gzip_out):
@@ -549,6 +578,8 @@ class seqFilter:
         opt = self.options
         indexed = opt.index1_file is not None or opt.index2_file is not None
         self.text_path = self.use_text_path and hasattr(eng, "frame")
+        if third_stream_mode(opt, self.paired) == capi.STORE_MERGED and not getattr(eng, "formats_merged", False):
+            self.text_path = False      # (an injected engine whose format() knows no merged reads: the host-side writer builds them)
         if self.text_path and self.use_pipe and not indexed and not opt.qc_only and isinstance(eng, capi.Engine):
             extra_bases = self._run_pipe(opt, paths, gzip_out)
             if extra_bases is not None:
@@ -614,7 +645,7 @@ class seqFilter:
             # (fastq.py:23-26: .gz through gzip.open, .bz2 through bz2.BZ2File upstream — here the pipe's own decoders: 1 gzip, 2 bzip2)
             res = pipe.run(files, paths[:len(files)], gzip_in=[1 if f.endswith(".gz") else 2 if f.endswith(".bz2") else 0 for f in files],
                            gzip_out=gzip_out, gzip_level=opt.compression, chunk_records=self.chunk_records, qc_sample=opt.qc_sample,
-                           store_overlap=bool(opt.store_overlap) and self.paired)
+                           store_overlap=third_stream_mode(opt, self.paired) if self.paired else capi.STORE_OFF)
         except capi.AqcError as e:
             # (an exception inside upstream's loop — capi.RECORD_ERRORS — ends the run at that record: the pipe has written
             #  everything before it and says so; there is nothing to rerun)
@@ -704,8 +735,9 @@ class seqFilter:
                 if n:
                     n, cut, death = self._judge(eng, 0, n, total)
                     if not opt.qc_only:
-                        write_streams(0, writers[:nr], eng.format(0, n, bool(opt.store_overlap)))
-                        write_streams(1, writers[nr:], eng.format_plain(1, 0, n, bool(opt.store_overlap)))
+                        mode = third_stream_mode(opt, self.paired)
+                        write_streams(0, writers[:nr], eng.format(0, n, mode))
+                        write_streams(1, writers[nr:], eng.format_plain(1, 0, n, mode))
                     if death is not None:
                         raise death
                     total += n
@@ -771,7 +803,8 @@ class seqFilter:
         files = [opt.read1_file] + ([opt.read2_file] if self.paired else [])
         inputs = [_TextInput(eng, f, self.chunk_bytes) for f in files]
         n_slots = min(2, getattr(eng, "n_slots", 1))
-        sink = _TextSink(eng, outs.per_file[:len(files)], n_slots, bool(opt.store_overlap))
+        mode = third_stream_mode(opt, self.paired)
+        sink = _TextSink(eng, outs.per_file[:len(files)], n_slots, mode)
         total = 0
         slot = 0
         cur = 0
@@ -794,7 +827,7 @@ class seqFilter:
                         if death is not None:
                             raise death
                     else:
-                        sink.emit(slot, eng.format(slot, n, bool(opt.store_overlap)), death)   # (the fetch thread releases the slot)
+                        sink.emit(slot, eng.format(slot, n, mode), death)   # (the fetch thread releases the slot)
                     total += n
                 else:
                     sink.release_slot(slot)
@@ -816,6 +849,7 @@ class seqFilter:
         vlen = len(opt.barcode_verify)
         bl = opt.barcode_length
         store = opt.store_overlap
+        merge = third_stream_mode(opt, paired) == capi.STORE_MERGED
         chunks = [[[], [], []] for _ in range(4)]      # per file: good, bad, overlap byte pieces
         rb1, rb2, rbi1, rbi2 = rbs
         flags = results["flag"]
@@ -862,9 +896,14 @@ class seqFilter:
                 name1 = b"@" + fb + name1[1:]
                 if paired:
                     name2 = b"@" + fb + name2[1:]
-            if store and paired and not opt.no_overlap and flag == capi.GOOD and ov > 30:
+            if (store or merge) and paired and not opt.no_overlap and flag == capi.GOOD and ov > 30:
                 dist = int(r["distance"])
-                if dist == 0 or dist == corrected:
+                if merge:
+                    # --store_merged: the same pairs, written once (stream 2 of read 1)
+                    rec = merged_record(name1, s1, p1, q1, s2, q2, ov) if dist == 0 or dist == corrected else None
+                    if rec is not None:
+                        chunks[0][2].append(rec)
+                elif dist == 0 or dist == corrected:
                     # getOverlap (preprocesser.py:78-84): the last overlap_len bases of both reads
                     chunks[0][2].append(name1 + b"\n" + bytes(s1[ln - ov:]) + b"\n" + p1 + b"\n" + bytes(q1[len(q1) - ov:]) + b"\n")
                     chunks[1][2].append(name2 + b"\n" + bytes(s2[ln2 - ov:]) + b"\n" + p2 + b"\n" + bytes(q2[len(q2) - ov:]) + b"\n")

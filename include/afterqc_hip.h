@@ -340,7 +340,15 @@ int aqc_reframe(aqc_ctx* ctx, int slot, aqc_frame_info* info);
  * barcodeprocesser.py:34-45).  store_overlap != 0 (--store_overlap, pairs only) adds the third stream: name / last
  * overlap_len bases / strand line / last overlap_len qualities of every good pair with overlap_len > 30 whose
  * mismatches were all corrected (getOverlap, preprocesser.py:78-84,614-616).
- * bytes_out[file * 3 + stream], stream 0 good / 1 bad / 2 overlap.  Index files are not handled here (host side). */
+ * store_overlap is a MODE: 0 no third stream; AQC_STORE_MERGED (--store_merged) the same pairs written ONCE, as merged reads, in
+ * stream [file 0][2], stream [file 1][2] empty; any other value (AQC_STORE_OVERLAP) the overlap tails above.
+ * A merged read is built from the two mates as the good streams hold them (s1, q1, s2, q2), p = len(s2) - overlap_len:
+ *     name line of read 1 / s1 + reverseComplement(s2[0:p]) / strand line of read 1 / q1 + reversed(q2[0:p])
+ * (util.reverseComplement: COMP, anything else 'N'); a pair with a mate whose written quality line is not as long as its
+ * written sequence line is left out.
+ * bytes_out[file * 3 + stream], stream 0 good / 1 bad / 2 overlap or merged.  Index files are not handled here (host side). */
+#define AQC_STORE_OVERLAP 1
+#define AQC_STORE_MERGED 2
 int aqc_format(aqc_ctx* ctx, int slot, uint64_t n, int32_t store_overlap, uint64_t bytes_out[6]);
 /* aqc_format WITHOUT the copies nobody needs.  A good record that is written as its own bytes — not trimmed, not renamed, no edit of
  * the walk in it, every line followed directly by its '\n': the bulk of a run without trimming — already stands in the chunk the
@@ -353,7 +361,9 @@ int aqc_format(aqc_ctx* ctx, int slot, uint64_t n, int32_t store_overlap, uint64
  *     aqc_frame_info when n is the slot's record count)
  * — byte for byte what aqc_format + aqc_fetch_text(file, 0) hand out.  The bad and overlap streams are as with aqc_format.
  * aqc_pipe_run writes plain-text outputs this way (writev from its page-locked input buffers): PCIe carries the good records one
- * way only.  n_events[file] events; fetch them with aqc_fetch_span_events, the streams with aqc_fetch_streams / aqc_fetch_text. */
+ * way only.  n_events[file] events; fetch them with aqc_fetch_span_events, the streams with aqc_fetch_streams / aqc_fetch_text.
+ * store_overlap: the mode of aqc_format (0 / AQC_STORE_OVERLAP / AQC_STORE_MERGED); with either third stream every good record is
+ * still sized, the merged reads of AQC_STORE_MERGED are whole records of stream [file 0][2] as aqc_format writes them. */
 typedef struct aqc_span_event {
     uint32_t in_start; /* the record's first byte in its chunk */
     uint32_t in_len;   /* the chunk bytes it takes (up to the next record's first byte) */
@@ -400,7 +410,8 @@ int aqc_census_ms(aqc_ctx* ctx, int slot, float* ms);
 int aqc_format_fused(aqc_ctx* ctx, int slot);
 /* index files (-7 / -5, preprocesser.py:222-232): the n records framed into `slot` are written WHOLE, routed and (when
  * bad) renamed by the verdicts of the read records of `verdict_slot` (same chunk, same n); the overlap stream takes
- * the whole record wherever the reads' overlap record is written (preprocesser.py:616). */
+ * the whole record wherever the reads' overlap record is written (preprocesser.py:616).  store_overlap: the mode of aqc_format;
+ * index files have no merged stream — with AQC_STORE_MERGED both third streams are empty. */
 int aqc_format_plain(aqc_ctx* ctx, int slot, int verdict_slot, uint64_t n, int32_t store_overlap, uint64_t bytes_out[6]);
 /* copy one formatted stream (file 0/1, stream 0 good / 1 bad / 2 overlap) to host memory and wait for it */
 int aqc_fetch_text(aqc_ctx* ctx, int slot, int file, int stream, uint8_t* dst, uint64_t cap);
@@ -504,7 +515,8 @@ typedef struct aqc_pipe_io {
 typedef struct aqc_pipe_opts {
     uint64_t chunk_records;        /* records per chunk (0: 131072) */
     int64_t qc_sample;             /* --qc_sample: post-filter QC while TOTAL_READS < qc_sample (<= 0: every record) */
-    int32_t store_overlap;         /* --store_overlap */
+    int32_t store_overlap;         /* the third stream's mode, as aqc_format's: 0 / AQC_STORE_OVERLAP (--store_overlap) /
+                                      AQC_STORE_MERGED (--store_merged: out_path[0][2] is the merged file, out_path[1][2] NULL) */
     int32_t no_output;             /* 1: verdicts and statistics only, no text is formatted or fetched (--qc_only style) */
     uint64_t chunk_index0;         /* this input holds chunks chunk_index0, chunk_index0 + stride, ... of a larger one: */
     uint64_t chunk_index_stride;   /*   first_index = (chunk_index0 + i * stride) * chunk_records   (0 = 1) */
