@@ -15,7 +15,8 @@
 //   bzb_scatter_kernel  a wave per candidate: the successor vector from the counts (stable counting sort: tt[j] = i << 8 | byte,
 //                       plain stores);
 //   bzb_chase_kernel    ... the chase from origPtr for nblock steps (dependent loads: the stage to watch, timed on its own);
-//   bzb_size_kernel     ... and the size the block has once its RLE1 runs are expanded.
+//   bzb_size_kernel     ... and the size the block has once its RLE1 runs are expanded (a block that ends on a run of four with
+//                       no count byte behind it is damaged: it does not chain).
 //   bzb_chain_kernel    one lane: from the bit the previous group ended on it follows  end of block == start of a candidate,
 //                       keeps what decoded, and sums the expanded sizes into the blocks' places in the group's text.
 //   bzb_expand_kernel   a wave per chained block: the runs expanded into the group's contiguous text, bzip2's CRC-32 (polynomial
@@ -297,7 +298,11 @@ BZB_HD inline bool bzb_bwt_chase(uint8_t* bw, const uint32_t* tt, uint32_t nbloc
 }
 
 // ---- RLE1 and CRC --------------------------------------------------------------------------------------------------------------------
-// four equal bytes are followed by a count byte 0..255 of further repeats; the size of pre[0, n) with its runs expanded
+// four equal bytes MUST be followed, inside the same block, by a count byte 0..255 of further repeats; behind the count byte the
+// run state starts afresh, and it never crosses a block boundary.  A block whose last four bytes are a run still waiting for
+// its count byte is damaged (libbz2 reads the count byte before it looks for the block's end and rejects the stream).
+// The size of pre[0, n) with its runs expanded, or BZB_NO_SIZE: the block ends on four equal bytes without a count byte.
+constexpr uint64_t BZB_NO_SIZE = ~0ull;
 BZB_HD inline uint64_t bzb_rle1_size(const uint8_t* pre, uint32_t n) {
     uint64_t size = 0;
     uint32_t run = 0, last = 256u;
@@ -308,14 +313,16 @@ BZB_HD inline uint64_t bzb_rle1_size(const uint8_t* pre, uint32_t n) {
         last = c;
         ++size;
     }
-    return size;
+    return run == 4u ? BZB_NO_SIZE : size;
 }
 BZB_HD inline uint32_t bzb_crc_entry(uint32_t i) {
     uint32_t c = i << 24;
     for (int k = 0; k < 8; ++k) c = (c & 0x80000000u) ? (c << 1) ^ 0x04c11db7u : c << 1;
     return c;
 }
-// the runs expanded into out[0, cap); returns the block's CRC (bzip2's: 0x04c11db7, MSB first); *written = bytes written
+// the runs expanded into out[0, cap); returns the block's CRC (bzip2's: 0x04c11db7, MSB first); *written = bytes written.
+// (Only blocks that chained come here, and a block that ends on a run without its count byte never chains — it has no size,
+//  bzb_size_kernel makes it BZB_BAD — so the rule is not stated a second time.)
 BZB_HD inline uint32_t bzb_rle1_write(const uint8_t* pre, uint32_t n, uint8_t* out, uint64_t cap, const uint32_t* crc_tab, uint64_t* written) {
     uint32_t crc = 0xffffffffu, run = 0, last = 256u;
     uint64_t o = 0;
@@ -441,7 +448,9 @@ __global__ __launch_bounds__(64) void bzb_size_kernel(BzbJob J) {
     const uint32_t c = blockIdx.x;
     if (threadIdx.x != 0 || c >= J.g) return;
     BzbBlock* const b = J.blk + c;
-    if (b->status == BZB_OK) b->out_size = bzb_rle1_size(J.bw + (size_t)c * J.slot, b->nblock);
+    if (b->status != BZB_OK) return;
+    b->out_size = bzb_rle1_size(J.bw + (size_t)c * J.slot, b->nblock);
+    if (b->out_size == BZB_NO_SIZE) { b->out_size = 0; b->status = BZB_BAD; }
 }
 
 __global__ void bzb_chain_kernel(BzbJob J) {

@@ -3,11 +3,13 @@
 // aqcbz::decode_stream (csrc/aqc_bz2.hpp) that drives the device.  No GPU, no HIP.
 //
 //   bzb_selftest <manifest>
-// a line of the manifest:  <file.bz2> <file with the expected text, or - > <window bytes> <group blocks> <text bytes per group> <exact|error>
-//   exact: the file decodes to the expected text and NO block was handed back to libbz2;  error: a negative status.
+// a line of the manifest:  <file.bz2> <file with the expected text, or - > <window bytes> <group blocks> <text bytes per group> <exact|handback|error>
+//   exact: the file decodes to the expected text and NO block was handed back to libbz2;  handback: the expected text, and at
+//   least one block was handed back (libbz2 finished the stream);  error: a negative status.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -30,6 +32,9 @@ std::vector<uint8_t> slurp(const char* path, bool* ok) {
     return v;
 }
 
+// the device's candidate list holds as many (aqc_bunzip2_offload.hip: BZB_CAND_CAP)
+constexpr size_t CAND_CAP = 65536;
+
 // what DeviceBunzip2 does with kernels, with loops
 struct CpuBlocks {
     size_t group_size = 4;
@@ -51,14 +56,19 @@ struct CpuBlocks {
             for (uint32_t s = 0; s < 64u; ++s)
                 if (((mb | me) >> s) & 1ull) cands.push_back(((word * 64u + s) << 1) | ((me >> s) & 1ull));
         }
-        *overflow = false;
+        // (more hits than the device's list holds: incomplete there, so not used here either — as DeviceBunzip2::try_scan)
+        *overflow = cands.size() > CAND_CAP;
+        if (*overflow) cands.clear();
         cand = cands;
         return true;
     }
     bool group(size_t first, size_t g, uint64_t cur, uint32_t level, aqcbz::GroupResult& R) {
         const uint32_t slot = (level * 100000u + 15u) & ~15u;
-        std::vector<uint8_t> bw(g * (size_t)slot);
-        std::vector<uint32_t> tt((size_t)slot), counts(g * 256u), idx(g), cf(256);
+        // (fresh and exactly sized for every group, so that the sanitizer build sees a step outside a slot; not zeroed — a
+        //  stream of tens of thousands of tiny blocks would spend its time there: every byte is written before it is read)
+        const std::unique_ptr<uint8_t[]> bw(new uint8_t[g * (size_t)slot]);
+        const std::unique_ptr<uint32_t[]> tt(new uint32_t[slot]);
+        std::vector<uint32_t> counts(g * 256u), idx(g), cf(256);
         std::vector<uint64_t> off(g + 1);
         std::vector<BzbBlock> blk(g);
         sel.resize(BZB_SEL_BYTES);
@@ -66,11 +76,12 @@ struct CpuBlocks {
             BzbBlock& b = blk[c];
             if (cand[first + c] & 1ull) { b = BzbBlock{}; b.status = BZB_EOS; continue; }
             BzbTables T;
-            bzb_entropy_block(comp.data(), nbits, cand[first + c] >> 1, level, T, sel.data(), bw.data() + c * slot, counts.data() + c * 256u, &b);
+            bzb_entropy_block(comp.data(), nbits, cand[first + c] >> 1, level, T, sel.data(), bw.get() + c * slot, counts.data() + c * 256u, &b);
             if (b.status != BZB_OK) continue;
-            if (!bzb_bwt_scatter(bw.data() + c * slot, tt.data(), b.nblock, b.orig_ptr, counts.data() + c * 256u, cf.data()) ||
-                !bzb_bwt_chase(bw.data() + c * slot, tt.data(), b.nblock, b.orig_ptr)) { b.status = BZB_BAD; continue; }
-            b.out_size = bzb_rle1_size(bw.data() + c * slot, b.nblock);
+            if (!bzb_bwt_scatter(bw.get() + c * slot, tt.get(), b.nblock, b.orig_ptr, counts.data() + c * 256u, cf.data()) ||
+                !bzb_bwt_chase(bw.get() + c * slot, tt.get(), b.nblock, b.orig_ptr)) { b.status = BZB_BAD; continue; }
+            b.out_size = bzb_rle1_size(bw.get() + c * slot, b.nblock);
+            if (b.out_size == BZB_NO_SIZE) { b.out_size = 0; b.status = BZB_BAD; }
         }
         BzbChain ch;
         bzb_chain(cand.data() + first, (uint32_t)g, blk.data(), cur, out_cap, &ch, idx.data(), off.data());
@@ -80,7 +91,7 @@ struct CpuBlocks {
         for (uint32_t k = 0; k < ch.n; ++k) {
             const BzbBlock& b = blk[idx[k]];
             uint64_t written = 0;
-            const uint32_t crc = bzb_rle1_write(bw.data() + (size_t)idx[k] * slot, b.nblock, text.data() + off[k], off[k + 1] - off[k], crc_tab, &written);
+            const uint32_t crc = bzb_rle1_write(bw.get() + (size_t)idx[k] * slot, b.nblock, text.data() + off[k], off[k + 1] - off[k], crc_tab, &written);
             R.crc_hdr[k] = b.crc; R.end_bit[k] = b.end_bit;
             R.crc_txt[k] = written == off[k + 1] - off[k] ? crc : ~b.crc;
         }
@@ -128,7 +139,9 @@ int main(int argc, char** argv) {
         const int rc = decode_file(bz, (size_t)window, (size_t)group, out_cap, text, st);
         bool good;
         if (!strcmp(want, "error")) good = rc < 0;
-        else good = rc == 0 && text == plain && st.host_blocks == 0 && st.dev_bytes == text.size();
+        else if (!strcmp(want, "handback")) good = rc == 0 && text == plain && st.host_blocks >= 1;
+        else if (!strcmp(want, "exact")) good = rc == 0 && text == plain && st.host_blocks == 0 && st.dev_bytes == text.size();
+        else good = false;
         printf("%s %s: window %llu group %llu — rc %d, %zu bytes of text (expected %zu), %llu blocks decoded by the emulated device, %llu handed back\n", good ? "ok  " : "FAIL", a,
                window, group, rc, text.size(), plain.size(), (unsigned long long)st.dev_blocks, (unsigned long long)st.host_blocks);
         failures += good ? 0 : 1;

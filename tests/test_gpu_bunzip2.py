@@ -1,10 +1,12 @@
 """-m gpu: .bz2 input decoded on the device, one bzip2 block at a time (csrc/aqc_bunzip2_dev.hpp through aqc_bunzip2_dev and
 through the pipe's Bz2Source) — byte for byte what Python's bz2 module (fastq.py:25-26 upstream: bz2.BZ2File) makes of the same
-file, with no block handed back to libbz2 for a valid input; damaged input is an error, never text and never a hang."""
+file, with no block handed back to libbz2 for a valid input; damaged input is an error, never text and never a hang.  The
+inputs are those libbz2's encoder writes (valid_cases, damaged_cases) and those it never does (crafted_cases)."""
 import bz2
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -53,7 +55,7 @@ sys.path.insert(0, sys.argv[1])
 from afterqc_amd import capi
 data = open(sys.argv[2], "rb").read()
 try:
-    text, stats = capi.bunzip2_dev(data, int(sys.argv[3]))
+    text, stats = capi.bunzip2_dev(data, int(sys.argv[3]), group_blocks=int(sys.argv[4]) if len(sys.argv) > 4 else 0)
 except capi.AqcError as e:
     print("ERROR %d" % e.code)
 else:
@@ -74,6 +76,52 @@ def test_damaged_input_is_an_error_in_bounded_time(tmp_path, name):
     out = subprocess.run([sys.executable, "-c", _CHILD, ROOT, p, str(1 << 20)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert out.stdout.strip().startswith("ERROR -"), out.stdout[-2000:] + out.stderr[-2000:]
+
+
+def _crafted_runs():
+    """(name, group_blocks): every crafted case in one group, those of several blocks also in groups of one block; the stream of
+    65,537 blocks in groups of 256 (130 MB of group buffers at level 1, where the default group would take 1.7 GB)"""
+    runs = []
+    for name, image, cls in bz2_cases.crafted_cases():
+        if name == "blocks_65537_one_byte_each":
+            runs.append((name, 256))
+            continue
+        runs.append((name, 0))
+        if len(bz2_cases.magic_hits(image, bz2_cases.BLOCK_MAGIC)) > 1 and name != "stream_then_70000_block_magics":
+            runs.append((name, 1))
+    return runs
+
+
+@pytest.mark.parametrize("name,group_blocks", _crafted_runs())
+def test_crafted_streams_as_libbz2_reads_them(tmp_path, name, group_blocks):
+    """legal corners of the format that libbz2's encoder never writes, and a few illegal ones (tests/bz2_cases.py: crafted_cases,
+    written with tests/bz2_writer.py; every one of them has passed the CPU emulation, plain and under ASan / UBSan, in
+    test_bz2_dev_cpu.py).  Python's bz2 rules: where it raises, so does the device (in a child process, within the time limit);
+    where it returns text, the device returns that text — with every block decoded on the device and none on the host (exact),
+    or with libbz2 finishing the stream (handback)"""
+    _, image, cls, dev_blocks = bz2_cases.crafted_case(name)
+    try:
+        text = bz2.decompress(image)
+    except (OSError, ValueError, EOFError):
+        text = None
+    assert (text is None) == (cls == "error"), (name, cls)
+    if text is None:
+        p = str(tmp_path / "crafted.bz2")
+        with open(p, "wb") as f:
+            f.write(image)
+        out = subprocess.run([sys.executable, "-c", _CHILD, ROOT, p, str(1 << 20), str(group_blocks)], capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        assert out.stdout.strip().startswith("ERROR -"), out.stdout[-2000:] + out.stderr[-2000:]
+        return
+    t0 = time.perf_counter()
+    got, stats = capi.bunzip2_dev(image, len(text) + 4096, group_blocks=group_blocks)
+    print("%s, groups of %d: %.2f s, stats %s" % (name, group_blocks, time.perf_counter() - t0, [int(x) for x in stats[:3]]))
+    assert len(got) == len(text) and got == text, (name, len(got), len(text))
+    assert stats[0] == dev_blocks, (name, stats)
+    if cls == "exact":
+        assert stats[1] == 0 and stats[2] == 0, (name, stats)
+    else:
+        assert cls == "handback" and stats[1] >= 1, (name, stats)
 
 
 _PIPE_CHILD = r"""
