@@ -54,6 +54,11 @@ OPTIONS = [
     ("", "--overlap_output_folder", dict(default=None, help="the folder to store only overlapped bases of the good reads")),
     ("", "--store_merged", dict(default="off", help="specify whether to write every good pair whose overlap came out clean (the pairs --store_overlap selects) once, as a merged read: read 1 followed by the reverse complement of the part of read 2 that lies outside the overlap; paired input only, not together with --store_overlap on")),
     ("", "--merged_output_folder", dict(default=None, help="the folder to store the merged reads, by default it is named 'merged', in the same folder as good_output_folder")),
+    ("", "--cut_front", dict(default="off", help="specify whether to cut each read's head where its own quality is low: a window of cut_window_size bases slides from the front, the bases before the first window whose mean quality reaches cut_mean_quality are dropped (a read without such a window is dropped whole). Runs inside the trim stage, after -f / -t. Default is off")),
+    ("", "--cut_tail", dict(default="off", help="specify whether to cut each read's tail where its own quality is low: the bases behind the last window whose mean quality reaches cut_mean_quality are dropped. Default is off")),
+    ("", "--cut_right", dict(default="off", help="specify whether to cut each read at the first window (from the front, or from where cut_front starts the read) whose mean quality is below cut_mean_quality, dropping that window and everything behind it. Default is off")),
+    ("", "--cut_window_size", dict(default=4, type="int", help="the window size of cut_front / cut_tail / cut_right, 1 to 1000. Default is 4")),
+    ("", "--cut_mean_quality", dict(default=20, type="int", help="the mean phred quality a window needs to be good, 0 to 93. Default is 20")),
     ("", "--qc_only", dict(action="store_true", default=False, help="if qconly is true, only QC result will be output, this can be much fast")),
     ("", "--qc_sample", dict(default=200000, type="int", help="sample up to qc_sample reads when do QC, 0 means sample all reads. Default is 200,000")),
     ("", "--qc_kmer", dict(default=8, type="int", help="specify the kmer length for KMER statistics for QC, default is 8")),
@@ -63,6 +68,10 @@ OPTIONS = [
     ("-z", "--gzip", dict(action="store_true", default=False, help="force gzip compression for output, even the input is not gzip compressed")),
     ("", "--compression", dict(type="int", default=2, help="set compression level (0~9) for gzip output, default is 2 (0 = best speed, 9 = best compression).  Here: 1-5 use the GPU's fast encoder (ratio about zlib level 2-3), 6-9 its hash-chain match search (8 / 16 / 32 / 64 candidates per position: smaller files than zlib level 3-4, slower); 0 writes stored members; AQC_GZ_DEVICE=0 builds the files on the host at a speed / ratio that follows the level")),
 ]
+
+
+CUT_MAX_WINDOW = 1000       # AQC_MAX_READ_LEN
+CUT_MAX_QUALITY = 93
 
 
 def parseBool(s):
@@ -89,6 +98,12 @@ def finalize_options(options):
         # (both are the device writer's third stream: one of them per run)
         raise SystemExit("afterqc_amd: --store_merged on and --store_overlap on exclude each other (the writer has one third "
                          "output stream per file); run them separately")
+    for k in ("cut_front", "cut_tail", "cut_right"):
+        setattr(options, k, parseBool(getattr(options, k)))
+    if not 1 <= options.cut_window_size <= CUT_MAX_WINDOW:
+        raise SystemExit("afterqc_amd: --cut_window_size %d is outside 1 .. %d" % (options.cut_window_size, CUT_MAX_WINDOW))
+    if not 0 <= options.cut_mean_quality <= CUT_MAX_QUALITY:
+        raise SystemExit("afterqc_amd: --cut_mean_quality %d is outside 0 .. %d" % (options.cut_mean_quality, CUT_MAX_QUALITY))
     options.trim_front2 = options.trim_front
     options.trim_tail2 = options.trim_tail
     return options

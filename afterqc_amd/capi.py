@@ -93,6 +93,15 @@ class Config(C.Structure):
             self.barcode_verify[i] = ch
 
 
+class CutConfig(C.Structure):
+    """struct aqc_cut_config: per-read sliding-window quality cutting (--cut_front / --cut_tail / --cut_right)"""
+    _fields_ = [("front", C.c_int32), ("tail", C.c_int32), ("right", C.c_int32), ("window", C.c_int32), ("mean_quality", C.c_int32)]
+
+    @property
+    def on(self):
+        return bool(self.front or self.tail or self.right)
+
+
 class BatchStruct(C.Structure):
     """struct aqc_batch"""
     _fields_ = [("n", C.c_uint64), ("first_index", C.c_uint64),
@@ -352,6 +361,10 @@ def load_library():
     lib.aqc_set_config.argtypes = [P, C.POINTER(Config)]
     lib.aqc_set_circles.argtypes = [P, P, P, P, P, P, C.c_int32]
     lib.aqc_reset_stats.argtypes = [P]
+    lib.aqc_set_quality_cut.argtypes = [P, C.POINTER(CutConfig)]
+    lib.aqc_get_cut_stats.argtypes = [P, P]
+    lib.aqc_cut_ms.argtypes = [P, C.c_int, C.POINTER(C.c_float)]
+    lib.aqc_quality_cut_views.argtypes = [P, C.POINTER(BatchStruct), C.POINTER(CutConfig), C.c_int32, C.c_int32, P]
     lib.aqc_upload.argtypes = [P, C.c_int, C.POINTER(BatchStruct)]
     lib.aqc_run.argtypes = [P, C.c_int, C.c_uint64]
     lib.aqc_qc_stat.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int]
@@ -443,7 +456,7 @@ def load_library():
                  "aqc_timing_mean", "aqc_get_counters", "aqc_get_histograms", "aqc_get_qc", "aqc_get_kmers",
                  "aqc_overlap", "aqc_read_stats", "aqc_edit_distance", "aqc_frame", "aqc_frame_mixed", "aqc_reframe", "aqc_format", "aqc_format_plain",
                  "aqc_fetch_text", "aqc_fetch_quality_views", "aqc_error_record", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused",
-                 "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms"):
+                 "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms", "aqc_set_quality_cut", "aqc_get_cut_stats", "aqc_cut_ms", "aqc_quality_cut_views"):
         getattr(lib, name).restype = C.c_int
     if lib.aqc_abi_version() != 3:
         raise RuntimeError("libafterqc_hip.so ABI version mismatch")
@@ -462,6 +475,7 @@ EXPORTED_SYMBOLS = ["aqc_abi_version", "aqc_device_count", "aqc_device_index", "
                     "aqc_host_count_newlines", "aqc_bgzf_compress", "aqc_pipe_split",
                     "aqc_source_open", "aqc_source_open2", "aqc_source_read", "aqc_source_error", "aqc_source_gz_stats", "aqc_gz_input_stats", "aqc_bz2_input_stats", "aqc_source_close",
                     "aqc_gz_deflate_block", "aqc_gz_inflate_raw", "aqc_gz_crc32",
+                    "aqc_set_quality_cut", "aqc_get_cut_stats", "aqc_cut_ms", "aqc_quality_cut_views",
                     # the reference's own native seam (editdistance/_editdistance.h:16,23), same names and signatures
                     "edit_distance", "seek_overlap"]
 
@@ -517,6 +531,22 @@ class Engine:
 
     def reset_stats(self):
         self._check(self.lib.aqc_reset_stats(self.h))
+
+    def set_quality_cut(self, cut):
+        """cut: a CutConfig, or None (off).  With no mode set nothing of the cut runs."""
+        self._check(self.lib.aqc_set_quality_cut(self.h, C.byref(cut) if cut is not None else None))
+
+    def cut_stats(self):
+        """reads of R1 the cut made shorter, bases it removed from them, the same for R2"""
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.aqc_get_cut_stats(self.h, _ptr(out)))
+        return out
+
+    def cut_ms(self, slot):
+        """device time of the cut pass of the slot's last run(); 0.0: it launched none"""
+        ms = C.c_float(0)
+        self._check(self.lib.aqc_cut_ms(self.h, slot, C.byref(ms)))
+        return float(ms.value)
 
     def upload(self, slot, batch):
         s = batch.as_struct()
@@ -713,6 +743,13 @@ class Engine:
         s = batch.as_struct()
         self._check(self.lib.aqc_read_stats(self.h, C.byref(s), max_poly, mismatch, qual, _ptr(px), _ptr(lq), _ptr(nn)))
         return px, lq, nn
+
+    def quality_cut_views(self, batch, cut, trim_front=0, trim_tail=0):
+        """cut_window() of trim(qual1) for every read of the batch -> (c0, c1) arrays"""
+        v = np.zeros(batch.n, dtype=np.uint32)
+        s = batch.as_struct()
+        self._check(self.lib.aqc_quality_cut_views(self.h, C.byref(s), C.byref(cut), int(trim_front), int(trim_tail), _ptr(v)))
+        return (v & 0xffff).astype(np.int64), (v >> 16).astype(np.int64)
 
     def edit_distance(self, batch):
         d = np.zeros(batch.n, dtype=np.int32)
@@ -981,6 +1018,9 @@ class MergedEngines:
 
     def counters(self):
         return sum(e.counters() for e in self.engines)
+
+    def cut_stats(self):
+        return sum(e.cut_stats() for e in self.engines)
 
     def histograms(self, n=AQC_QC_COLS):
         hs = [e.histograms(n) for e in self.engines]

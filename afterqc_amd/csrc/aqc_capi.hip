@@ -220,12 +220,14 @@ void aqc_destroy(aqc_ctx* c) {
             }
         if (s.status) (void)hipFree(s.status);
         for (hipEvent_t e : s.census_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : s.cut_ev) if (e) (void)hipEventDestroy(e);
         if (s.ev_main) (void)hipEventDestroy(s.ev_main);
         if (s.ev_qc) (void)hipEventDestroy(s.ev_qc);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
     if (c->qc_stream) (void)hipStreamDestroy(c->qc_stream);
     (void)hipFree(c->counters); (void)hipFree(c->ovl_hist); (void)hipFree(c->dist_hist);
+    if (c->cut_stats) (void)hipFree(c->cut_stats);
     for (int k = 0; k < 4; k++) {
         (void)hipFree(c->qc[k].acc);
         free_kmer(c->qc[k].kt);
@@ -306,6 +308,33 @@ int aqc_set_config(aqc_ctx* c, const aqc_config* cfg) {
     return 0;
 }
 
+// the quality cut (aqc_qcut.hpp): NULL or no mode set switches it off
+int aqc_set_quality_cut(aqc_ctx* c, const aqc_cut_config* cut) {
+    if (!c) return fail(AQC_ERR_ARG, "aqc_set_quality_cut: null context");
+    QcutOpts o{};
+    if (cut) o = QcutOpts{cut->front ? 1 : 0, cut->tail ? 1 : 0, cut->right ? 1 : 0, cut->window, cut->mean_quality};
+    if (!qcut_on(o)) { c->cut = QcutOpts{}; return 0; }
+    if (!qcut_opts_ok(o))
+        return fail(AQC_ERR_ARG, "aqc_set_quality_cut: window %d (1 .. %d) / mean quality %d (0 .. %d)", o.window, AQC_MAX_READ_LEN, o.mean_quality, QCUT_MAX_QUALITY);
+    if (!c->cut_stats) {
+        // (the counts exist from the first time a cut is set: a context that never has one allocates what it always did)
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipMalloc((void**)&c->cut_stats, sizeof(unsigned long long) * 4));
+        HIP_TRY(hipMemset(c->cut_stats, 0, sizeof(unsigned long long) * 4));
+    }
+    c->cut = o;
+    return 0;
+}
+
+int aqc_get_cut_stats(aqc_ctx* c, int64_t out[4]) {
+    if (!c || !out) return fail(AQC_ERR_ARG, "null argument");
+    int rc = sync_all(c);
+    if (rc) return rc;
+    for (int k = 0; k < 4; ++k) out[k] = 0;
+    if (c->cut_stats) HIP_TRY(hipMemcpy(out, c->cut_stats, sizeof(int64_t) * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int aqc_set_circles(aqc_ctx* c, const double* cx, const double* cy, const double* r, const int32_t* lane,
                     const int32_t* tile, int32_t n) {
     if (!c || n < 0) return fail(AQC_ERR_ARG, "aqc_set_circles: bad arguments");
@@ -335,6 +364,7 @@ int aqc_reset_stats(aqc_ctx* c) {
     HIP_TRY(hipMemset(c->counters, 0, sizeof(unsigned long long) * (AQC_N_COUNTERS + 16)));
     HIP_TRY(hipMemset(c->ovl_hist, 0, sizeof(unsigned long long) * AQC_QC_COLS));
     HIP_TRY(hipMemset(c->dist_hist, 0, sizeof(unsigned long long) * AQC_QC_COLS));
+    if (c->cut_stats) HIP_TRY(hipMemset(c->cut_stats, 0, sizeof(unsigned long long) * 4));
     for (auto& sl : c->slots) { HIP_TRY(hipMemcpy(sl.status, &STATUS_CLEAR, sizeof(STATUS_CLEAR), hipMemcpyHostToDevice)); sl.err_record = UINT64_MAX; }
     for (int k = 0; k < 4; k++) {
         HIP_TRY(hipMemset(c->qc[k].acc, 0, sizeof(unsigned long long) * AQC_QC_ROWS * AQC_QC_COLS));

@@ -11,8 +11,9 @@
 // aqc_gzdev.hpp + aqc_gzlz.hpp; the member, bit-ring and symbol functions the three encoders share are in aqc_gzdev.hpp and
 // aqc_deflate_sym.hpp):
 //   aqc_upload.hpp   narrow_offsets_kernel, mark_irregular_kernel, quality_views_kernel
-//   aqc_record.hpp   filter_overlap_kernel, filter_overlap_list_kernel
-//   aqc_fast.hpp     fast_filter_overlap_kernel<NW, PAIRED, WPBT, BARCODE, FUSE> (a template: the variants are instantiated here)
+//   aqc_record.hpp   filter_overlap_kernel, filter_overlap_list_kernel, filter_overlap_cut_kernel<LIST>
+//   aqc_fast.hpp     fast_filter_overlap_kernel<NW, PAIRED, WPBT, BARCODE, FUSE, CUT> (a template: the variants are instantiated here)
+//   aqc_qcut.hpp     quality_cut_kernel<G> (the quality cut's pass in front of the verdict kernel, and its function seam)
 //   aqc_gzdev.hpp    gz_hist_kernel, gz_encode_wave_kernel, gz_encode_kernel, gz_offsets_kernel, gz_pack_kernel
 //   aqc_gzlz.hpp     gz_hist_lz_kernel, gz_encode_lz_kernel (levels 6 - 9)
 //   aqc_seams.hpp    overlap_seam_kernel, read_stats_seam_kernel, edit_distance_seam_kernel, edit_distance_any_kernel,
@@ -46,7 +47,7 @@ constexpr int FUSE_WPBT = 12;      // waves per workgroup of the fused verdict k
 #endif
 constexpr int TIER20_WPBT_PAIRED = AQC_TIER20_WPBT;
 static_assert(TIER20_WPBT_PAIRED == 10 || TIER20_WPBT_PAIRED == 11, "the 20-word rows of 10 or 11 waves fit a CU's LDS");
-template <int NW, bool PAIRED, int WPBT, bool BARCODE, bool FUSE = false>
+template <int NW, bool PAIRED, int WPBT, bool BARCODE, bool FUSE = false, bool CUT = false>
 static void launch_fast(aqc_ctx* c, Slot* s, const aqc_config& cfg, const DevStats& st, uint64_t accum_limit, const FuseArgs* fz = nullptr) {
     constexpr uint64_t per_block = (uint64_t)WPBT * FastWaveLds<NW, PAIRED, FUSE>::PPW;
     uint64_t blocks = (s->n + per_block - 1) / per_block;
@@ -64,12 +65,24 @@ static void launch_fast(aqc_ctx* c, Slot* s, const aqc_config& cfg, const DevSta
     K.fb = s->view; K.cfg = cfg; K.circ = c->circles; K.results = (aqc_result*)s->results.p; K.st = st; K.accum_limit = accum_limit;
     K.deferred = (uint32_t*)s->deferred.p; K.n_deferred = (unsigned int*)s->n_deferred.p;
     K.fz = fz ? *fz : FuseArgs{};
-    hipLaunchKernelGGL((fast_filter_overlap_kernel<NW, PAIRED, WPBT, BARCODE, FUSE>), dim3((unsigned)blocks), dim3(WPBT * WAVE), 0, s->stream, K);
+    if constexpr (CUT) {
+        // (the cut's instances take the view array — the mates of a record side by side — behind the arguments every instance takes)
+        FastCutArgs KC;
+        static_cast<FastArgs&>(KC) = K;
+        KC.cut = (const uint32_t*)s->cut.p;
+        hipLaunchKernelGGL((fast_filter_overlap_kernel<NW, PAIRED, WPBT, false, false, true>), dim3((unsigned)blocks), dim3(WPBT * WAVE), 0, s->stream, KC);
+    } else
+        hipLaunchKernelGGL((fast_filter_overlap_kernel<NW, PAIRED, WPBT, BARCODE, FUSE>), dim3((unsigned)blocks), dim3(WPBT * WAVE), 0, s->stream, K);
 }
 
 // one tier of the lane-per-pair kernel (NW words per read; waves per workgroup for pairs / single reads): paired x barcode
 template <int NW, int WPBT_PAIRED, int WPBT_SINGLE>
 static void launch_fast_tier(aqc_ctx* c, Slot* s, const aqc_config& cfg, const DevStats& st, uint64_t accum_limit) {
+    if (qcut_on(c->cut)) {      // (never with a barcode: aqc_run refuses that)
+        if (cfg.paired) launch_fast<NW, true, WPBT_PAIRED, false, false, true>(c, s, cfg, st, accum_limit);
+        else launch_fast<NW, false, WPBT_SINGLE, false, false, true>(c, s, cfg, st, accum_limit);
+        return;
+    }
     if (cfg.paired) { if (cfg.barcode) launch_fast<NW, true, WPBT_PAIRED, true>(c, s, cfg, st, accum_limit); else launch_fast<NW, true, WPBT_PAIRED, false>(c, s, cfg, st, accum_limit); }
     else { if (cfg.barcode) launch_fast<NW, false, WPBT_SINGLE, true>(c, s, cfg, st, accum_limit); else launch_fast<NW, false, WPBT_SINGLE, false>(c, s, cfg, st, accum_limit); }
 }
@@ -230,7 +243,8 @@ static Verdict choose_verdict_kernel(const aqc_ctx* c, const Slot& s, const aqc_
     // AQC_FUSED=1: pairs of device-framed text whose records are plain four-line text are placed in their output
     // streams by the verdict kernel itself, which also copies the good records that go out as their own bytes
     // (31-bit stream offsets; a bad record grows by its flag text)
-    if (c->fuse_opt && s.framed && cfg.paired && !cfg.barcode && s.max_len <= 160 && !s.has_irregular && s.m[0].consumed + 16 * s.n < (1ull << 31) &&
+    // (not with the quality cut on: its instances are the plain tiers)
+    if (c->fuse_opt && !qcut_on(c->cut) && s.framed && cfg.paired && !cfg.barcode && s.max_len <= 160 && !s.has_irregular && s.m[0].consumed + 16 * s.n < (1ull << 31) &&
         s.m[1].consumed + 16 * s.n < (1ull << 31))
         return Verdict::FUSED;
     // (TIER18, 257 .. 288 bases: 2x250 reads that still carry a barcode + verify prefix (BASELINE config 5: 267 bases))
@@ -255,25 +269,72 @@ static int prepare_fuse(Slot& s, FuseArgs& fz) {
     return 0;
 }
 
+// ---- the quality cut's pass (aqc_qcut.hpp): one view per mate and record into `view` (n_mates per record), the four counts into `stats` (may be NULL)
+static int launch_cut(aqc_ctx* c, Slot& s, const QcutOpts& o, const int32_t trim_front[2], const int32_t trim_tail[2], int n_mates, uint32_t* view,
+                      unsigned long long* stats, uint64_t accum_limit) {
+    QcutArgs A{};
+    A.b = s.view; A.o = o; A.n_mates = n_mates; A.view = view; A.stats = stats; A.accum_limit = accum_limit; A.status = s.status;
+    for (int k = 0; k < 2; ++k) { A.trim_front[k] = trim_front[k]; A.trim_tail[k] = trim_tail[k]; }
+    // lanes per read by the longest quality line: a line of its own length (or a length nobody has looked at) may be anything up to AQC_MAX_READ_LEN
+    const uint32_t longest = (s.has_irregular || s.raw_max_len == 0) ? (uint32_t)AQC_MAX_READ_LEN : s.raw_max_len;
+    const int G = longest <= 128 ? 8 : longest <= 256 ? 16 : longest <= 512 ? 32 : 64;
+    uint64_t blocks = (s.n + (QCUT_THREADS / G) - 1) / (QCUT_THREADS / G);
+    const uint64_t cap = (uint64_t)c->n_cu * 16;
+    if (blocks > cap) blocks = cap;
+    const dim3 grid((unsigned)blocks), block(QCUT_THREADS);
+    if (G == 8) hipLaunchKernelGGL(quality_cut_kernel<8>, grid, block, 0, s.stream, A);
+    else if (G == 16) hipLaunchKernelGGL(quality_cut_kernel<16>, grid, block, 0, s.stream, A);
+    else if (G == 32) hipLaunchKernelGGL(quality_cut_kernel<32>, grid, block, 0, s.stream, A);
+    else hipLaunchKernelGGL(quality_cut_kernel<64>, grid, block, 0, s.stream, A);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the cut pass of an aqc_run: both mates' views into the slot's arrays, timed by an event pair of its own
+static int run_cut(aqc_ctx* c, Slot& s, const aqc_config& cfg, uint64_t accum_limit) {
+    const int nm = cfg.paired ? 2 : 1;
+    if (s.cut.reserve(sizeof(uint32_t) * s.n * nm)) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    for (hipEvent_t& e : s.cut_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    const int32_t tf[2] = {cfg.trim_front, cfg.trim_front2}, tt[2] = {cfg.trim_tail, cfg.trim_tail2};
+    HIP_TRY(hipEventRecord(s.cut_ev[0], s.stream));
+    const int rc = launch_cut(c, s, c->cut, tf, tt, nm, (uint32_t*)s.cut.p, c->cut_stats, accum_limit);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(s.cut_ev[1], s.stream));
+    s.cut_ran = true;
+    return 0;
+}
+
 int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
     GET_SLOT(s);
     if (!c->has_cfg) return fail(AQC_ERR_STATE, "aqc_run before aqc_set_config");
     if (c->cfg.paired && !s->paired) return fail(AQC_ERR_STATE, "config says paired but the slot holds single-end records");
     if (c->cfg.debubble && c->circles.n > 0 && !s->view.aux_ok) return fail(AQC_ERR_ARG, "debubble needs the aux_* arrays");
+    const bool cut = qcut_on(c->cut);
+    if (cut && c->cfg.barcode) return fail(AQC_ERR_UNSUPPORTED, "aqc_run: the quality cut together with a barcode is not implemented");
     s->fused = false;
     s->verdict_words = 0;
+    s->cut_ran = false;
     if (s->n == 0) { s->ran = true; return 0; }
     aqc_config cfg = c->cfg;
     if (!cfg.paired) cfg.no_overlap = 1;
     DevStats st{c->counters, c->ovl_hist, c->dist_hist, s->status, err_key_of(*s)};
     s->err_record = UINT64_MAX;
     if (s->qc.pending()) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_qc, 0));      // (statRead of the previous run still reads the results)
+    if (cut) {
+        const int rc = run_cut(c, *s, cfg, accum_limit);
+        if (rc) return rc;
+    }
     HIP_TRY(hipEventRecord(launch_event(*s, AQC_K_FILTER_OVERLAP, 0), s->stream));
     const Verdict k = choose_verdict_kernel(c, *s, cfg);
     s->used_fast = k != Verdict::GENERAL;
     s->verdict_words = verdict_words(k);
+    // (with the cut on, the general kernel and the deferred list's take the views behind their usual arguments)
+    FilterCutArgs fc{FilterArgs{s->view, cfg, c->circles, (aqc_result*)s->results.p, st, accum_limit}, nullptr, nullptr,
+                     (const uint32_t*)s->cut.p};
     if (k == Verdict::GENERAL) {
-        hipLaunchKernelGGL(filter_overlap_kernel, dim3(grid_for(c, s->n)), dim3(BLOCK), 0, s->stream, s->view, cfg, c->circles,
+        if (cut) hipLaunchKernelGGL(filter_overlap_cut_kernel<false>, dim3(grid_for(c, s->n)), dim3(BLOCK), 0, s->stream, fc);
+        else hipLaunchKernelGGL(filter_overlap_kernel, dim3(grid_for(c, s->n)), dim3(BLOCK), 0, s->stream, s->view, cfg, c->circles,
                            (aqc_result*)s->results.p, st, accum_limit);
     } else {
         if (s->deferred.reserve(sizeof(uint32_t) * (s->n + 1)) || s->n_deferred.reserve(sizeof(unsigned int)))
@@ -288,7 +349,10 @@ int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
         else if (k == Verdict::TIER16) launch_fast_tier<16, 12, 11>(c, s, cfg, st, accum_limit);
         else if (k == Verdict::TIER18) launch_fast_tier<18, 12, 10>(c, s, cfg, st, accum_limit);
         else launch_fast_tier<20, TIER20_WPBT_PAIRED, 9>(c, s, cfg, st, accum_limit);
-        hipLaunchKernelGGL(filter_overlap_list_kernel, dim3((unsigned)c->n_cu), dim3(BLOCK), 0, s->stream, s->view, cfg, c->circles,
+        fc.list = (const uint32_t*)s->deferred.p;
+        fc.n_list = (const unsigned int*)s->n_deferred.p;
+        if (cut) hipLaunchKernelGGL(filter_overlap_cut_kernel<true>, dim3((unsigned)c->n_cu), dim3(BLOCK), 0, s->stream, fc);
+        else hipLaunchKernelGGL(filter_overlap_list_kernel, dim3((unsigned)c->n_cu), dim3(BLOCK), 0, s->stream, s->view, cfg, c->circles,
                            (aqc_result*)s->results.p, st, accum_limit, (const uint32_t*)s->deferred.p,
                            (const unsigned int*)s->n_deferred.p);
     }
@@ -320,6 +384,16 @@ int aqc_fetch_quality_views(aqc_ctx* c, int slot, int mate, uint32_t* out, uint6
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, s->off_stage.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(slot_sync(*s));
+    return 0;
+}
+
+int aqc_cut_ms(aqc_ctx* c, int slot, float* ms) {
+    GET_SLOT(s);
+    if (!ms) return fail(AQC_ERR_ARG, "aqc_cut_ms: null argument");
+    *ms = 0.f;
+    if (!s->cut_ran) return 0;
+    HIP_TRY(slot_sync(*s));
+    HIP_TRY(hipEventElapsedTime(ms, s->cut_ev[0], s->cut_ev[1]));
     return 0;
 }
 
@@ -510,6 +584,24 @@ int aqc_edit_distance(aqc_ctx* c, const aqc_batch* b, int32_t* dist) {
                        (int32_t*)o.p, s->status);
     HIP_TRY(hipGetLastError());
     if ((rc = seam_out(s, o, dist, n))) return rc;
+    HIP_TRY(slot_sync(*s));
+    return check_status(*s);
+}
+
+int aqc_quality_cut_views(aqc_ctx* c, const aqc_batch* b, const aqc_cut_config* cut, int32_t trim_front, int32_t trim_tail, uint32_t* view) {
+    if (!cut || !view) return fail(AQC_ERR_ARG, "aqc_quality_cut_views: null argument");
+    const QcutOpts o{cut->front ? 1 : 0, cut->tail ? 1 : 0, cut->right ? 1 : 0, cut->window, cut->mean_quality};
+    if (!qcut_opts_ok(o) || trim_front < 0 || trim_tail < 0) return fail(AQC_ERR_ARG, "aqc_quality_cut_views: window / mean quality / trim out of range");
+    Slot* s;
+    int rc = seam_prepare(c, b, true, false, &s);
+    if (rc) return rc;
+    const uint64_t n = b->n;
+    if (n == 0) return 0;
+    DevBuf out;
+    if (out.reserve(4 * n)) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    const int32_t tf[2] = {trim_front, 0}, tt[2] = {trim_tail, 0};
+    if ((rc = launch_cut(c, *s, o, tf, tt, 1, (uint32_t*)out.p, nullptr, UINT64_MAX))) return rc;
+    if ((rc = seam_out(s, out, view, n))) return rc;
     HIP_TRY(slot_sync(*s));
     return check_status(*s);
 }

@@ -12,6 +12,7 @@
 
 #include "aqc_dev.hpp"
 #include "aqc_batch.hpp"
+#include "aqc_qcut.hpp"
 
 namespace aqc {
 
@@ -75,6 +76,9 @@ struct __attribute__((visibility("hidden"))) Slot {
     uint64_t n = 0;
     bool paired = false, ran = false, used_fast = false;
     int verdict_words = 0;         // words per read of the lane-per-pair instance the last aqc_run launched, 0: the general kernel
+    DevBuf cut;                                  // the quality cut's views (aqc_qcut.hpp: one per mate and record), filled by aqc_run in front of the verdict kernel
+    hipEvent_t cut_ev[2] = {nullptr, nullptr};   // around the cut pass of the last aqc_run (aqc_cut_ms) ...
+    bool cut_ran = false;                        // ... if it launched one
     // AQC_FUSED=1: the verdict kernel placed the slot's records in their streams and copied the whole good ones (aqc_fast.hpp, FUSE)
     DevBuf fz_state, fz_misc;                 // look-back words per batch (Mate::fz_rec: position words per record); ticket | abort | totals[4]
     bool fused = false;                       // ... for the records the slot holds now (aqc_format checks fz_misc's abort word)
@@ -125,6 +129,8 @@ struct __attribute__((visibility("hidden"))) aqc_ctx {
     std::vector<aqc::Slot> slots;
     aqc_config cfg{};
     bool has_cfg = false;
+    aqc::QcutOpts cut{};               // aqc_set_quality_cut: the quality cut (all modes 0: off, no kernel of it is launched)
+    unsigned long long* cut_stats = nullptr;   // [4] reads of R1 the cut made shorter, bases it took from them, the same for R2
     aqc::DevBuf circ[5];
     aqc::DevBuf kmer_partial;          // per-round u16 count slices of kmer_count_kernel
     aqc::DevBuf gz_crc;                // GzCrcTables (aqc_compress)

@@ -41,6 +41,7 @@
 #include "afterqc_hip.h"
 #include "aqc_prim.hpp"
 #include "aqc_batch.hpp"
+#include "aqc_qcut.hpp"
 
 namespace aqc {
 
@@ -243,9 +244,18 @@ typedef const FastArgs __attribute__((address_space(4))) * FastArgsRare;
 // (one workgroup of WPBT waves per CU — its LDS rows allow no second one — is WPBT / 4 waves per SIMD: that is the occupancy the
 //  register budget is sized for: 128 VGPRs for the 16-wave 2 x 150 variant, 168 for the 12-wave ones)
 constexpr int FAST_MIN_WAVES = 4;
-template <int NW, bool PAIRED, int WPBT, bool BARCODE, bool FUSE = false>
-__global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < FAST_MIN_WAVES ? (WPBT + 3) / 4 : FAST_MIN_WAVES) void fast_filter_overlap_kernel(FastArgs K) {
+// CUT: the quality cut is on (aqc_qcut.hpp): the kernel's arguments continue with the view array of the cut pass (the mates of a record side by side), and the trim
+// stage slices every read by its own view after the fixed trim.  Only those instances take the longer argument struct: the others
+// take what they always took and come out of the compiler with the same instructions (profiles/r16_qcut.txt).
+struct FastCutArgs : FastArgs {
+    const uint32_t* cut;                       // c0 | c1 << 16 of the trimmed reads: [2 r], [2 r + 1] for read 1 / 2 of pair r, [r] single-end
+};
+typedef const FastCutArgs __attribute__((address_space(4))) * FastCutArgsRare;
+
+template <int NW, bool PAIRED, int WPBT, bool BARCODE, bool FUSE = false, bool CUT = false>
+__global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < FAST_MIN_WAVES ? (WPBT + 3) / 4 : FAST_MIN_WAVES) void fast_filter_overlap_kernel(std::conditional_t<CUT, FastCutArgs, FastArgs> K) {
     static_assert(!FUSE || (PAIRED && !BARCODE), "the fused variant is the plain paired one");
+    static_assert(!CUT || (!FUSE && !BARCODE), "the cut goes with the plain instances");
     const DevBatch& fb = K.fb;
     const aqc_config& cfg = K.cfg;
     aqc_result* __restrict__ const results = K.results;
@@ -287,7 +297,7 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < FAST_MIN_WAVES ? (WPB
     const uint32_t* const qo1 = fb.qoff1 ? fb.qoff1 : fb.off1;
     const uint32_t* const qo2 = PAIRED ? (fb.qoff2 ? fb.qoff2 : fb.off2) : nullptr;
     const int thr4 = __builtin_amdgcn_readfirstlane((cfg.qualified_quality_phred + 33) * 0x01010101);
-    const int do_trim = __builtin_amdgcn_readfirstlane((cfg.trim_front > 0 || cfg.trim_tail > 0) ? 1 : 0);
+    const int do_trim = __builtin_amdgcn_readfirstlane((CUT || cfg.trim_front > 0 || cfg.trim_tail > 0) ? 1 : 0);
     // read 1's low-quality count: with a view that is only known per read (trim, barcode) phase 1 leaves one bit per base
     // and the owner counts inside its view; otherwise the chunks are simply summed
     // longest run of identical bases any firing polyX window must contain (pigeonhole over the mismatches)
@@ -521,7 +531,7 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < FAST_MIN_WAVES ? (WPB
         // spills them to VGPR lanes — v_writelane / v_readlane + hazard nops were ~6 % of the vector instructions issued.
         FastArgsRare Rb = R;
         asm volatile("" : "+s"(Rb));
-        const int o_do_trim = do_trim, o_run_req = run_req, o_r2b = r2b, o_thr4 = thr4, o_poly_word = poly_word;
+        const int o_do_trim = CUT ? 1 : do_trim, o_run_req = run_req, o_r2b = r2b, o_thr4 = thr4, o_poly_word = poly_word;
         __builtin_amdgcn_s_setprio(0);
         const uint32_t base = cur * PPW;
         // exactly ONE batch of lookahead (its descriptors travel while this batch is processed): a slow wave never sits
@@ -824,6 +834,13 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < FAST_MIN_WAVES ? (WPB
             int st_ = 0, nl_ = 0;
             trim_view(len_own, role ? R->cfg.trim_front2 : R->cfg.trim_front, role ? R->cfg.trim_tail2 : R->cfg.trim_tail, st_, nl_);
             a_own += st_; len_own = nl_;
+            if (CUT) {
+                // the cut pass's view of this read, relative to the trimmed read: [c0:c1] the python way
+                const FastCutArgsRare Rc = (FastCutArgsRare)R;
+                const uint32_t cv = valid ? Rc->cut[PAIRED ? 2u * rec + (uint32_t)role : rec] : 0u;
+                qcut_slice(len_own, (int)(cv & 0xffffu), (int)(cv >> 16), st_, nl_);
+                a_own += st_; len_own = nl_;
+            }
         }
         int a_par = 0, len_par = 0;
         if (PAIRED) { a_par = xchg(a_own); len_par = xchg(len_own); }

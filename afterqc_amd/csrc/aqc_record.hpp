@@ -11,6 +11,7 @@
 #include "afterqc_hip.h"
 #include "aqc_prim.hpp"
 #include "aqc_batch.hpp"
+#include "aqc_qcut.hpp"
 
 namespace aqc {
 
@@ -241,10 +242,11 @@ struct WaveLds {
     uint8_t *rs1, *rs2;                // 2 x 64 bytes (barcode readStart strings)
 };
 
-template <class Cfg>      // aqc_config, or aqc_config in the kernarg segment (address space 4: its fields are scalar loads where they are used)
+// CUT: the trim stage also applies the per-read views of the quality cut (aqc_qcut.hpp: c0 | c1 << 16, the mates of a record side by side)
+template <bool CUT = false, class Cfg>      // aqc_config, or aqc_config in the kernarg segment (address space 4: its fields are scalar loads where they are used)
 __device__ __forceinline__ void process_record_wave(const DevBatch& b, uint64_t rec, const Cfg& cfg, const DevCircles& circ,
                                            const WaveLds& w, aqc_result* __restrict__ results, BlockAcc& acc,
-                                           const DevStats& st, bool accum) {
+                                           const DevStats& st, bool accum, const uint32_t* cut = nullptr) {
     const int lane = lane_id();
     uint8_t* s1 = w.s1;
     uint8_t* q1 = w.q1;
@@ -333,7 +335,21 @@ __device__ __forceinline__ void process_record_wave(const DevBatch& b, uint64_t 
             }
         }
         // ---- trim (preprocesser.py:455-466, python slice semantics of trim() :19-28)
-        if (flag < 0 && (cfg.trim_front > 0 || cfg.trim_tail > 0)) {
+        if (CUT) {
+            // ... and the quality cut: every string is sliced by its own length, trim() first, then [c0:c1] of the cut pass
+            if (flag < 0) {
+                const uint32_t v1 = cut[paired ? 2 * rec : rec];
+                qcut_apply(a1, len1, cfg.trim_front, cfg.trim_tail, v1);
+                qcut_apply(qa1, ql1, cfg.trim_front, cfg.trim_tail, v1);
+                if (len1 < 5) flag = AQC_BADTRIM1;
+                else if (paired) {
+                    const uint32_t v2 = cut[2 * rec + 1];
+                    qcut_apply(a2, len2, cfg.trim_front2, cfg.trim_tail2, v2);
+                    qcut_apply(qa2, ql2, cfg.trim_front2, cfg.trim_tail2, v2);
+                    if (len2 < 5) flag = AQC_BADTRIM2;
+                }
+            }
+        } else if (flag < 0 && (cfg.trim_front > 0 || cfg.trim_tail > 0)) {
             int end = cfg.trim_tail > 0 ? max(len1 - cfg.trim_tail, 0) : len1;
             int stt = min(cfg.trim_front, len1);
             int nl = max(end - stt, 0);
@@ -661,6 +677,46 @@ __global__ __launch_bounds__(BLOCK) void filter_overlap_list_kernel(DevBatch b, 
     }
     __syncthreads();
     flush_block_acc(acc, st);
+}
+
+// The two kernels above with the quality cut on (aqc_qcut.hpp): the same pipeline, the trim stage takes each mate's view from the
+// slot's arrays.  LIST: over the records the lane-per-read kernel deferred.  Kernels of their own, so that the ones above take the
+// arguments — and come out of the compiler — as they always did.
+struct FilterCutArgs {
+    FilterArgs a;
+    const uint32_t* list;
+    const unsigned int* n_list;
+    const uint32_t* cut;
+};
+
+template <bool LIST>
+__global__ __launch_bounds__(BLOCK) void filter_overlap_cut_kernel(FilterCutArgs A) {
+    __shared__ uint8_t lds[WPB][5][LSTR];
+    __shared__ uint8_t rsbuf[WPB][2][64];
+    __shared__ BlockAcc acc;
+    const uint64_t n = LIST ? (uint64_t)*A.n_list : A.a.b.n;
+    if (n == 0) return;
+    const int wave = threadIdx.x / WAVE;
+    for (int i = threadIdx.x; i < (int)(sizeof(BlockAcc) / 4); i += BLOCK) ((unsigned int*)&acc)[i] = 0;
+    __syncthreads();
+    const WaveLds w{lds[wave][0], lds[wave][1], lds[wave][2], lds[wave][3], lds[wave][4], rsbuf[wave][0], rsbuf[wave][1]};
+    const uint64_t nwaves = (uint64_t)gridDim.x * WPB;
+    for (uint64_t i = (uint64_t)blockIdx.x * WPB + wave; i < n; i += nwaves) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const FilterCutArgs __attribute__((address_space(4)))* ka = (const FilterCutArgs __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        const uint64_t rec = LIST ? (uint64_t)ka->list[i] : i;
+        const DevBatch bb = ka->a.b;
+        const DevCircles ci = ka->a.circ;
+        const DevStats ss = ka->a.st;
+        process_record_wave<true>(bb, rec, ka->a.cfg, ci, w, ka->a.results, acc, ss, rec < ka->a.accum_limit, ka->cut);
+#else
+        const uint64_t rec = LIST ? (uint64_t)A.list[i] : i;
+        process_record_wave<true>(A.a.b, rec, A.a.cfg, A.a.circ, w, A.a.results, acc, A.a.st, rec < A.a.accum_limit, A.cut);
+#endif
+    }
+    __syncthreads();
+    flush_block_acc(acc, A.a.st);
 }
 
 }  // namespace aqc

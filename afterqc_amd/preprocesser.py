@@ -99,6 +99,23 @@ def load_circles(debubble_dir):
     return circles
 
 
+def cut_config(opt):
+    """--cut_front / --cut_tail / --cut_right as the engine takes them; None: every mode is off (options objects built without
+    the cut options count as off)"""
+    modes = [bool(getattr(opt, k, False)) for k in ("cut_front", "cut_tail", "cut_right")]
+    if not any(modes):
+        return None
+    return capi.CutConfig(int(modes[0]), int(modes[1]), int(modes[2]), int(getattr(opt, "cut_window_size", 4)), int(getattr(opt, "cut_mean_quality", 20)))
+
+
+def set_cut(engine, cut):
+    """the cut on an engine — only ever called with a mode on: an engine that cannot cut is an error, never a run without the cut"""
+    if not hasattr(engine, "set_quality_cut"):
+        raise RuntimeError("afterqc_amd: --cut_front / --cut_tail / --cut_right need an engine with set_quality_cut; %s has none"
+                           % type(engine).__name__)
+    engine.set_quality_cut(cut)
+
+
 def build_config(opt, paired, has_index2):
     cfg = capi.Config()
     cfg.paired = 1 if paired else 0
@@ -402,6 +419,7 @@ class seqFilter:
         self.paired = opt.read2_file is not None
         self.bubbleCircles = []
         self.stat = None
+        self.cut = cut_config(opt)
 
     # ---- helpers ---------------------------------------------------------------------------------
     def _engine(self):
@@ -421,6 +439,8 @@ class seqFilter:
                 e = capi.Engine(d, max(2, self.pipe_slots))
                 e.set_config(cfg)
                 e.set_circles(circles)
+                if self.cut is not None:
+                    set_cut(e, self.cut)
                 e.reset_stats()
                 self.extra_engines.append(e)
         return [eng] + self.extra_engines
@@ -437,6 +457,10 @@ class seqFilter:
     # ---- the run -----------------------------------------------------------------------------------
     def run(self):
         opt = self.options
+        if opt.barcode and self.cut is not None:
+            # (the barcode stage moves the view before the trim stage: that combination is not implemented; refused before anything is created)
+            raise SystemExit("afterqc_amd: --cut_front / --cut_tail / --cut_right are not implemented for barcoded input "
+                             "(%s); run it with --barcode off or without the cut" % opt.read1_file)
         t_init = time.perf_counter()
         eng = self._engine()
         self.timing = {"init_s": time.perf_counter() - t_init}       # (a fresh process: HIP runtime start + the library's code object)
@@ -479,6 +503,10 @@ class seqFilter:
         self._last_cfg = (build_config(opt, self.paired, opt.index2_file is not None), self.bubbleCircles)
         for e in self._engines():
             e.set_config(self._last_cfg[0])
+            if self.cut is not None:
+                set_cut(e, self.cut)
+            elif hasattr(e, "set_quality_cut"):
+                e.set_quality_cut(None)          # (an engine the caller handed over may come from a run that had the cut on)
             if first:
                 e.set_circles(self.bubbleCircles)
                 e.reset_stats()
@@ -982,4 +1010,11 @@ class seqFilter:
                 mtx[a] = {b: c(capi.C_ERR_MATRIX0 + 4 * i + j) for j, b in enumerate(ALL_BASES) if b != a}
             ov['error_matrix'] = mtx
             stat["afterqc_overlap"] = ov
+        if self.cut is not None:
+            n = [int(v) for v in eng.cut_stats()]
+            stat["quality_cut"] = {
+                'cut_front': bool(self.cut.front), 'cut_tail': bool(self.cut.tail), 'cut_right': bool(self.cut.right),
+                'cut_window_size': int(self.cut.window), 'cut_mean_quality': int(self.cut.mean_quality),
+                'read1_cut_reads': n[0], 'read1_cut_bases': n[1], 'read2_cut_reads': n[2], 'read2_cut_bases': n[3],
+            }
         return stat

@@ -228,6 +228,23 @@ int aqc_set_circles(aqc_ctx* ctx, const double* cx, const double* cy, const doub
 /* zero the counters, histograms, QC accumulators and k-mer tables of the context */
 int aqc_reset_stats(aqc_ctx* ctx);
 
+/* ---- per-read sliding-window quality cutting (--cut_front / --cut_tail / --cut_right) ---------- */
+/* Inside the trim stage of preprocesser.py:455-466, behind upstream's fixed trim: each mate keeps [c0, c1) of its trimmed lines,
+ * decided on its own quality line.  A window of w = min(window, n) bases is good when the sum of its (byte - 33) is at least
+ * mean_quality * w.  front: c0 = the first good window's start; tail: c1 = the last good window's end; right: c1 = the first bad
+ * window's start at or behind c0; front or tail without any good window: nothing is kept.  The stage then runs whatever the fixed
+ * trim amounts are, its `< 5` tests as they stand (AQC_BADTRIM1 leaves read 2 untrimmed and uncut).  Both mates take the same
+ * rule.  window 1 .. AQC_MAX_READ_LEN, mean_quality 0 .. 93. */
+typedef struct aqc_cut_config { int32_t front, tail, right, window, mean_quality; } aqc_cut_config;
+/* NULL or no mode set: off — no kernel of the cut is launched and aqc_run is what it is without it.  A bad window / quality:
+ * AQC_ERR_ARG.  With a cut on, aqc_run of a configuration that has `barcode` set returns AQC_ERR_UNSUPPORTED. */
+int aqc_set_quality_cut(aqc_ctx* ctx, const aqc_cut_config* cut);
+/* out[0..3]: reads of R1 the cut made shorter, bases it removed from them, the same for R2.  Records below accum_limit only; R2 is
+ * not counted where it was left untrimmed (AQC_BADTRIM1).  Zeroed by aqc_reset_stats; contexts add up. */
+int aqc_get_cut_stats(aqc_ctx* ctx, int64_t out[4]);
+/* device time of the cut pass of the slot's last aqc_run (HIP events on the slot's stream); 0: it launched none */
+int aqc_cut_ms(aqc_ctx* ctx, int slot, float* ms);
+
 /* ---- the hot path: preprocesser.py:411-631 over a batch --------------------------------------- */
 /* copy a batch into slot `slot` (async on the slot's stream; see the note on host buffers above) */
 int aqc_upload(aqc_ctx* ctx, int slot, const aqc_batch* batch);
@@ -482,6 +499,9 @@ int aqc_read_stats(aqc_ctx* ctx, const aqc_batch* reads, int32_t max_poly, int32
 /* util.editDistance(a, b) (util.py:65-83; native twin editdistance/_editdistance.h:16) for n string pairs
  * given as seq1 (a) / seq2 (b) of a batch; strings up to 64 bytes on the device path */
 int aqc_edit_distance(aqc_ctx* ctx, const aqc_batch* pairs, int32_t* dist);
+/* the cut pass alone: for every read of the batch (seq1 / qual1, qlen1 honoured) the part of its TRIMMED quality line that the cut
+ * keeps, view[i] = c0 | c1 << 16 (trim() by trim_front / trim_tail first; no mode set: 0 | n << 16) */
+int aqc_quality_cut_views(aqc_ctx* ctx, const aqc_batch* reads, const aqc_cut_config* cut, int32_t trim_front, int32_t trim_tail, uint32_t* view);
 
 /* ---- whole-input pipeline: the byte path of seqFilter.run's main loop (preprocesser.py:411-631) --------------------- */
 /* Reads one input (a read file, or a pair of mate files; plain, .gz, or text already in host memory), cuts it into chunks

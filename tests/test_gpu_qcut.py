@@ -1,0 +1,594 @@
+"""Per-read sliding-window quality cutting on the GPU (-m gpu): --cut_front / --cut_tail / --cut_right from the cut pass
+(quality_cut_kernel, csrc/aqc_qcut.hpp) through the verdict kernels to the CLI, against the model of tests/cut_rule.py.
+
+  seam        aqc_quality_cut_views against cut_window(), one batch per group size of the pass (8, 16, 32, 64 lanes per read): the
+              lengths at which the pass changes shape, six windows, three qualities, the seven mode combinations, the named quality
+              patterns at every length; irregular quality lines and fixed trims.
+  verdicts    a run with the cut on against a run of the same build, cut and trim off, on precut(records): every tier of the
+              lane-per-read kernel, paired and single-end, and the general kernel (reads of 321 bases; AQC_FORCE_GENERIC=1 in a child).
+  below 5     records the cut leaves under 5 bases, against the model: BADTRIM1 with read 2 untouched, BADTRIM2, the bad files' text.
+  counts      aqc_get_cut_stats against the model, with an accum_limit and over two contexts.
+  end to end  the CLI through the whole-input pipe and the serial text loop against a run on pre-cut files with the options off.
+  off is off  aqc_set_quality_cut(NULL) after a cut run gives what a context that never had the cut gives."""
+import bz2
+import gzip
+import json
+import os
+import random
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "tests", "golden")):       # (the child processes below run this file as a script)
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import cut_rule
+import test_host_golden as thg
+from afterqc_amd import after, capi, preprocesser, synth
+
+pytestmark = pytest.mark.gpu
+
+ERR_UNSUPPORTED = -7
+# lanes per read of quality_cut_kernel<G> -> the lengths of its batch: the host picks G by the batch's longest read (<= 128, <= 256,
+# <= 512, anything up to AQC_MAX_READ_LEN), so every group size gets a batch of its own whose longest read is its range's
+GROUP_LENGTHS = {8: [0, 1, 3, 4, 5, 15, 16, 17, 31, 32, 33, 127, 128], 16: [129, 159, 160, 161, 255, 256],
+                 32: [257, 288, 289, 320, 321, 511, 512], 64: [513, 999, 1000]}
+GROUP_RANGE = {8: (0, 128), 16: (129, 256), 32: (257, 512), 64: (513, 1000)}
+WINDOWS = [1, 4, 16, 17, 33, 1000]
+QUALITIES = [0, 20, 93]
+
+
+def cutcfg(modes, window=4, mean_quality=20):
+    return capi.CutConfig(int(modes[0]), int(modes[1]), int(modes[2]), window, mean_quality)
+
+
+def pack_mate(seqs, quals):
+    """-> (seq arena, qual arena, seq offsets, qual offsets, lengths, quality lengths): arenas of their own, so that a quality
+    line may have any length"""
+    sl = np.array([len(s) for s in seqs], dtype=np.uint32)
+    ql = np.array([len(x) for x in quals], dtype=np.uint32)
+    so, st = capi.Batch._offsets(sl)
+    qo, qt = capi.Batch._offsets(ql)
+    sa, qa = np.zeros(st, dtype=np.uint8), np.zeros(qt, dtype=np.uint8)
+    for i, (s, x) in enumerate(zip(seqs, quals)):
+        sa[int(so[i]):int(so[i]) + len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
+        qa[int(qo[i]):int(qo[i]) + len(x)] = np.frombuffer(bytes(x), dtype=np.uint8)
+    return sa, qa, so, qo, sl, ql
+
+
+def pack(seqs1, quals1, seqs2=None, quals2=None):
+    """a capi.Batch of byte strings; quality lines that are not as long as their sequence lines travel as qlen1 / qlen2"""
+    b = capi.Batch(len(seqs1))
+    b.seq1, b.qual1, b.off1, b.qoff1, b.len1, ql1 = pack_mate(seqs1, quals1)
+    irregular = not np.array_equal(b.len1, ql1)
+    ql2 = None
+    if seqs2 is not None:
+        b.seq2, b.qual2, b.off2, b.qoff2, b.len2, ql2 = pack_mate(seqs2, quals2)
+        irregular = irregular or not np.array_equal(b.len2, ql2)
+    if irregular:
+        b.qlen1, b.qlen2 = ql1, ql2
+    return b
+
+
+def bases(rng, n):
+    return bytes(rng.choice(b"ACGT") for _ in range(n))
+
+
+# ---- the seam against the model ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def seam_lines():
+    """per window and group size: the quality lines of every length of the group and every named pattern (one good window at every
+    start 0 .. 33 and at n - w, at every length), shared by the cases"""
+    out = {}
+    for W in WINDOWS:
+        for G, lengths in GROUP_LENGTHS.items():
+            rng = random.Random(4100 + 7 * W + G)
+            out[W, G] = [line for n in lengths for _, line in cut_rule.pattern_lines(n, W, rng)]
+    return out
+
+
+@pytest.mark.parametrize("G", sorted(GROUP_LENGTHS))
+@pytest.mark.parametrize("W", WINDOWS)
+def test_seam_against_the_model(W, G, gpu_engine, seam_lines):
+    """regular quality lines, one batch per group size: quality_cut_kernel<8>, <16>, <32> and <64> each against the model"""
+    lines = seam_lines[W, G]
+    rng = random.Random(W)
+    batch = pack([bases(rng, len(x)) for x in lines], lines)
+    assert batch.qlen1 is None and GROUP_RANGE[G][0] <= batch.max_len() <= GROUP_RANGE[G][1]
+    for Q in QUALITIES:
+        for modes in cut_rule.MODES:
+            c0, c1 = gpu_engine.quality_cut_views(batch, cutcfg(modes, W, Q))
+            want = [cut_rule.cut_window(x, W, Q, *modes) for x in lines]
+            got = list(zip(c0.tolist(), c1.tolist()))
+            bad = [i for i in range(len(lines)) if got[i] != want[i]]
+            assert not bad, (W, G, Q, modes, len(bad), [(len(lines[i]), got[i], want[i]) for i in bad[:5]])
+
+
+@pytest.mark.parametrize("trim", [(0, 0), (3, 0), (0, 7), (200, 200)])
+def test_seam_fixed_trim_and_irregular_lines(trim, gpu_engine):
+    """150-base reads behind a fixed trim; quality lines shorter and longer than their sequence lines (qlen1): the view is that of
+    the trimmed QUALITY line.  (A batch with quality lines of their own length always takes quality_cut_kernel<64>; the same trims
+    on regular lines, which take <16>, are the second half.)"""
+    rng = random.Random(77 + trim[0])
+    seqs, quals = [], []
+    for i in range(600):
+        n = 150
+        ql = n if i % 3 else rng.choice([0, 1, 4, 17, 100, 149, 151, 170, 400, 1000])
+        seqs.append(bases(rng, n))
+        quals.append(cut_rule.decaying_quality(rng, ql) if i % 2 else bytes(rng.randrange(33, 75) for _ in range(ql)))
+    batch = pack(seqs, quals)
+    assert batch.qlen1 is not None
+    for modes in cut_rule.MODES:
+        for W, Q in ((4, 20), (17, 25)):
+            c0, c1 = gpu_engine.quality_cut_views(batch, cutcfg(modes, W, Q), trim[0], trim[1])
+            want = [cut_rule.cut_window(cut_rule.trim(x, *trim), W, Q, *modes) for x in quals]
+            assert list(zip(c0.tolist(), c1.tolist())) == want, (modes, W, Q)
+    regular = [x[:150] + bytes([33 + 30]) * (150 - len(x)) for x in quals]
+    batch = pack(seqs, regular)
+    assert batch.qlen1 is None
+    for modes in cut_rule.MODES:
+        c0, c1 = gpu_engine.quality_cut_views(batch, cutcfg(modes, 4, 20), trim[0], trim[1])
+        assert list(zip(c0.tolist(), c1.tolist())) == [cut_rule.cut_window(cut_rule.trim(x, *trim), 4, 20, *modes) for x in regular], modes
+
+
+def test_seam_refuses_bad_options(gpu_engine):
+    batch = pack([b"ACGT"], [b"IIII"])
+    for W, Q in ((0, 20), (1001, 20), (4, -1), (4, 94)):
+        with pytest.raises(capi.AqcError) as e:
+            gpu_engine.quality_cut_views(batch, cutcfg((1, 0, 0), W, Q))
+        assert e.value.code == capi.ERR_ARG
+        with pytest.raises(capi.AqcError) as e:
+            gpu_engine.set_quality_cut(cutcfg((1, 0, 0), W, Q))
+        assert e.value.code == capi.ERR_ARG
+    gpu_engine.set_quality_cut(cutcfg((0, 0, 0), 0, -5))       # no mode set: off, whatever the rest says
+    gpu_engine.set_quality_cut(None)
+
+
+# ---- verdicts: the cut on against a run on the pre-cut records ------------------------------------------------------------------
+def base_config(paired, trim=(0, 0)):
+    cfg = capi.Config()
+    cfg.paired = 1 if paired else 0
+    cfg.seq_len_req = 35
+    cfg.poly_size_limit = 35
+    cfg.allow_mismatch_in_poly = 2
+    cfg.qualified_quality_phred = 15
+    cfg.unqualified_base_limit = 60
+    cfg.n_base_limit = 5
+    cfg.barcode_length = 12
+    cfg.set_verify("CAGTA")
+    cfg.qc_kmer = 8
+    cfg.trim_front = cfg.trim_front2 = trim[0]
+    cfg.trim_tail = cfg.trim_tail2 = trim[1]
+    return cfg
+
+
+def tailed_pairs(n, L, seed, short=()):
+    """synth.make_pairs (planted overlaps, adapter read-through, mismatches, N) with quality lines of this test's own: high up
+    to a knee in the read's last 40 %, single low bases sprinkled in front of it (never two in a window of four), decaying
+    behind it — no window of four in front of the knee is bad, no mate is cut below 5 bases.  short: records whose read 1 is high
+    for its first 9 .. 13 bases and phred 2 behind them: whatever the modes and a front trim of 2, the cut leaves 5 .. 15 bases."""
+    d = synth.make_pairs(n, L, seed=seed, short_frac=0.5, dirty=True)
+    rng = random.Random(seed)
+    out = []
+    for i in range(n):
+        mates = []
+        for k, (sq, ql) in enumerate((("seq1", "qual1"), ("seq2", "qual2"))):
+            if i in short and k == 0:
+                knee = rng.randint(9, 13)
+                line = bytearray([33 + 40] * knee + [33 + 2] * (L - knee))
+            else:
+                knee = rng.randint((6 * L) // 10, L)
+                line = bytearray(cut_rule.decaying_quality(rng, L, good=40, knee=knee))
+                for p in range(rng.randrange(5), knee - 1, 9):
+                    line[p] = 33 + 2
+            mates.append((d[sq][i].tobytes(), bytes(line)))
+        out.append((mates[0][0], mates[0][1], mates[1][0], mates[1][1]))
+    return out
+
+
+def run_pairs(eng, pairs, paired, cfg, cut, slot=0, accum_limit=capi.UINT64_MAX):
+    """one upload + run -> what the comparison looks at"""
+    batch = pack([p[0] for p in pairs], [p[1] for p in pairs], [p[2] for p in pairs] if paired else None, [p[3] for p in pairs] if paired else None)
+    eng.set_config(cfg)
+    eng.set_quality_cut(cut)
+    eng.reset_stats()
+    eng.upload(slot, batch)
+    eng.run(slot, accum_limit)
+    res = eng.fetch_results(slot)
+    qv = [eng.fetch_quality_views(slot, m) for m in ((0, 1) if paired else (0,))]
+    ovl, dist = eng.histograms()
+    return dict(res=res, qv=qv, counters=eng.counters(), ovl=ovl, dist=dist, words=eng.last_verdict_words(slot), deferred=eng.last_deferred(slot),
+                cut_ms=eng.cut_ms(slot), cut_stats=eng.cut_stats())
+
+
+def view_bytes(pairs, run, paired):
+    """the bytes each result keeps of every line: start / len of the result record, the quality views for the quality lines"""
+    out = []
+    for i, (p, r) in enumerate(zip(pairs, run["res"])):
+        row = []
+        for m in ((0, 1) if paired else (0,)):
+            a, l = int(r["start%d" % (m + 1)]), int(r["len%d" % (m + 1)])
+            qa, ql = int(run["qv"][m][0][i]), int(run["qv"][m][1][i])
+            row += [p[2 * m][a:a + l], p[2 * m + 1][qa:qa + ql]]
+        out.append(row)
+    return out
+
+
+def compare_runs(pairs, pre, A, B, paired):
+    for f in ("flag", "n_edits", "offset", "overlap_len", "distance", "len1") + (("len2",) if paired else ()):
+        assert np.array_equal(A["res"][f], B["res"][f]), f
+    assert A["res"]["edits"].tobytes() == B["res"]["edits"].tobytes()
+    assert view_bytes(pairs, A, paired) == view_bytes(pre, B, paired)
+    keep = np.ones(len(A["counters"]), dtype=bool)
+    keep[capi.C_TOTAL_BASES] = False
+    assert np.array_equal(A["counters"][keep], B["counters"][keep])
+    assert np.array_equal(A["ovl"], B["ovl"]) and np.array_equal(A["dist"], B["dist"])
+
+
+def precut_pairs(pairs, cut, paired):
+    out = []
+    for s1, q1, s2, q2 in pairs:
+        k1 = cut_rule.cut_lines(s1, q1, cut, 0)
+        k2 = cut_rule.cut_lines(s2, q2, cut, 1) if paired else (None, None)
+        out.append((k1[0], k1[1], k2[0], k2[1]))
+    return out
+
+
+VERDICT_CASES = [(150, 10, True, (0, 1, 0), (2, 3)), (150, 10, False, (1, 1, 1), (0, 0)), (250, 16, True, (1, 1, 0), (0, 0)), (250, 16, False, (0, 1, 0), (2, 3)),
+                 (280, 18, True, (0, 0, 1), (2, 3)), (280, 18, False, (0, 1, 1), (0, 0)), (310, 20, True, (1, 1, 1), (2, 3)), (310, 20, False, (0, 1, 0), (0, 0)),
+                 (321, 0, True, (0, 1, 0), (2, 3)), (321, 0, False, (1, 1, 1), (0, 0))]
+
+
+@pytest.mark.parametrize("L,words,paired,modes,trim", VERDICT_CASES)
+def test_verdicts_equal_a_run_on_precut_records(L, words, paired, modes, trim, gpu_engine):
+    n = 1500
+    short = set(range(7, n, 97))
+    pairs = tailed_pairs(n, L, 900 + L + int(paired), short)
+    model = cut_rule.CutConfig(*modes, window=4, mean_quality=20, trim_front=trim[0], trim_tail=trim[1])
+    pre = precut_pairs(pairs, model, paired)
+    assert min(len(p[0]) for p in pre) >= 5 and (not paired or min(len(p[2]) for p in pre) >= 5)
+    A = run_pairs(gpu_engine, pairs, paired, base_config(paired, trim), cutcfg(modes))
+    B = run_pairs(gpu_engine, pre, paired, base_config(paired), None)
+    assert A["words"] == words
+    assert A["cut_ms"] > 0 and B["cut_ms"] == 0
+    compare_runs(pairs, pre, A, B, paired)
+    assert A["cut_stats"].tolist() == cut_rule.cut_counts([p if paired else (p[0], p[1], None, None) for p in pairs], model)
+    if words:
+        # the fast path is kept: only a mate the cut leaves under 16 bases sends its record to the general kernel
+        under16 = sum(1 for p in pre if len(p[0]) < 16 or (paired and len(p[2]) < 16))
+        assert under16 >= len(short) - 1
+        assert A["deferred"] <= B["deferred"] + under16
+        assert A["deferred"] < n // 4
+
+
+def test_irregular_mates_take_the_views_too(gpu_engine):
+    """quality lines of their own length (LEN_IRR: the general kernel's): sequence and quality are each sliced by their own lengths,
+    the final quality view comes back through aqc_fetch_quality_views — against a run on the pre-cut records, irregular as well"""
+    rng = random.Random(31)
+    pairs = tailed_pairs(300, 150, 31)
+    for i in range(0, 300, 7):
+        s1, q1, s2, q2 = pairs[i]
+        # (longer than the sequence line: a shorter one ends the run at the overlap walk, as upstream's IndexError does)
+        if i % 2:
+            q1 = q1 + cut_rule.decaying_quality(rng, rng.randint(1, 30), good=38, knee=0)
+        else:
+            q2 = q2 + cut_rule.decaying_quality(rng, rng.randint(1, 30), good=38, knee=0)
+        pairs[i] = (s1, q1, s2, q2)
+    for modes in ((0, 1, 0), (1, 0, 1)):
+        model = cut_rule.CutConfig(*modes, window=4, mean_quality=20, trim_front=2, trim_tail=3)
+        pre = precut_pairs(pairs, model, True)
+        assert any(len(p[0]) != len(p[1]) for p in pre) and any(len(p[2]) != len(p[3]) for p in pre)
+        A = run_pairs(gpu_engine, pairs, True, base_config(True, (2, 3)), cutcfg(modes))
+        B = run_pairs(gpu_engine, pre, True, base_config(True), None)
+        assert A["words"] == 10 and A["deferred"] >= 43
+        compare_runs(pairs, pre, A, B, True)
+        assert A["cut_stats"].tolist() == cut_rule.cut_counts(pairs, model)
+
+
+# ---- records the cut leaves under 5 bases ------------------------------------------------------------------------------------
+def sub5_pairs(n=400, L=150, seed=5):
+    rng = random.Random(seed)
+    out = []
+    for i in range(n):
+        knees = [rng.randint((6 * L) // 10, L), rng.randint((6 * L) // 10, L)]
+        low = {i % 2} | ({1} if i % 5 == 0 else set())          # even records: read 1 goes under 5; odd: read 2; every fifth: both
+        q = [cut_rule.decaying_quality(rng, L, good=40, floor=2, knee=k) for k in knees]
+        for k in low:
+            hi = rng.randint(0, 2)                              # phred 40 for 0 .. 2 bases, 2 behind them: the cut leaves 0 or 4 bases
+            q[k] = bytes([33 + 40] * hi + [33 + 2] * (L - hi))
+        out.append((bases(rng, L), q[0], bases(rng, L), q[1]))
+    return out
+
+
+def test_reads_cut_below_five_bases(gpu_engine):
+    pairs = sub5_pairs()
+    trim = (2, 3)
+    model = cut_rule.CutConfig(0, 1, 0, window=4, mean_quality=20, trim_front=trim[0], trim_tail=trim[1])
+    A = run_pairs(gpu_engine, pairs, True, base_config(True, trim), cutcfg((0, 1, 0)), accum_limit=300)
+    gpu_engine.set_quality_cut(None)
+    n1 = n2 = 0
+    for i, (p, r) in enumerate(zip(pairs, A["res"])):
+        k1, k2 = cut_rule.cut_lines(p[0], p[1], model, 0), cut_rule.cut_lines(p[2], p[3], model, 1)
+        assert len(k1[0]) < 5 or len(k2[0]) < 5
+        a1, l1, a2, l2 = int(r["start1"]), int(r["len1"]), int(r["start2"]), int(r["len2"])
+        assert p[0][a1:a1 + l1] == k1[0]
+        if len(k1[0]) < 5:
+            assert int(r["flag"]) == capi.BADTRIM1
+            assert (a2, l2) == (0, len(p[2]))                   # read 2 is neither trimmed nor cut
+            n1 += 1
+        else:
+            assert int(r["flag"]) == capi.BADTRIM2
+            assert p[2][a2:a2 + l2] == k2[0]
+            n2 += 1
+    assert n1 >= 200 and n2 >= 100
+    # records below accum_limit only, and read 2 is not counted where it was left as it is
+    assert A["cut_stats"].tolist() == cut_rule.cut_counts(pairs, model, accum_limit=300)
+    assert int(A["counters"][capi.C_FLAG0 + capi.BADTRIM1]) + int(A["counters"][capi.C_FLAG0 + capi.BADTRIM2]) == 300
+
+
+def fastq_text(pairs, mate):
+    return b"".join(b"@r%d/%d\n%s\n+\n%s\n" % (i, mate + 1, p[2 * mate], p[2 * mate + 1]) for i, p in enumerate(pairs))
+
+
+def test_bad_file_text_of_reads_cut_below_five_bases(gpu_engine):
+    """text in, text out: every record goes to the bad streams as @BADTRIM1... / @BADTRIM2..., read 1 cut, read 2 cut only under BADTRIM2"""
+    pairs = sub5_pairs(300, 150, 6)
+    model = cut_rule.CutConfig(0, 1, 0, window=4, mean_quality=20)
+    gpu_engine.set_config(base_config(True))
+    gpu_engine.set_quality_cut(cutcfg((0, 1, 0)))
+    gpu_engine.reset_stats()
+    t = [fastq_text(pairs, 0), fastq_text(pairs, 1)]
+    pad = lambda b: np.frombuffer(b + b"\0" * 4096, dtype=np.uint8).copy()
+    info = gpu_engine.frame(1, pad(t[0]), len(t[0]), True, pad(t[1]), len(t[1]), True)
+    assert int(info.n) == len(pairs)
+    gpu_engine.run(1)
+    sizes = gpu_engine.format(1, len(pairs), False)
+    gpu_engine.set_quality_cut(None)
+    want = [[], []]
+    for i, p in enumerate(pairs):
+        k1, k2 = cut_rule.cut_lines(p[0], p[1], model, 0), cut_rule.cut_lines(p[2], p[3], model, 1)
+        flag = b"BADTRIM1" if len(k1[0]) < 5 else b"BADTRIM2"
+        if flag == b"BADTRIM1":
+            k2 = (p[2], p[3])
+        want[0].append(b"@%sr%d/1\n%s\n+\n%s\n" % (flag, i, k1[0], k1[1]))
+        want[1].append(b"@%sr%d/2\n%s\n+\n%s\n" % (flag, i, k2[0], k2[1]))
+    for file in (0, 1):
+        assert sizes[file * 3] == 0
+        nb = sizes[file * 3 + 1]
+        buf = np.zeros(nb + 64, dtype=np.uint8)
+        gpu_engine.fetch_text(1, file, 1, buf, buf.size)
+        assert buf[:nb].tobytes() == b"".join(want[file])
+
+
+# ---- the counts over two contexts ---------------------------------------------------------------------------------------------
+def test_cut_stats_add_up_over_two_contexts(gpu_engine):
+    pairs = tailed_pairs(600, 150, 12)
+    model = cut_rule.CutConfig(1, 1, 0, window=4, mean_quality=20)
+    other = capi.Engine(0, 2)
+    try:
+        a = run_pairs(gpu_engine, pairs[:350], True, base_config(True), cutcfg((1, 1, 0)))
+        b = run_pairs(other, pairs[350:], True, base_config(True), cutcfg((1, 1, 0)))
+        merged = capi.MergedEngines([gpu_engine, other]).cut_stats()
+        assert merged.tolist() == cut_rule.cut_counts(pairs, model)
+        assert (a["cut_stats"] + b["cut_stats"]).tolist() == merged.tolist()
+        gpu_engine.reset_stats()
+        assert gpu_engine.cut_stats().tolist() == [0, 0, 0, 0]
+    finally:
+        other.close()
+        gpu_engine.set_quality_cut(None)
+
+
+# ---- off is off -------------------------------------------------------------------------------------------------------------
+def test_off_after_a_cut_run_is_the_run_without_it(gpu_engine):
+    pairs = tailed_pairs(1200, 150, 44)
+    cfg = base_config(True, (2, 3))
+    fresh = capi.Engine(0, 2)
+    try:
+        want = run_pairs(fresh, pairs, True, cfg, None)            # a context that never had the cut
+    finally:
+        fresh.close()
+    run_pairs(gpu_engine, pairs, True, cfg, cutcfg((1, 1, 1)))
+    got = run_pairs(gpu_engine, pairs, True, cfg, None)            # the same slot, the cut taken away again
+    assert got["res"].tobytes() == want["res"].tobytes()
+    assert np.array_equal(got["counters"], want["counters"]) and np.array_equal(got["ovl"], want["ovl"]) and np.array_equal(got["dist"], want["dist"])
+    assert got["cut_ms"] == 0 and got["words"] == want["words"] == 10
+    assert got["cut_stats"].tolist() == [0, 0, 0, 0]
+
+
+def test_barcode_with_the_cut_is_unsupported(gpu_engine):
+    pairs = tailed_pairs(64, 150, 3)
+    cfg = base_config(True)
+    cfg.barcode = 1
+    with pytest.raises(capi.AqcError) as e:
+        run_pairs(gpu_engine, pairs, True, cfg, cutcfg((0, 1, 0)))
+    assert e.value.code == ERR_UNSUPPORTED
+    gpu_engine.set_quality_cut(None)
+
+
+# ---- child processes: AQC_FORCE_GENERIC=1, AQC_FUSED=1 ----------------------------------------------------------------------------
+def child_generic():
+    """the general kernel alone decides 150-base pairs with the cut on: equal to its run on the pre-cut pairs"""
+    eng = capi.Engine(0, 2)
+    pairs = tailed_pairs(800, 150, 71, set(range(3, 800, 50)))
+    model = cut_rule.CutConfig(1, 1, 0, window=4, mean_quality=20, trim_front=2, trim_tail=3)
+    pre = precut_pairs(pairs, model, True)
+    A = run_pairs(eng, pairs, True, base_config(True, (2, 3)), cutcfg((1, 1, 0)))
+    B = run_pairs(eng, pre, True, base_config(True), None)
+    compare_runs(pairs, pre, A, B, True)
+    assert A["cut_stats"].tolist() == cut_rule.cut_counts(pairs, model)
+    print(json.dumps({"words": A["words"], "cut_ms_on": A["cut_ms"] > 0}))
+
+
+def child_fused():
+    """AQC_FUSED=1: with the cut on the verdict kernel never places the records itself; with the cut off again it does"""
+    eng = capi.Engine(0, 2)
+    pairs = tailed_pairs(512, 150, 72)
+    t = [fastq_text(pairs, 0), fastq_text(pairs, 1)]
+    pad = lambda b: np.frombuffer(b + b"\0" * 4096, dtype=np.uint8).copy()
+    out = []
+    for cut in (cutcfg((0, 1, 0)), None):
+        eng.set_config(base_config(True))
+        eng.set_quality_cut(cut)
+        eng.reset_stats()
+        info = eng.frame(0, pad(t[0]), len(t[0]), True, pad(t[1]), len(t[1]), True)
+        eng.run(0)
+        eng.format(0, int(info.n), False)
+        out.append((eng.format_fused(0), eng.cut_ms(0) > 0))
+    print(json.dumps({"fused": out}))
+
+
+def run_child(role, env):
+    e = dict(os.environ)
+    e.update(env)
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), role], capture_output=True, text=True, timeout=300, env=e, cwd=os.path.join(ROOT, "tests"))
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    return json.loads(p.stdout.strip().splitlines()[-1])
+
+
+def test_general_kernel_alone_in_a_child_process():
+    assert run_child("generic", {"AQC_FORCE_GENERIC": "1"}) == {"words": 0, "cut_ms_on": True}
+
+
+def test_fused_placement_is_back_with_the_cut_off_in_a_child_process():
+    assert run_child("fused", {"AQC_FUSED": "1"}) == {"fused": [[0, True], [1, False]]}
+
+
+# ---- end to end -------------------------------------------------------------------------------------------------------------
+def e2e_pairs(n, L, seed):
+    """tailed pairs with one irregular-quality record and one record whose cut leaves fewer than 16 bases (none under 5)"""
+    pairs = tailed_pairs(n, L, seed, short={5, n // 2})
+    s1, q1, s2, q2 = pairs[9]
+    pairs[9] = (s1, q1 + bytes([33 + 3]) * 11, s2, q2)          # (a quality line longer than its sequence line)
+    return pairs
+
+
+def write_inputs(work, tag, pairs, paired, gz, index=False):
+    os.makedirs(work, exist_ok=True)
+    names = []
+    for mate in range(2 if paired else 1):
+        text = b"".join(b"@SIM:1:FC1:1:1101:%d:%d %d:N:0:ACGT\n%s\n+\n%s\n" % (1000 + i, 2000 + i, mate + 1, p[2 * mate], p[2 * mate + 1]) for i, p in enumerate(pairs))
+        path = os.path.join(work, "%s_R%d.fq%s" % (tag, mate + 1, gz))
+        with (gzip.open(path, "wb", compresslevel=1) if gz == ".gz" else bz2.open(path, "wb") if gz == ".bz2" else open(path, "wb")) as f:
+            f.write(text)
+        names.append(path)
+    if index:
+        for k in (1, 2):
+            path = os.path.join(work, "%s_I%d.fq" % (tag, k))
+            with open(path, "wb") as f:
+                f.write(b"".join(b"@SIM:1:FC1:1:1101:%d:%d %d:N:0:ACGT\nACGTACGT\n+\nIIIIIIII\n" % (1000 + i, 2000 + i, k) for i in range(len(pairs))))
+            names.append(path)
+    return names
+
+
+def run_cli(work, files, paired, argv, kw, engine, index=False):
+    args = ["-1", files[0]] + (["-2", files[1]] if paired else []) + ["-g", os.path.join(work, "good"), "--qc_sample", "0", "--barcode", "off"] + argv
+    if index:
+        args += ["-7", files[-2], "-5", files[-1]]
+    options, _ = after.parseCommand(args)
+    after.finalize_options(options)
+    options.barcode = False
+    kw = dict(kw)
+    if kw.pop("own_engines", False):
+        engine = None
+    flt = preprocesser.seqFilter(options, engine=engine, **kw)
+    stat = flt.run()
+    return stat, flt.used_pipe
+
+
+def read_outputs(work):
+    out = {}
+    for folder in ("good", "bad", "overlap", "merged"):
+        d = os.path.join(work, folder)
+        if not os.path.isdir(d):
+            continue
+        for f in sorted(os.listdir(d)):
+            p = os.path.join(d, f)
+            with (gzip.open(p, "rb") if f.endswith(".gz") else open(p, "rb")) as fh:
+                # the two runs' inputs are named "raw_*" and "pre_*"
+                out[folder + "/" + f[4:]] = fh.read()
+    return out
+
+
+E2E_CASES = {
+    # name: (paired, input compression, argv with the cut, argv of the pre-cut run, model, driver, index files)
+    "pipe_pe": (True, "", ["--cut_tail", "on"], [], dict(tail=1), "pipe_small_chunks", False),
+    "pipe_se_gz": (False, ".gz", ["--cut_front", "on", "--cut_tail", "on"], [], dict(front=1, tail=1), "pipe_small_chunks", False),
+    "pipe_two_contexts_merged": (True, "", ["--cut_tail", "on", "--store_merged", "on"], ["--store_merged", "on"], dict(tail=1), "pipe_two_contexts", False),
+    "text_pe_gz_overlap": (True, ".gz", ["--cut_right", "on", "--store_overlap", "on"], ["--store_overlap", "on"], dict(right=1), "text", False),
+    "text_se_trim": (False, "", ["--cut_tail", "on", "--cut_window_size", "5", "--cut_mean_quality", "22"], [], dict(tail=1, window=5, mean_quality=22), "text", False),
+    "text_pe_index": (True, "", ["--cut_front", "on", "--cut_tail", "on", "--cut_right", "on"], [], dict(front=1, tail=1, right=1), "text", True),
+    "pipe_pe_bz2": (True, ".bz2", ["--cut_tail", "on", "--cut_right", "on"], [], dict(tail=1, right=1), "pipe_small_chunks", False),
+    "text_pe_debubble": (True, "", ["--cut_tail", "on", "--debubble"], ["--debubble"], dict(tail=1), "text", False),
+    "text_pe_qc_only": (True, "", ["--cut_front", "on", "--cut_tail", "on", "--qc_only", "--qc_sample", "300"], ["--qc_only", "--qc_sample", "300"], dict(front=1, tail=1), "text", False),
+}
+
+
+@pytest.mark.parametrize("name", sorted(E2E_CASES))
+def test_cli_equals_a_run_on_precut_files(name, tmp_path, gpu_engine):
+    paired, gz, argv_cut, argv_pre, model_kw, driver, index = E2E_CASES[name]
+    trim = (2, 3) if name in ("text_se_trim", "pipe_pe") else (0, 0)
+    model = cut_rule.CutConfig(trim_front=trim[0], trim_tail=trim[1], **model_kw)
+    pairs = e2e_pairs(900, 150, 300 + len(name))
+    pre = precut_pairs(pairs, model, paired)
+    assert min(len(p[0]) for p in pre) >= 5 and (not paired or min(len(p[2]) for p in pre) >= 5)
+    assert any(len(p[0]) < 16 for p in pre) and any(len(p[0]) != len(p[1]) for p in pairs)
+    kw = thg.MODES[driver] if driver in thg.MODES else thg.PIPE_MODES[driver]
+    work = [os.path.join(str(tmp_path), "a"), os.path.join(str(tmp_path), "b")]
+    fa = write_inputs(work[0], "raw", pairs, paired, gz, index)
+    fb = write_inputs(work[1], "pre", [p if paired else (p[0], p[1], b"", b"") for p in pre], paired, gz, index)
+    extra = []
+    if "--debubble" in argv_cut:
+        # a circle around record 100's place on the tile (the names' x = 1000 + i, y = 2000 + i, lane 1, tile field 1101: upstream
+        # drops the field's first character, preprocesser.py:187-192)
+        with open(os.path.join(str(tmp_path), "circles.csv"), "w") as f:
+            f.write("x,y,radius,lane,tile\n1100,2100,30,1,101\n")
+        extra = ["--debubble_dir", str(tmp_path)]
+    sa, pipe_a = run_cli(work[0], fa, paired, ["-f", str(trim[0]), "-t", str(trim[1])] + argv_cut + extra, kw, gpu_engine, index)
+    sb, pipe_b = run_cli(work[1], fb, paired, ["-f", "0", "-t", "0"] + argv_pre + extra, kw, gpu_engine, index)
+    # the driver the case names is the driver that ran: no quiet fall-back to the serial loop with the cut on
+    assert pipe_a == pipe_b == name.startswith("pipe_"), (pipe_a, pipe_b)
+    oa, ob = read_outputs(work[0]), read_outputs(work[1])
+    assert sorted(oa) == sorted(ob)
+    if "--qc_only" in argv_cut:
+        assert not oa
+    else:
+        assert any(k.startswith("good/") for k in oa) and any(k.startswith("bad/") for k in oa)
+    if "--debubble" in argv_cut:
+        assert sa["afterqc_main_summary"]["bad_reads_with_reads_in_bubble"] >= 20
+    if "--store_merged" in argv_cut:
+        assert any(k.startswith("merged/") and oa[k] for k in oa)
+    if "--store_overlap" in argv_cut:
+        assert any(k.startswith("overlap/") and oa[k] for k in oa)
+    for k in oa:
+        assert oa[k] == ob[k], k
+    # the statistics: every key the run without the options has, but what sees the raw reads — total_bases, the pre-filter QC
+    # sections and readlen (the pre-filter sample's read length) — and the echo of the options
+    assert "quality_cut" in sa and "quality_cut" not in sb
+    # (--qc_only ends upstream's loop once the sample is full, preprocesser.py:630-631: the records the run without the options
+    #  counted are the records the cut's counts cover)
+    counted = sb["afterqc_main_summary"]["total_reads"] if "--qc_only" in argv_cut else None
+    assert counted is None or 300 <= counted < len(pairs)
+    want = cut_rule.cut_counts([p if paired else (p[0], p[1], None, None) for p in pairs], model, accum_limit=counted)
+    qc = sa["quality_cut"]
+    assert [qc["read1_cut_reads"], qc["read1_cut_bases"], qc["read2_cut_reads"], qc["read2_cut_bases"]] == want
+    assert (qc["cut_front"], qc["cut_tail"], qc["cut_right"]) == (model.front, model.tail, model.right)
+    assert (qc["cut_window_size"], qc["cut_mean_quality"]) == (model.window, model.mean_quality)
+    assert sorted(k for k in sa if k != "quality_cut") == sorted(sb)
+    for k in sb:
+        if k == "command":
+            continue
+        if k == "afterqc_main_summary":
+            skip = ("total_bases", "readlen")
+            assert {x: v for x, v in sa[k].items() if x not in skip} == {x: v for x, v in sb[k].items() if x not in skip}
+        elif isinstance(sb[k], dict) and any("prefilter" in x for x in sb[k]):
+            assert {x: v for x, v in sa[k].items() if "prefilter" not in x} == {x: v for x, v in sb[k].items() if "prefilter" not in x}, k
+        else:
+            assert sa[k] == sb[k], k
+
+
+if __name__ == "__main__":
+    {"generic": child_generic, "fused": child_fused}[sys.argv[1]]()

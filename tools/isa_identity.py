@@ -3,11 +3,17 @@
 Functions are keyed by mangled name; what depends only on the order of definition is normalised away: the function index in
 .LBB<i>_<j> / .LJTI<i>_<j> / .Lfunc_begin<i> / .Lfunc_end<i> labels, .loc / .file / .cfi and comment lines, trailing comments, and
 the order of the functions in the file.  What is compared is the instruction stream and, for kernels, the whole .amdhsa_kernel
-block (registers, LDS, scratch).  argv: before.s after.s [-v]; exit status 1 if anything differs or is missing."""
+block (registers, LDS, scratch).  argv: before.s after.s [-v] [--rename REGEX REPL]; exit status 1 if anything differs or is
+missing.  --rename rewrites the text of after.s first (re.sub): a kernel template that gained a parameter has new mangled names, and
+its old instances are compared under their old ones."""
 import difflib, re, sys
 
-def functions(path):
+RENAME = (sys.argv[sys.argv.index('--rename') + 1], sys.argv[sys.argv.index('--rename') + 2]) if '--rename' in sys.argv else None
+
+def functions(path, rename=None):
     s = open(path).read()
+    if rename:
+        s = re.sub(rename[0], rename[1], s)
     out = {}
     for m in re.finditer(r'^(\S+):[ \t]*; @\1\n(.*?)^\.Lfunc_end\d+:', s, re.S | re.M):
         body = []
@@ -19,7 +25,7 @@ def functions(path):
         out[m.group(1)] = (body, '.amdhsa_kernel ' + m.group(1) in m.group(2))
     return out
 
-a, b = functions(sys.argv[1]), functions(sys.argv[2])
+a, b = functions(sys.argv[1]), functions(sys.argv[2], RENAME)
 missing = sorted(set(a) - set(b))
 added = sorted(set(b) - set(a))
 differ = sorted(n for n in a if n in b and a[n][0] != b[n][0])

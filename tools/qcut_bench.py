@@ -1,0 +1,166 @@
+#!/usr/bin/env python3
+"""Measure per-read quality cutting (--cut_front / --cut_tail / --cut_right) on the MI355X: 1 M pairs of 2 x 150 and 2 x 300 resident
+in HBM, reads with decaying quality tails.
+
+    python tools/qcut_bench.py kernels [--pairs N] [--reps R]
+        two contexts in one process, both with a fixed trim (-f 2 -t 3), one with --cut_tail on, their aqc_run ALTERNATING:
+        the cut pass's time (aqc_cut_ms) and its rate over the bytes it must move — both mates' quality bytes plus 8 bytes of
+        views per pair — as a share of the 8000 GB/s peak; the verdict kernel's CUT instance against the plain instance of the
+        same tier (HIP events around AQC_K_FILTER_OVERLAP), and the deferred share of each
+    python tools/qcut_bench.py step [--tree DIR] [--cut_tail] [--pairs N] [--reps R]
+        the device step on text resident in HBM: aqc_reframe -> aqc_run -> aqc_format, wall time per step with the slot synced.
+        --tree: import afterqc_amd from another checkout (the parent's, built there) — a job script alternates processes of the
+        two trees; the step uses only calls both have.  --cut_tail: with the cut on (this tree only)
+
+Results: profiles/r16_qcut.txt."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PEAK = 8.0e12          # HBM_PEAK_GBS of bench.py
+
+
+def make_input(n, L):
+    """synth.make_pairs with quality lines that are high up to a knee in the last 40 % of the read and decay behind it"""
+    import numpy as np
+    from afterqc_amd import synth
+    d = synth.make_pairs(n, L, seed=1003, workers=min(16, os.cpu_count() or 1))
+    rng = np.random.Generator(np.random.PCG64(1616 + L))
+    j = np.arange(L, dtype=np.int32)[None, :]
+    for k in ("qual1", "qual2"):
+        knee = rng.integers((6 * L) // 10, L + 1, n).astype(np.int32)[:, None]
+        noise = rng.integers(0, 6, (n, L)).astype(np.int32)
+        q = np.where(j < knee, 40 - noise, np.maximum(2, 32 - (3 * (j - knee)) // 2 - noise))
+        d[k] = (q + 33).astype(np.uint8)
+    return d
+
+
+def config(trim=(0, 0)):
+    from afterqc_amd import capi
+    cfg = capi.Config()
+    cfg.paired = 1
+    cfg.seq_len_req, cfg.poly_size_limit, cfg.allow_mismatch_in_poly = 35, 35, 2
+    cfg.qualified_quality_phred, cfg.unqualified_base_limit, cfg.n_base_limit = 15, 60, 5
+    cfg.barcode_length = 12
+    cfg.set_verify("CAGTA")
+    cfg.qc_kmer = 8
+    cfg.trim_front = cfg.trim_front2 = trim[0]
+    cfg.trim_tail = cfg.trim_tail2 = trim[1]
+    return cfg
+
+
+def kernels(a):
+    import numpy as np
+    from afterqc_amd import capi
+    plain, cut = capi.Engine(0, 1), capi.Engine(0, 1)
+    print("# qcut_bench kernels on %s: %d pairs, %d warm-up + %d timed aqc_run per context, alternating; both contexts -f 2 -t 3, `cut` with --cut_tail on (window 4, quality 20)"
+          % (plain.device_name(), a.pairs, a.warmup, a.reps), flush=True)
+    print("# %-6s %-6s %5s %10s %9s %7s %9s | %9s %9s %8s" % ("load", "ctx", "words", "verdict_ms", "min_ms", "max/min", "deferred", "cut_ms", "min_ms", "of_peak"))
+    for L in (150, 300):
+        d = make_input(a.pairs, L)
+        batch = capi.Batch.from_matrices(d["seq1"], d["qual1"], d["len1"], d["seq2"], d["qual2"], d["len2"])
+        engines = (("plain", plain), ("cut", cut))
+        for tag, eng in engines:
+            eng.set_config(config((2, 3)))
+            eng.set_quality_cut(capi.CutConfig(0, 1, 0, 4, 20) if tag == "cut" else None)
+            eng.reset_stats()
+            eng.upload(0, batch)
+        ms, cms = {}, []
+        for k in range(a.warmup + a.reps):
+            for tag, eng in engines:
+                eng.timing_reset(0)
+                eng.run(0)
+                t, cnt = eng.timing_mean(0)
+                assert cnt[capi.K_FILTER_OVERLAP] == 1
+                if k >= a.warmup:
+                    ms.setdefault(tag, []).append(float(t[capi.K_FILTER_OVERLAP]))
+                    if tag == "cut":
+                        cms.append(eng.cut_ms(0))
+        for tag, eng in engines:
+            v = np.array(ms[tag])
+            row = "  pe%-4d %-6s %5d %10.4f %9.4f %7.3f %9.5f" % (L, tag, eng.last_verdict_words(0), float(np.median(v)), float(v.min()), float(v.max() / v.min()),
+                                                                 eng.last_deferred(0) / batch.n)
+            if tag == "cut":
+                c = np.array(cms)
+                moved = (2 * L + 8) * batch.n
+                row += " | %9.4f %9.4f %8.4f" % (float(np.median(c)), float(c.min()), moved / (float(np.median(c)) * 1e-3) / PEAK)
+            print(row, flush=True)
+        st = cut.cut_stats()
+        print("  pe%-4d the CUT instance takes %.3f x the plain instance's time (medians); cut pass + CUT instance %.4f ms against %.4f ms; reads cut %d + %d of %d pairs, bases %d + %d"
+              % (L, float(np.median(ms["cut"]) / np.median(ms["plain"])), float(np.median(ms["cut"]) + np.median(cms)), float(np.median(ms["plain"])),
+                 int(st[0]) // (a.warmup + a.reps), int(st[2]) // (a.warmup + a.reps), batch.n, int(st[1]) // (a.warmup + a.reps), int(st[3]) // (a.warmup + a.reps)), flush=True)
+    plain.close()
+    cut.close()
+
+
+def step(a):
+    sys.path.insert(0, os.path.abspath(a.tree) if a.tree else ROOT)
+    import numpy as np
+    from afterqc_amd import capi, synth
+    eng = capi.Engine(0, 2)
+    label = ("parent" if a.tree else "this") + (" cut_tail" if a.cut_tail else "")
+    for L in (150, 300):
+        d = make_input(a.pairs, L)
+        n_rec = len(d["len1"])
+        eng.set_config(config())
+        if a.cut_tail:
+            eng.set_quality_cut(capi.CutConfig(0, 1, 0, 4, 20))
+        eng.reset_stats()
+        w = synth.fixed_record_width(L)
+        texts = []
+        for mate in (1, 2):
+            hb = eng.host_buffer(n_rec * w + 4096)
+            _, nbytes = synth.render_fastq_fixed(d["seq%d" % mate], d["qual%d" % mate], mate, out=hb.array)
+            texts.append((hb, nbytes))
+        info = eng.frame(0, texts[0][0].array, texts[0][1], True, texts[1][0].array, texts[1][1], True)
+        assert int(info.n) == n_rec
+        t = []
+        for k in range(a.warmup + a.reps):
+            eng.sync(0)
+            t0 = time.perf_counter()
+            eng.reframe(0)
+            eng.run(0)
+            sizes = eng.format(0, n_rec, False)
+            eng.sync(0)
+            if k >= a.warmup:
+                t.append(1000.0 * (time.perf_counter() - t0))
+        if a.detail:
+            # where a step's time goes: each call synced on its own, and the verdict kernel by its HIP events
+            parts = {"reframe": [], "run": [], "format": [], "verdict_kernel": []}
+            for k in range(a.reps):
+                for name, call in (("reframe", lambda: eng.reframe(0)), ("run", lambda: eng.run(0)), ("format", lambda: eng.format(0, n_rec, False))):
+                    t0 = time.perf_counter()
+                    call()
+                    eng.sync(0)
+                    parts[name].append(1000.0 * (time.perf_counter() - t0))
+                parts["verdict_kernel"].append(float(eng.kernel_ms(0)[capi.K_FILTER_OVERLAP]))
+            print("%-16s pe%-4d medians, each call synced: %s" % (label, L, "  ".join("%s %.4f" % (k, float(np.median(v))) for k, v in parts.items())), flush=True)
+        v = np.array(t)
+        print("%-16s pe%-4d device_step ms min %.4f median %.4f max %.4f  good bytes %d" % (label, L, float(v.min()), float(np.median(v)), float(v.max()), int(sizes[0] + sizes[3])), flush=True)
+    eng.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    for name in ("kernels", "step"):
+        p = sub.add_parser(name)
+        p.add_argument("--pairs", type=int, default=1000000)
+        p.add_argument("--warmup", type=int, default=3)
+        p.add_argument("--reps", type=int, default=10)
+        if name == "step":
+            p.add_argument("--tree", default="")
+            p.add_argument("--cut_tail", action="store_true")
+            p.add_argument("--detail", action="store_true", help="also time reframe / run / format synced one by one, and the verdict kernel's events")
+    a = ap.parse_args()
+    if a.cmd == "kernels":
+        sys.path.insert(0, ROOT)
+        kernels(a)
+    else:
+        step(a)
+
+
+if __name__ == "__main__":
+    main()
