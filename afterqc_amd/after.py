@@ -59,6 +59,9 @@ OPTIONS = [
     ("", "--cut_right", dict(default="off", help="specify whether to cut each read at the first window (from the front, or from where cut_front starts the read) whose mean quality is below cut_mean_quality, dropping that window and everything behind it. Default is off")),
     ("", "--cut_window_size", dict(default=4, type="int", help="the window size of cut_front / cut_tail / cut_right, 1 to 1000. Default is 4")),
     ("", "--cut_mean_quality", dict(default=20, type="int", help="the mean phred quality a window needs to be good, 0 to 93. Default is 20")),
+    ("", "--adapter_sequence", dict(default=None, help="the adapter of read 1, 4 to 64 letters of A, C, G, T: each read is cut at the first place where the adapter (or, at the read's tail, its first adapter_min_overlap bases or more) lies with at most one mismatch per eight compared bases. Runs inside the trim stage, after -f / -t and after cut_front / cut_tail / cut_right. By default no adapter is searched")),
+    ("", "--adapter_sequence_r2", dict(default=None, help="the adapter of read 2, by default the same as adapter_sequence; given alone, only read 2 is searched")),
+    ("", "--adapter_min_overlap", dict(default=4, type="int", help="the fewest bases of an adapter that must lie on the read for a match at its tail, 1 to the length of the shorter adapter. Default is 4")),
     ("", "--qc_only", dict(action="store_true", default=False, help="if qconly is true, only QC result will be output, this can be much fast")),
     ("", "--qc_sample", dict(default=200000, type="int", help="sample up to qc_sample reads when do QC, 0 means sample all reads. Default is 200,000")),
     ("", "--qc_kmer", dict(default=8, type="int", help="specify the kmer length for KMER statistics for QC, default is 8")),
@@ -72,6 +75,7 @@ OPTIONS = [
 
 CUT_MAX_WINDOW = 1000       # AQC_MAX_READ_LEN
 CUT_MAX_QUALITY = 93
+ADAPTER_MIN_LEN, ADAPTER_MAX_LEN = 4, 64
 
 
 def parseBool(s):
@@ -104,6 +108,31 @@ def finalize_options(options):
         raise SystemExit("afterqc_amd: --cut_window_size %d is outside 1 .. %d" % (options.cut_window_size, CUT_MAX_WINDOW))
     if not 0 <= options.cut_mean_quality <= CUT_MAX_QUALITY:
         raise SystemExit("afterqc_amd: --cut_mean_quality %d is outside 0 .. %d" % (options.cut_mean_quality, CUT_MAX_QUALITY))
+    # (a run of one single-end file, -1 without -2, has no read 2: its adapter takes no part, and given alone it is refused below
+    #  and in seqFilter.run, which also sees the single-end files of a folder)
+    single = options.read1_file is not None and options.read2_file is None
+    given = []
+    for k in ("adapter_sequence", "adapter_sequence_r2"):
+        a = getattr(options, k)
+        if a is None:
+            continue
+        a = a.upper()
+        if not ADAPTER_MIN_LEN <= len(a) <= ADAPTER_MAX_LEN:
+            raise SystemExit("afterqc_amd: --%s has %d letters, outside %d .. %d" % (k, len(a), ADAPTER_MIN_LEN, ADAPTER_MAX_LEN))
+        if set(a) - set("ACGT"):
+            raise SystemExit("afterqc_amd: --%s %s holds letters other than A, C, G, T" % (k, a))
+        setattr(options, k, a)
+        if not (single and k == "adapter_sequence_r2"):
+            given.append(a)
+    if single and options.adapter_sequence_r2 is not None and options.adapter_sequence is None:
+        raise SystemExit("afterqc_amd: --adapter_sequence_r2 is given alone but the input is single-end (no -2): there is no read 2 to search; "
+                         "give the adapter as --adapter_sequence")
+    if options.adapter_sequence_r2 is None:
+        options.adapter_sequence_r2 = options.adapter_sequence          # (read 2 takes read 1's adapter)
+    shortest = min(len(a) for a in given) if given else ADAPTER_MAX_LEN
+    if not 1 <= options.adapter_min_overlap <= shortest:
+        raise SystemExit("afterqc_amd: --adapter_min_overlap %d is outside 1 .. %d%s" % (options.adapter_min_overlap, shortest,
+                                                                                         " (the shorter adapter)" if given else ""))
     options.trim_front2 = options.trim_front
     options.trim_tail2 = options.trim_tail
     return options

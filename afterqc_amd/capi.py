@@ -102,6 +102,28 @@ class CutConfig(C.Structure):
         return bool(self.front or self.tail or self.right)
 
 
+class AdapterConfig(C.Structure):
+    """struct aqc_adapter_config: the adapters to trim from read 1 / read 2 (--adapter_sequence / --adapter_sequence_r2); an
+    empty adapter: that mate is not searched"""
+    _fields_ = [("len1", C.c_int32), ("len2", C.c_int32), ("min_overlap", C.c_int32), ("seq1", C.c_uint8 * 64), ("seq2", C.c_uint8 * 64)]
+
+    def __init__(self, seq1=b"", seq2=b"", min_overlap=4):
+        super().__init__()
+        seq1, seq2 = [s.encode() if isinstance(s, str) else bytes(s) for s in (seq1, seq2)]
+        # (a length the library refuses travels as it is, with the bytes that fit)
+        self.len1, self.len2, self.min_overlap = len(seq1), len(seq2), int(min_overlap)
+        for dst, s in ((self.seq1, seq1), (self.seq2, seq2)):
+            for i, ch in enumerate(s[:64]):
+                dst[i] = ch
+
+    @property
+    def on(self):
+        return bool(self.len1 or self.len2)
+
+    def adapters(self):
+        return bytes(self.seq1[:min(self.len1, 64)]), bytes(self.seq2[:min(self.len2, 64)])
+
+
 class BatchStruct(C.Structure):
     """struct aqc_batch"""
     _fields_ = [("n", C.c_uint64), ("first_index", C.c_uint64),
@@ -365,6 +387,10 @@ def load_library():
     lib.aqc_get_cut_stats.argtypes = [P, P]
     lib.aqc_cut_ms.argtypes = [P, C.c_int, C.POINTER(C.c_float)]
     lib.aqc_quality_cut_views.argtypes = [P, C.POINTER(BatchStruct), C.POINTER(CutConfig), C.c_int32, C.c_int32, P]
+    lib.aqc_set_adapter_trim.argtypes = [P, C.POINTER(AdapterConfig)]
+    lib.aqc_get_adapter_stats.argtypes = [P, P]
+    lib.aqc_adapter_ms.argtypes = [P, C.c_int, C.POINTER(C.c_float)]
+    lib.aqc_adapter_views.argtypes = [P, C.POINTER(BatchStruct), C.POINTER(AdapterConfig), C.c_int32, C.c_int32, P, P]
     lib.aqc_upload.argtypes = [P, C.c_int, C.POINTER(BatchStruct)]
     lib.aqc_run.argtypes = [P, C.c_int, C.c_uint64]
     lib.aqc_qc_stat.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int]
@@ -456,7 +482,8 @@ def load_library():
                  "aqc_timing_mean", "aqc_get_counters", "aqc_get_histograms", "aqc_get_qc", "aqc_get_kmers",
                  "aqc_overlap", "aqc_read_stats", "aqc_edit_distance", "aqc_frame", "aqc_frame_mixed", "aqc_reframe", "aqc_format", "aqc_format_plain",
                  "aqc_fetch_text", "aqc_fetch_quality_views", "aqc_error_record", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused",
-                 "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms", "aqc_set_quality_cut", "aqc_get_cut_stats", "aqc_cut_ms", "aqc_quality_cut_views"):
+                 "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms", "aqc_set_quality_cut", "aqc_get_cut_stats", "aqc_cut_ms", "aqc_quality_cut_views",
+                 "aqc_set_adapter_trim", "aqc_get_adapter_stats", "aqc_adapter_ms", "aqc_adapter_views"):
         getattr(lib, name).restype = C.c_int
     if lib.aqc_abi_version() != 3:
         raise RuntimeError("libafterqc_hip.so ABI version mismatch")
@@ -476,6 +503,7 @@ EXPORTED_SYMBOLS = ["aqc_abi_version", "aqc_device_count", "aqc_device_index", "
                     "aqc_source_open", "aqc_source_open2", "aqc_source_read", "aqc_source_error", "aqc_source_gz_stats", "aqc_gz_input_stats", "aqc_bz2_input_stats", "aqc_source_close",
                     "aqc_gz_deflate_block", "aqc_gz_inflate_raw", "aqc_gz_crc32",
                     "aqc_set_quality_cut", "aqc_get_cut_stats", "aqc_cut_ms", "aqc_quality_cut_views",
+                    "aqc_set_adapter_trim", "aqc_get_adapter_stats", "aqc_adapter_ms", "aqc_adapter_views",
                     # the reference's own native seam (editdistance/_editdistance.h:16,23), same names and signatures
                     "edit_distance", "seek_overlap"]
 
@@ -546,6 +574,22 @@ class Engine:
         """device time of the cut pass of the slot's last run(); 0.0: it launched none"""
         ms = C.c_float(0)
         self._check(self.lib.aqc_cut_ms(self.h, slot, C.byref(ms)))
+        return float(ms.value)
+
+    def set_adapter_trim(self, adapter):
+        """adapter: an AdapterConfig, or None (off).  With both adapters empty nothing of the pass runs."""
+        self._check(self.lib.aqc_set_adapter_trim(self.h, C.byref(adapter) if adapter is not None else None))
+
+    def adapter_stats(self):
+        """reads of R1 the adapter made shorter, bases it removed from them, the same for R2"""
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.aqc_get_adapter_stats(self.h, _ptr(out)))
+        return out
+
+    def adapter_ms(self, slot):
+        """device time of the adapter pass of the slot's last run(); 0.0: it launched none"""
+        ms = C.c_float(0)
+        self._check(self.lib.aqc_adapter_ms(self.h, slot, C.byref(ms)))
         return float(ms.value)
 
     def upload(self, slot, batch):
@@ -749,6 +793,19 @@ class Engine:
         v = np.zeros(batch.n, dtype=np.uint32)
         s = batch.as_struct()
         self._check(self.lib.aqc_quality_cut_views(self.h, C.byref(s), C.byref(cut), int(trim_front), int(trim_tail), _ptr(v)))
+        return (v & 0xffff).astype(np.int64), (v >> 16).astype(np.int64)
+
+    def adapter_views(self, batch, adapter, trim_front=0, trim_tail=0, view_in=None):
+        """the adapter pass alone on read 1 of the batch -> (c0, c1) arrays; view_in: (c0, c1) arrays of the views the reads come
+        with (a quality cut's), None: everything"""
+        v = np.zeros(batch.n, dtype=np.uint32)
+        vin = None
+        if view_in is not None:
+            vin = (np.asarray(view_in[0], dtype=np.uint32) | (np.asarray(view_in[1], dtype=np.uint32) << 16)).astype(np.uint32)
+            assert vin.shape == (batch.n,)
+        s = batch.as_struct()
+        self._check(self.lib.aqc_adapter_views(self.h, C.byref(s), C.byref(adapter), int(trim_front), int(trim_tail),
+                                               _ptr(vin) if vin is not None else None, _ptr(v)))
         return (v & 0xffff).astype(np.int64), (v >> 16).astype(np.int64)
 
     def edit_distance(self, batch):
@@ -1021,6 +1078,9 @@ class MergedEngines:
 
     def cut_stats(self):
         return sum(e.cut_stats() for e in self.engines)
+
+    def adapter_stats(self):
+        return sum(e.adapter_stats() for e in self.engines)
 
     def histograms(self, n=AQC_QC_COLS):
         hs = [e.histograms(n) for e in self.engines]

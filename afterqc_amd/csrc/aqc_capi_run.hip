@@ -14,6 +14,7 @@
 //   aqc_record.hpp   filter_overlap_kernel, filter_overlap_list_kernel, filter_overlap_cut_kernel<LIST>
 //   aqc_fast.hpp     fast_filter_overlap_kernel<NW, PAIRED, WPBT, BARCODE, FUSE, CUT> (a template: the variants are instantiated here)
 //   aqc_qcut.hpp     quality_cut_kernel<G> (the quality cut's pass in front of the verdict kernel, and its function seam)
+//   aqc_adapter.hpp  adapter_cut_kernel<G> (the adapter pass behind it, a second producer of the same views, and its function seam)
 //   aqc_gzdev.hpp    gz_hist_kernel, gz_encode_wave_kernel, gz_encode_kernel, gz_offsets_kernel, gz_pack_kernel
 //   aqc_gzlz.hpp     gz_hist_lz_kernel, gz_encode_lz_kernel (levels 6 - 9)
 //   aqc_seams.hpp    overlap_seam_kernel, read_stats_seam_kernel, edit_distance_seam_kernel, edit_distance_any_kernel,
@@ -37,6 +38,9 @@
 #include <zlib.h>
 
 using namespace aqc;
+
+// a pass in front of the verdict kernel leaves a view per mate and record: the quality cut, the adapter pass, or both
+static bool views_on(const aqc_ctx* c) { return qcut_on(c->cut) || adp_on(c->adapter); }
 
 constexpr int FUSE_WPBT = 12;      // waves per workgroup of the fused verdict kernel
 // waves per workgroup of the 20-word tier's paired instances: 10 or 11 fit the CU's 160 KiB of LDS (144,048 / 157,568 bytes).  11 by
@@ -78,7 +82,7 @@ static void launch_fast(aqc_ctx* c, Slot* s, const aqc_config& cfg, const DevSta
 // one tier of the lane-per-pair kernel (NW words per read; waves per workgroup for pairs / single reads): paired x barcode
 template <int NW, int WPBT_PAIRED, int WPBT_SINGLE>
 static void launch_fast_tier(aqc_ctx* c, Slot* s, const aqc_config& cfg, const DevStats& st, uint64_t accum_limit) {
-    if (qcut_on(c->cut)) {      // (never with a barcode: aqc_run refuses that)
+    if (views_on(c)) {      // (never with a barcode: aqc_run refuses that)
         if (cfg.paired) launch_fast<NW, true, WPBT_PAIRED, false, false, true>(c, s, cfg, st, accum_limit);
         else launch_fast<NW, false, WPBT_SINGLE, false, false, true>(c, s, cfg, st, accum_limit);
         return;
@@ -243,8 +247,8 @@ static Verdict choose_verdict_kernel(const aqc_ctx* c, const Slot& s, const aqc_
     // AQC_FUSED=1: pairs of device-framed text whose records are plain four-line text are placed in their output
     // streams by the verdict kernel itself, which also copies the good records that go out as their own bytes
     // (31-bit stream offsets; a bad record grows by its flag text)
-    // (not with the quality cut on: its instances are the plain tiers)
-    if (c->fuse_opt && !qcut_on(c->cut) && s.framed && cfg.paired && !cfg.barcode && s.max_len <= 160 && !s.has_irregular && s.m[0].consumed + 16 * s.n < (1ull << 31) &&
+    // (not with the quality cut or an adapter on: their instances are the plain tiers)
+    if (c->fuse_opt && !views_on(c) && s.framed && cfg.paired && !cfg.barcode && s.max_len <= 160 && !s.has_irregular && s.m[0].consumed + 16 * s.n < (1ull << 31) &&
         s.m[1].consumed + 16 * s.n < (1ull << 31))
         return Verdict::FUSED;
     // (TIER18, 257 .. 288 bases: 2x250 reads that still carry a barcode + verify prefix (BASELINE config 5: 267 bases))
@@ -269,15 +273,20 @@ static int prepare_fuse(Slot& s, FuseArgs& fz) {
     return 0;
 }
 
+// lanes per read of the passes in front of the verdict kernel, by the slot's longest line: a quality line of its own length (or a
+// length nobody has looked at) may be anything up to AQC_MAX_READ_LEN
+static int view_pass_lanes(const Slot& s) {
+    const uint32_t longest = (s.has_irregular || s.raw_max_len == 0) ? (uint32_t)AQC_MAX_READ_LEN : s.raw_max_len;
+    return longest <= 128 ? 8 : longest <= 256 ? 16 : longest <= 512 ? 32 : 64;
+}
+
 // ---- the quality cut's pass (aqc_qcut.hpp): one view per mate and record into `view` (n_mates per record), the four counts into `stats` (may be NULL)
 static int launch_cut(aqc_ctx* c, Slot& s, const QcutOpts& o, const int32_t trim_front[2], const int32_t trim_tail[2], int n_mates, uint32_t* view,
                       unsigned long long* stats, uint64_t accum_limit) {
     QcutArgs A{};
     A.b = s.view; A.o = o; A.n_mates = n_mates; A.view = view; A.stats = stats; A.accum_limit = accum_limit; A.status = s.status;
     for (int k = 0; k < 2; ++k) { A.trim_front[k] = trim_front[k]; A.trim_tail[k] = trim_tail[k]; }
-    // lanes per read by the longest quality line: a line of its own length (or a length nobody has looked at) may be anything up to AQC_MAX_READ_LEN
-    const uint32_t longest = (s.has_irregular || s.raw_max_len == 0) ? (uint32_t)AQC_MAX_READ_LEN : s.raw_max_len;
-    const int G = longest <= 128 ? 8 : longest <= 256 ? 16 : longest <= 512 ? 32 : 64;
+    const int G = view_pass_lanes(s);
     uint64_t blocks = (s.n + (QCUT_THREADS / G) - 1) / (QCUT_THREADS / G);
     const uint64_t cap = (uint64_t)c->n_cu * 16;
     if (blocks > cap) blocks = cap;
@@ -305,24 +314,70 @@ static int run_cut(aqc_ctx* c, Slot& s, const aqc_config& cfg, uint64_t accum_li
     return 0;
 }
 
+// ---- the adapter pass (aqc_adapter.hpp): the view each mate leaves it with into `view`; view_in: the views they come with (may be `view`; NULL: everything)
+static int launch_adapter(aqc_ctx* c, Slot& s, const AdapterOpts& a, const int32_t trim_front[2], const int32_t trim_tail[2], int n_mates,
+                          const uint32_t* view_in, uint32_t* view, unsigned long long* stats, uint64_t accum_limit) {
+    AdapterArgs A{};
+    A.n = s.view.n; A.min_overlap = a.min_overlap; A.n_mates = n_mates; A.view_in = view_in; A.view = view; A.stats = stats; A.accum_limit = accum_limit; A.status = s.status;
+    for (int k = 0; k < n_mates; ++k) {
+        AdapterMate& M = A.m[k];
+        M.seq = k ? s.view.seq2 : s.view.seq1; M.off = k ? s.view.off2 : s.view.off1; M.len = k ? s.view.len2 : s.view.len1;
+        M.trim_front = trim_front[k]; M.trim_tail = trim_tail[k]; M.alen = a.len[k];
+        for (int j = 0; j < ADP_WORDS; ++j) M.w[j] = a.w[k][j];
+    }
+    const int G = view_pass_lanes(s);
+    uint64_t blocks = (s.n + (ADP_THREADS / G) - 1) / (ADP_THREADS / G);
+    const uint64_t cap = (uint64_t)c->n_cu * 16;
+    if (blocks > cap) blocks = cap;
+    const dim3 grid((unsigned)blocks), block(ADP_THREADS);
+    if (G == 8) hipLaunchKernelGGL(adapter_cut_kernel<8>, grid, block, 0, s.stream, A);
+    else if (G == 16) hipLaunchKernelGGL(adapter_cut_kernel<16>, grid, block, 0, s.stream, A);
+    else if (G == 32) hipLaunchKernelGGL(adapter_cut_kernel<32>, grid, block, 0, s.stream, A);
+    else hipLaunchKernelGGL(adapter_cut_kernel<64>, grid, block, 0, s.stream, A);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the adapter pass of an aqc_run, behind the cut pass: it updates the cut's views in place, or fills the array itself
+static int run_adapter(aqc_ctx* c, Slot& s, const aqc_config& cfg, uint64_t accum_limit) {
+    const int nm = cfg.paired ? 2 : 1;
+    if (s.cut.reserve(sizeof(uint32_t) * s.n * nm)) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    for (hipEvent_t& e : s.adapter_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    const int32_t tf[2] = {cfg.trim_front, cfg.trim_front2}, tt[2] = {cfg.trim_tail, cfg.trim_tail2};
+    AdapterOpts a = c->adapter;
+    if (nm == 1) a.len[1] = 0;
+    HIP_TRY(hipEventRecord(s.adapter_ev[0], s.stream));
+    const int rc = launch_adapter(c, s, a, tf, tt, nm, s.cut_ran ? (const uint32_t*)s.cut.p : nullptr, (uint32_t*)s.cut.p, c->adapter_stats, accum_limit);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(s.adapter_ev[1], s.stream));
+    s.adapter_ran = true;
+    return 0;
+}
+
 int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
     GET_SLOT(s);
     if (!c->has_cfg) return fail(AQC_ERR_STATE, "aqc_run before aqc_set_config");
     if (c->cfg.paired && !s->paired) return fail(AQC_ERR_STATE, "config says paired but the slot holds single-end records");
     if (c->cfg.debubble && c->circles.n > 0 && !s->view.aux_ok) return fail(AQC_ERR_ARG, "debubble needs the aux_* arrays");
-    const bool cut = qcut_on(c->cut);
-    if (cut && c->cfg.barcode) return fail(AQC_ERR_UNSUPPORTED, "aqc_run: the quality cut together with a barcode is not implemented");
+    const bool cut = views_on(c);           // the verdict kernels take views: the CUT instances
+    if (cut && c->cfg.barcode) return fail(AQC_ERR_UNSUPPORTED, "aqc_run: the quality cut or an adapter together with a barcode is not implemented");
     s->fused = false;
     s->verdict_words = 0;
     s->cut_ran = false;
+    s->adapter_ran = false;
     if (s->n == 0) { s->ran = true; return 0; }
     aqc_config cfg = c->cfg;
     if (!cfg.paired) cfg.no_overlap = 1;
     DevStats st{c->counters, c->ovl_hist, c->dist_hist, s->status, err_key_of(*s)};
     s->err_record = UINT64_MAX;
     if (s->qc.pending()) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_qc, 0));      // (statRead of the previous run still reads the results)
-    if (cut) {
+    if (qcut_on(c->cut)) {
         const int rc = run_cut(c, *s, cfg, accum_limit);
+        if (rc) return rc;
+    }
+    if (adp_on(c->adapter)) {
+        const int rc = run_adapter(c, *s, cfg, accum_limit);
         if (rc) return rc;
     }
     HIP_TRY(hipEventRecord(launch_event(*s, AQC_K_FILTER_OVERLAP, 0), s->stream));
@@ -394,6 +449,16 @@ int aqc_cut_ms(aqc_ctx* c, int slot, float* ms) {
     if (!s->cut_ran) return 0;
     HIP_TRY(slot_sync(*s));
     HIP_TRY(hipEventElapsedTime(ms, s->cut_ev[0], s->cut_ev[1]));
+    return 0;
+}
+
+int aqc_adapter_ms(aqc_ctx* c, int slot, float* ms) {
+    GET_SLOT(s);
+    if (!ms) return fail(AQC_ERR_ARG, "aqc_adapter_ms: null argument");
+    *ms = 0.f;
+    if (!s->adapter_ran) return 0;
+    HIP_TRY(slot_sync(*s));
+    HIP_TRY(hipEventElapsedTime(ms, s->adapter_ev[0], s->adapter_ev[1]));
     return 0;
 }
 
@@ -601,6 +666,28 @@ int aqc_quality_cut_views(aqc_ctx* c, const aqc_batch* b, const aqc_cut_config* 
     if (out.reserve(4 * n)) return fail(AQC_ERR_HIP, "hipMalloc failed");
     const int32_t tf[2] = {trim_front, 0}, tt[2] = {trim_tail, 0};
     if ((rc = launch_cut(c, *s, o, tf, tt, 1, (uint32_t*)out.p, nullptr, UINT64_MAX))) return rc;
+    if ((rc = seam_out(s, out, view, n))) return rc;
+    HIP_TRY(slot_sync(*s));
+    return check_status(*s);
+}
+
+int aqc_adapter_views(aqc_ctx* c, const aqc_batch* b, const aqc_adapter_config* adapter, int32_t trim_front, int32_t trim_tail, const uint32_t* view_in,
+                      uint32_t* view) {
+    if (!adapter || !view) return fail(AQC_ERR_ARG, "aqc_adapter_views: null argument");
+    AdapterOpts a{};
+    if (!adp_from_config(adapter, a) || trim_front < 0 || trim_tail < 0) return fail(AQC_ERR_ARG, "aqc_adapter_views: adapter / min overlap / trim out of range");
+    a.len[1] = 0;
+    Slot* s;
+    // (the search reads sequence lines only; a batch that brings quality lines is taken as aqc_run takes it, LEN_IRR marks included)
+    int rc = seam_prepare(c, b, b && b->qual1 != nullptr, false, &s);
+    if (rc) return rc;
+    const uint64_t n = b->n;
+    if (n == 0) return 0;
+    DevBuf out;
+    if (out.reserve(4 * n)) return fail(AQC_ERR_HIP, "hipMalloc failed");
+    if (view_in) HIP_TRY(hipMemcpyAsync(out.p, view_in, 4 * n, hipMemcpyHostToDevice, s->stream));
+    const int32_t tf[2] = {trim_front, 0}, tt[2] = {trim_tail, 0};
+    if ((rc = launch_adapter(c, *s, a, tf, tt, 1, view_in ? (const uint32_t*)out.p : nullptr, (uint32_t*)out.p, nullptr, UINT64_MAX))) return rc;
     if ((rc = seam_out(s, out, view, n))) return rc;
     HIP_TRY(slot_sync(*s));
     return check_status(*s);

@@ -13,6 +13,7 @@
 #include "aqc_dev.hpp"
 #include "aqc_batch.hpp"
 #include "aqc_qcut.hpp"
+#include "aqc_adapter.hpp"
 
 namespace aqc {
 
@@ -79,6 +80,8 @@ struct __attribute__((visibility("hidden"))) Slot {
     DevBuf cut;                                  // the quality cut's views (aqc_qcut.hpp: one per mate and record), filled by aqc_run in front of the verdict kernel
     hipEvent_t cut_ev[2] = {nullptr, nullptr};   // around the cut pass of the last aqc_run (aqc_cut_ms) ...
     bool cut_ran = false;                        // ... if it launched one
+    hipEvent_t adapter_ev[2] = {nullptr, nullptr};   // the same for the adapter pass (aqc_adapter.hpp, aqc_adapter_ms): it writes its views into `cut` too
+    bool adapter_ran = false;
     // AQC_FUSED=1: the verdict kernel placed the slot's records in their streams and copied the whole good ones (aqc_fast.hpp, FUSE)
     DevBuf fz_state, fz_misc;                 // look-back words per batch (Mate::fz_rec: position words per record); ticket | abort | totals[4]
     bool fused = false;                       // ... for the records the slot holds now (aqc_format checks fz_misc's abort word)
@@ -131,6 +134,8 @@ struct __attribute__((visibility("hidden"))) aqc_ctx {
     bool has_cfg = false;
     aqc::QcutOpts cut{};               // aqc_set_quality_cut: the quality cut (all modes 0: off, no kernel of it is launched)
     unsigned long long* cut_stats = nullptr;   // [4] reads of R1 the cut made shorter, bases it took from them, the same for R2
+    aqc::AdapterOpts adapter{};        // aqc_set_adapter_trim: the adapters to trim (both lengths 0: off, no kernel of it is launched)
+    unsigned long long* adapter_stats = nullptr;   // [4] the same counts for the adapter pass
     aqc::DevBuf circ[5];
     aqc::DevBuf kmer_partial;          // per-round u16 count slices of kmer_count_kernel
     aqc::DevBuf gz_crc;                // GzCrcTables (aqc_compress)

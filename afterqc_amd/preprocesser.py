@@ -116,6 +116,27 @@ def set_cut(engine, cut):
     engine.set_quality_cut(cut)
 
 
+def adapter_config(opt):
+    """--adapter_sequence / --adapter_sequence_r2 / --adapter_min_overlap as the engine takes them; None: no adapter is given
+    (options objects built without the adapter options count as off).  Single-end input has no read 2 to search."""
+    a1 = getattr(opt, "adapter_sequence", None) or ""
+    a2 = getattr(opt, "adapter_sequence_r2", None) or ""
+    if getattr(opt, "read2_file", None) is None:
+        a2 = ""
+    if not a1 and not a2:
+        return None
+    return capi.AdapterConfig(a1, a2, int(getattr(opt, "adapter_min_overlap", 4)))
+
+
+def set_adapter(engine, adapter):
+    """the adapters on an engine — only ever called with one given: an engine that cannot trim adapters is an error, never a run
+    without the option"""
+    if not hasattr(engine, "set_adapter_trim"):
+        raise RuntimeError("afterqc_amd: --adapter_sequence / --adapter_sequence_r2 need an engine with set_adapter_trim; %s has none"
+                           % type(engine).__name__)
+    engine.set_adapter_trim(adapter)
+
+
 def build_config(opt, paired, has_index2):
     cfg = capi.Config()
     cfg.paired = 1 if paired else 0
@@ -420,6 +441,7 @@ class seqFilter:
         self.bubbleCircles = []
         self.stat = None
         self.cut = cut_config(opt)
+        self.adapter = adapter_config(opt)
 
     # ---- helpers ---------------------------------------------------------------------------------
     def _engine(self):
@@ -441,6 +463,8 @@ class seqFilter:
                 e.set_circles(circles)
                 if self.cut is not None:
                     set_cut(e, self.cut)
+                if self.adapter is not None:
+                    set_adapter(e, self.adapter)
                 e.reset_stats()
                 self.extra_engines.append(e)
         return [eng] + self.extra_engines
@@ -461,6 +485,13 @@ class seqFilter:
             # (the barcode stage moves the view before the trim stage: that combination is not implemented; refused before anything is created)
             raise SystemExit("afterqc_amd: --cut_front / --cut_tail / --cut_right are not implemented for barcoded input "
                              "(%s); run it with --barcode off or without the cut" % opt.read1_file)
+        if self.adapter is None and getattr(opt, "adapter_sequence_r2", None) and not self.paired:
+            # (never a silent run without the option: only read 2's adapter is given and this input has no read 2)
+            raise SystemExit("afterqc_amd: --adapter_sequence_r2 is given alone but %s is single-end: there is no read 2 to search; "
+                             "give the adapter as --adapter_sequence" % opt.read1_file)
+        if opt.barcode and self.adapter is not None:
+            raise SystemExit("afterqc_amd: --adapter_sequence / --adapter_sequence_r2 are not implemented for barcoded input "
+                             "(%s); run it with --barcode off or without the adapter" % opt.read1_file)
         t_init = time.perf_counter()
         eng = self._engine()
         self.timing = {"init_s": time.perf_counter() - t_init}       # (a fresh process: HIP runtime start + the library's code object)
@@ -507,6 +538,10 @@ class seqFilter:
                 set_cut(e, self.cut)
             elif hasattr(e, "set_quality_cut"):
                 e.set_quality_cut(None)          # (an engine the caller handed over may come from a run that had the cut on)
+            if self.adapter is not None:
+                set_adapter(e, self.adapter)
+            elif hasattr(e, "set_adapter_trim"):
+                e.set_adapter_trim(None)
             if first:
                 e.set_circles(self.bubbleCircles)
                 e.reset_stats()
@@ -1016,5 +1051,12 @@ class seqFilter:
                 'cut_front': bool(self.cut.front), 'cut_tail': bool(self.cut.tail), 'cut_right': bool(self.cut.right),
                 'cut_window_size': int(self.cut.window), 'cut_mean_quality': int(self.cut.mean_quality),
                 'read1_cut_reads': n[0], 'read1_cut_bases': n[1], 'read2_cut_reads': n[2], 'read2_cut_bases': n[3],
+            }
+        if self.adapter is not None:
+            n = [int(v) for v in eng.adapter_stats()]
+            a1, a2 = self.adapter.adapters()
+            stat["adapter_trim"] = {
+                'adapter_sequence': a1.decode(), 'adapter_sequence_r2': a2.decode(), 'adapter_min_overlap': int(self.adapter.min_overlap),
+                'read1_trimmed_reads': n[0], 'read1_trimmed_bases': n[1], 'read2_trimmed_reads': n[2], 'read2_trimmed_bases': n[3],
             }
         return stat

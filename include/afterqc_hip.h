@@ -245,6 +245,24 @@ int aqc_get_cut_stats(aqc_ctx* ctx, int64_t out[4]);
 /* device time of the cut pass of the slot's last aqc_run (HIP events on the slot's stream); 0: it launched none */
 int aqc_cut_ms(aqc_ctx* ctx, int slot, float* ms);
 
+/* ---- trimming a given adapter from each read (--adapter_sequence / --adapter_sequence_r2) ------ */
+/* Inside the same trim stage, behind the fixed trim and behind the quality cut: let s be the part of a mate's SEQUENCE line that
+ * those two keep, n its length, A the mate's adapter of m bases.  At a place p the k = min(m, n - p) bases the read still has are
+ * compared with A's first k, byte for byte (an N or a lower-case base is a mismatch); p matches when at most k >> 3 differ.  The
+ * smallest matching p of 0 .. n - min_overlap ends the mate there; sequence and quality line are each sliced by their own length.
+ * The stage's `< 5` tests then run as they stand.  len 0: that mate is not searched; otherwise 4 .. 64 letters of A C G T;
+ * 1 <= min_overlap <= the shorter given adapter. */
+typedef struct aqc_adapter_config { int32_t len1, len2, min_overlap; uint8_t seq1[64], seq2[64]; } aqc_adapter_config;
+/* NULL or both lengths 0: off — no kernel of the pass is launched and aqc_run is what it is without it.  A bad length, letter or
+ * min_overlap: AQC_ERR_ARG.  With an adapter on, aqc_run of a configuration that has `barcode` set returns AQC_ERR_UNSUPPORTED. */
+int aqc_set_adapter_trim(aqc_ctx* ctx, const aqc_adapter_config* adapter);
+/* out[0..3]: reads of R1 the adapter made shorter, bases it removed from them (on the sequence line, beyond what trim and quality
+ * cut took), the same for R2.  Records below accum_limit only; R2 is counted only where read 1 leaves the stage with 5 bases or
+ * more.  Zeroed by aqc_reset_stats; contexts add up. */
+int aqc_get_adapter_stats(aqc_ctx* ctx, int64_t out[4]);
+/* device time of the adapter pass of the slot's last aqc_run (HIP events on the slot's stream); 0: it launched none */
+int aqc_adapter_ms(aqc_ctx* ctx, int slot, float* ms);
+
 /* ---- the hot path: preprocesser.py:411-631 over a batch --------------------------------------- */
 /* copy a batch into slot `slot` (async on the slot's stream; see the note on host buffers above) */
 int aqc_upload(aqc_ctx* ctx, int slot, const aqc_batch* batch);
@@ -502,6 +520,11 @@ int aqc_edit_distance(aqc_ctx* ctx, const aqc_batch* pairs, int32_t* dist);
 /* the cut pass alone: for every read of the batch (seq1 / qual1, qlen1 honoured) the part of its TRIMMED quality line that the cut
  * keeps, view[i] = c0 | c1 << 16 (trim() by trim_front / trim_tail first; no mode set: 0 | n << 16) */
 int aqc_quality_cut_views(aqc_ctx* ctx, const aqc_batch* reads, const aqc_cut_config* cut, int32_t trim_front, int32_t trim_tail, uint32_t* view);
+/* the adapter pass alone: for every read of the batch (seq1; adapter seq1 / len1 of the config) the view it leaves the pass with,
+ * view[i] = c0 | c1 << 16 relative to the TRIMMED lines.  view_in: the view each read comes with (a quality cut's), NULL: 0 | 0xffff << 16,
+ * "everything"; a read without a match keeps the view it came with */
+int aqc_adapter_views(aqc_ctx* ctx, const aqc_batch* reads, const aqc_adapter_config* adapter, int32_t trim_front, int32_t trim_tail,
+                      const uint32_t* view_in /* may be NULL */, uint32_t* view);
 
 /* ---- whole-input pipeline: the byte path of seqFilter.run's main loop (preprocesser.py:411-631) --------------------- */
 /* Reads one input (a read file, or a pair of mate files; plain, .gz, or text already in host memory), cuts it into chunks

@@ -12,6 +12,7 @@ pre-filter sampling pass, of pass 2 (read -> filter -> write) and of the whole r
 import argparse
 import json
 import os
+import shlex
 import shutil
 import sys
 import time
@@ -39,6 +40,7 @@ def main():
                     "writer's format; member-parallel inflate)")
     ap.add_argument("--bz2", action="store_true", help="bzip2 inputs (fastq.py:25-26): plain text first, then the bzip2 program; outputs are plain text")
     ap.add_argument("--config5", action="store_true", help="config-5 flavour: 2x250 bp + 17 bp barcode/verify prefix, file names with 'barcode', --debubble with a circles.csv")
+    ap.add_argument("--extra", default="", help="further options of the CLI, appended as they are, e.g. '--adapter_sequence AGATCGGAAGAGCACACGTCTGAACTCCAGTCA'")
     args = ap.parse_args()
     from afterqc_amd import after, preprocesser, synth
     os.makedirs(args.dir, exist_ok=True)
@@ -91,6 +93,7 @@ def main():
                                                               "-b", os.path.join(args.dir, "bad"), "-r", os.path.join(args.dir, "QC")]
     if args.config5:
         argv += ["--debubble", "--debubble_dir", os.path.join(args.dir, "D")]
+    argv += shlex.split(args.extra)
     options, _ = after.parseCommand(argv)
     after.finalize_options(options)
     options.barcode = bool(args.config5)       # what after.py:215-221 decides from the file name
@@ -111,7 +114,7 @@ def main():
            "init_s": round(flt.timing.get("init_s", 0), 3), "stats_s": round(flt.timing.get("stats_s", 0), 3), "report_s": round(flt.timing.get("report_s", 0), 3),
            "close_s": round(flt.timing.get("close_s", 0), 3),
            "good_reads": s["good_reads"], "bad_reads": s["bad_reads"], "text_path": flt.text_path, "used_pipe": flt.used_pipe,
-           "config5": args.config5, "devices": args.devices, "pipe_threads": flt.timing.get("pipe_threads")}
+           "config5": args.config5, "extra": args.extra, "devices": args.devices, "pipe_threads": flt.timing.get("pipe_threads")}
     print(json.dumps(out))
     if not args.keep:
         shutil.rmtree(args.dir, ignore_errors=True)
