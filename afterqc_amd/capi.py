@@ -560,21 +560,27 @@ class Engine:
     def reset_stats(self):
         self._check(self.lib.aqc_reset_stats(self.h))
 
+    def _four_counts(self, getter):
+        out = np.zeros(4, dtype=np.int64)
+        self._check(getter(self.h, _ptr(out)))
+        return out
+
+    def _pass_ms(self, getter, slot):
+        ms = C.c_float(0)
+        self._check(getter(self.h, slot, C.byref(ms)))
+        return float(ms.value)
+
     def set_quality_cut(self, cut):
         """cut: a CutConfig, or None (off).  With no mode set nothing of the cut runs."""
         self._check(self.lib.aqc_set_quality_cut(self.h, C.byref(cut) if cut is not None else None))
 
     def cut_stats(self):
         """reads of R1 the cut made shorter, bases it removed from them, the same for R2"""
-        out = np.zeros(4, dtype=np.int64)
-        self._check(self.lib.aqc_get_cut_stats(self.h, _ptr(out)))
-        return out
+        return self._four_counts(self.lib.aqc_get_cut_stats)
 
     def cut_ms(self, slot):
         """device time of the cut pass of the slot's last run(); 0.0: it launched none"""
-        ms = C.c_float(0)
-        self._check(self.lib.aqc_cut_ms(self.h, slot, C.byref(ms)))
-        return float(ms.value)
+        return self._pass_ms(self.lib.aqc_cut_ms, slot)
 
     def set_adapter_trim(self, adapter):
         """adapter: an AdapterConfig, or None (off).  With both adapters empty nothing of the pass runs."""
@@ -582,15 +588,11 @@ class Engine:
 
     def adapter_stats(self):
         """reads of R1 the adapter made shorter, bases it removed from them, the same for R2"""
-        out = np.zeros(4, dtype=np.int64)
-        self._check(self.lib.aqc_get_adapter_stats(self.h, _ptr(out)))
-        return out
+        return self._four_counts(self.lib.aqc_get_adapter_stats)
 
     def adapter_ms(self, slot):
         """device time of the adapter pass of the slot's last run(); 0.0: it launched none"""
-        ms = C.c_float(0)
-        self._check(self.lib.aqc_adapter_ms(self.h, slot, C.byref(ms)))
-        return float(ms.value)
+        return self._pass_ms(self.lib.aqc_adapter_ms, slot)
 
     def upload(self, slot, batch):
         s = batch.as_struct()

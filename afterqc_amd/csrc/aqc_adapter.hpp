@@ -4,12 +4,12 @@
 // has are compared with the adapter's first k, p matches when at most k >> 3 of them differ, the smallest p wins; a match at the
 // read's tail needs at least K bases of the adapter on the read (p <= n - K).
 //
-//   groups   as in quality_cut_kernel (aqc_qcut.hpp): G neighbouring lanes (8, 16, 32 or 64, by the slot's longest read) own one
-//            read, a workgroup of four waves owns 256 / G consecutive records and takes read 1, then read 2 of each.
-//   load     one 16-byte load per lane, at the sequence line's own alignment (the arenas are padded: aqc_batch), into the LDS row of
-//            the group; the bytes behind the line, and the 80 bytes behind the row that a comparison at the tail reaches, are 0 —
-//            no base.  The length comes from the length word (its LEN_IRR mark taken off: no address is formed with it), the
-//            part [c0, c1) of the trimmed line from the quality cut's view when a cut is on.
+// The frame — lanes per read, the 16-byte load, the view word, the counts — is that of every view pass: aqc_viewpass.hpp.  Here:
+//
+//   line     the sequence line, its 16 bytes per lane stored into the LDS row of the group; the bytes behind the line, and the 80
+//            bytes behind the row that a comparison at the tail reaches, are 0 — no base.  The length comes from the length word
+//            (its LEN_IRR mark taken off: no address is formed with it), the part [c0, c1) of the trimmed line from the view that
+//            comes in — the quality cut's when a cut is on, else VIEW_ALL.
 //   adapter  both adapters travel in the kernel's by-value arguments, 16 dwords each.  The mate in turn has its 16 dwords in scalar
 //            registers, fetched from the argument segment by one s_load_dwordx16 per mate and round: with both mates' 32 dwords
 //            live at once the kernel spills 56 scalar registers.  There is no table in device memory.
@@ -24,13 +24,12 @@
 #pragma once
 #include <stdint.h>
 
-#include "aqc_qcut.hpp"
+#include "aqc_viewpass.hpp"
 
 namespace aqc {
 
 constexpr int ADP_NONE = 0x7fffffff;
 constexpr int ADP_MIN_LEN = 4, ADP_MAX_LEN = 64, ADP_WORDS = ADP_MAX_LEN / 4;
-constexpr uint32_t ADP_VIEW_ALL = 0xffff0000u;      // (0, 0xffff): the view of a mate nothing has cut
 // words behind the 16 * G bytes of a group's row: a lane at the row's last byte reads ADP_WORDS + 1 words from its word on
 // (the row stays a multiple of 16 bytes, and neighbouring rows start 20 banks apart)
 constexpr int ADP_ROW_TAIL = 20;
@@ -42,19 +41,19 @@ struct AdapterOpts {
     uint32_t w[2][ADP_WORDS];
 };
 
-QCUT_HD bool adp_on(const AdapterOpts& a) { return a.len[0] > 0 || a.len[1] > 0; }
-QCUT_HD bool adp_opts_ok(const AdapterOpts& a) {
+VP_HD bool adp_on(const AdapterOpts& a) { return a.len[0] > 0 || a.len[1] > 0; }
+VP_HD bool adp_opts_ok(const AdapterOpts& a) {
     int shortest = ADP_MAX_LEN;
     for (int k = 0; k < 2; ++k) {
         if (a.len[k] == 0) continue;
         if (a.len[k] < ADP_MIN_LEN || a.len[k] > ADP_MAX_LEN) return false;
-        shortest = qcut_min(shortest, a.len[k]);
+        shortest = vp_min(shortest, a.len[k]);
     }
     return !adp_on(a) || (a.min_overlap >= 1 && a.min_overlap <= shortest);
 }
 
 // how many of the four bytes of x are not zero
-QCUT_HD int adp_mismatch4(uint32_t x) {
+VP_HD int adp_mismatch4(uint32_t x) {
     const uint32_t nz = (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
 #if defined(__HIP_DEVICE_COMPILE__)
     return __popc(nz);
@@ -64,10 +63,10 @@ QCUT_HD int adp_mismatch4(uint32_t x) {
 }
 
 // the bytes of a dword that are still compared when `left` bytes of the comparison remain at its first byte
-QCUT_HD uint32_t adp_tail_mask(int left) { return left >= 4 ? 0xffffffffu : left <= 0 ? 0u : (1u << (8 * left)) - 1u; }
+VP_HD uint32_t adp_tail_mask(int left) { return left >= 4 ? 0xffffffffu : left <= 0 ? 0u : (1u << (8 * left)) - 1u; }
 
 // the four bytes that start `sh` (0 .. 3) bytes into the little-endian word pair lo, hi
-QCUT_HD uint32_t adp_bytes_at(uint32_t lo, uint32_t hi, int sh) {
+VP_HD uint32_t adp_bytes_at(uint32_t lo, uint32_t hi, int sh) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)sh);
 #else
@@ -76,36 +75,15 @@ QCUT_HD uint32_t adp_bytes_at(uint32_t lo, uint32_t hi, int sh) {
 }
 
 // a lane's 16 loaded bytes as they go into the row: the bytes from `nvalid` on are 0
-QCUT_HD void adp_keep16(uint32_t d[4], int nvalid) {
+VP_HD void adp_keep16(uint32_t d[4], int nvalid) {
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
     for (int j = 0; j < 4; ++j) d[j] &= adp_tail_mask(nvalid - 4 * j);
 }
 
-// true when the condition holds in any lane of the wave / of the lane's group of G (the self-test's single lane: in the lane)
-QCUT_HD bool adp_wave_any(bool c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __ballot(c) != 0ull;
-#else
-    return c;
-#endif
-}
-template <int G>
-QCUT_HD bool adp_group_any(bool c, int g) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const unsigned long long b = __ballot(c);
-    if (G == 64) return b != 0ull;
-    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    return ((b >> (lane - g)) & ((1ull << (G & 63)) - 1ull)) != 0ull;
-#else
-    (void)g;
-    return c;
-#endif
-}
-
 // the mismatches of the adapter's dword I against the read's four bytes at the comparison's byte 4 * I, of which k are compared in all
-QCUT_HD int adp_dword(uint32_t lo, uint32_t hi, int sh, uint32_t a, int k, int I) {
+VP_HD int adp_dword(uint32_t lo, uint32_t hi, int sh, uint32_t a, int k, int I) {
     return adp_mismatch4((adp_bytes_at(lo, hi, sh) ^ a) & adp_tail_mask(k - 4 * I));
 }
 
@@ -114,9 +92,9 @@ QCUT_HD int adp_dword(uint32_t lo, uint32_t hi, int sh, uint32_t a, int k, int I
 // its bytes are past k and masked out, and the row has the words.  (Written out step by step — a recursion the compiler flattens —
 // so that A[I] names one scalar register: a loop that leaves on a wave-wide test is not unrolled, and would fetch A[i] from memory.)
 template <int I>
-QCUT_HD void adp_walk(const uint32_t* wp, uint32_t lo, int sh, const uint32_t (&A)[ADP_WORDS], int nd, int k, int allow, int& mm) {
+VP_HD void adp_walk(const uint32_t* wp, uint32_t lo, int sh, const uint32_t (&A)[ADP_WORDS], int nd, int k, int allow, int& mm) {
     if constexpr (I < ADP_WORDS) {
-        if (I >= nd || !adp_wave_any(mm <= allow)) return;
+        if (I >= nd || !vp_wave_any(mm <= allow)) return;
         const uint32_t mid = wp[I + 1], hi = wp[I + 2];
         mm += adp_dword(lo, mid, sh, A[I], k, I) + adp_dword(mid, hi, sh, A[I + 1], k, I + 1);
         adp_walk<I + 2>(wp, hi, sh, A, nd, k, allow, mm);
@@ -126,36 +104,37 @@ QCUT_HD void adp_walk(const uint32_t* wp, uint32_t lo, int sh, const uint32_t (&
 // Lane g of a group of G lanes: the first p = j * G + g at which the adapter A (m bytes) matches the read of n bytes that stands
 // in `row` (zero bytes behind it, ADP_ROW_TAIL words behind 16 * G bytes); ADP_NONE: nowhere.  Every lane of the wave runs it.
 template <int G>
-QCUT_HD int adp_lane_first(const uint32_t* row, int n, const uint32_t (&A)[ADP_WORDS], int m, int K, int g) {
+VP_HD int adp_lane_first(const uint32_t* row, int n, const uint32_t (&A)[ADP_WORDS], int m, int K, int g) {
     const int last = n - K;                          // the last place a match may start
     const int nd = (m + 3) >> 2;
     int best = ADP_NONE;
     bool open = true;                                // the lane's group has no match yet
-    for (int p0 = 0; adp_wave_any(open && p0 <= last); p0 += G) {
+    for (int p0 = 0; vp_wave_any(open && p0 <= last); p0 += G) {
         const int p = p0 + g;
         const bool active = open && p <= last;
         const int pp = active ? p : 0;               // (a lane with nothing to test reads the row's start)
-        const int k = qcut_min(m, n - pp), allow = k >> 3, sh = pp & 3;
+        const int k = vp_min(m, n - pp), allow = k >> 3, sh = pp & 3;
         const uint32_t* const wp = row + (pp >> 2);
         int mm = active ? 0 : (1 << 20);
         adp_walk<0>(wp, wp[0], sh, A, nd, k, allow, mm);
         const bool hit = active && mm <= allow;
         if (hit) best = p;
-        open = open && !adp_group_any<G>(hit, g);
+        open = open && !vp_group_any<G>(hit, g);
     }
     return best;
 }
 
 // the view a mate leaves the pass with: the one it came with, ended at its first match
-QCUT_HD uint32_t adp_view(uint32_t view_in, int p) {
+VP_HD uint32_t adp_view(uint32_t view_in, int p) {
     if (p == ADP_NONE) return view_in;
-    const uint32_t c0 = view_in & 0xffffu;
-    return c0 | ((c0 + (uint32_t)p) << 16);
+    const int c0 = view_c0(view_in);
+    return view_word(c0, c0 + p);
 }
 
 }  // namespace aqc
 
 #if defined(__HIPCC__)
+#include "aqc_batch.hpp"
 
 namespace aqc {
 
@@ -181,8 +160,6 @@ struct AdapterArgs {
     int* status;
 };
 
-constexpr int ADP_THREADS = QCUT_THREADS;
-
 static_assert(sizeof(((aqc_adapter_config*)nullptr)->seq1) == ADP_MAX_LEN, "an adapter of the C API fills the kernel's 16 dwords");
 
 // the C API's adapters as the kernel takes them (NULL: off); false: a bad length, a letter that is no base, a bad min_overlap
@@ -202,10 +179,9 @@ inline bool adp_from_config(const aqc_adapter_config* cfg, AdapterOpts& a) {
 }
 
 template <int G>
-__global__ __launch_bounds__(ADP_THREADS) void adapter_cut_kernel(AdapterArgs K) {
+__global__ __launch_bounds__(VP_THREADS) void adapter_cut_kernel(AdapterArgs K) {
     static_assert(G == 8 || G == 16 || G == 32 || G == 64, "a group is a power-of-two part of a wave");
-    constexpr int CAP = 16 * G;                     // longest read a group takes
-    constexpr int GROUPS = ADP_THREADS / G;         // records per workgroup and round
+    constexpr int CAP = vp_cap(G), GROUPS = vp_groups(G);
     constexpr int ROW = CAP / 4 + ADP_ROW_TAIL;     // words per group
     __shared__ __attribute__((aligned(16))) uint32_t lds[GROUPS * ROW];
     __shared__ unsigned long long tot[4];
@@ -226,49 +202,40 @@ __global__ __launch_bounds__(ADP_THREADS) void adapter_cut_kernel(AdapterArgs K)
             // ---- the read: where, how long behind trim() and the quality cut
             const AdapterMate& M = K.m[k];
             int L = have ? (int)(M.len[rec] & LEN_MASK) : 0;
-            const bool too_long = L > CAP || L > AQC_MAX_READ_LEN;
+            const bool too_long = vp_too_long<G>(L);
             if (!have || too_long) L = 0;
-            uint32_t vin = ADP_VIEW_ALL;
+            uint32_t vin = VIEW_ALL;
             const uint32_t vi = (uint32_t)rec * (uint32_t)nm + (uint32_t)k;       // (a slot holds fewer than 2^31 records)
             if (have && K.view_in) vin = K.view_in[vi];
             int t0, tl, s0, n;
-            qcut_trim(L, M.trim_front, M.trim_tail, t0, tl);
-            qcut_slice(tl, (int)(vin & 0xffffu), (int)(vin >> 16), s0, n);
+            vp_trim(L, M.trim_front, M.trim_tail, t0, tl);
+            view_slice(tl, vin, s0, n);
             const int m = M.alen;
             int p = ADP_NONE;
             if (m > 0) {                            // (wave-uniform)
                 // ---- 16 bytes per lane into the group's row
-                const int nvalid = min(max(n - 16 * g, 0), 16);
-                uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                if (nvalid > 0) v = load16u(M.seq + M.off[rec] + (t0 + s0) + 16 * g);
+                const int nvalid = vp_nvalid(n, g);
+                const uint8_t* s = nullptr;
+                if (nvalid > 0) s = M.seq + M.off[rec] + (t0 + s0);        // (no off[rec] behind the batch's last record)
+                const uint4 v = vp_load16(s, nvalid, g);
                 uint32_t d[4] = {v.x, v.y, v.z, v.w};
                 adp_keep16(d, nvalid);
                 *reinterpret_cast<uint4*>(row + 4 * g) = make_uint4(d[0], d[1], d[2], d[3]);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                vp_publish_row();
                 // ---- the search
-                p = qcut_group_min<G>(adp_lane_first<G>(row, n, M.w, m, K.min_overlap, g));
-                __builtin_amdgcn_wave_barrier();                                    // (the next read overwrites the row)
+                p = vp_group_min<G>(adp_lane_first<G>(row, n, M.w, m, K.min_overlap, g));
+                vp_release_row();                                                   // (the next read overwrites the row)
             }
             if (have && g == 0) {
                 K.view[vi] = adp_view(vin, p);
-                if (too_long) atomicCAS(K.status, 0, AQC_ERR_READ_TOO_LONG);
+                if (too_long) vp_raise_too_long(K.status);
                 const int kept = p == ADP_NONE ? n : p;
-                if (rec < K.accum_limit && r1_kept && kept < n) { cnt[2 * k] += 1u; cnt[2 * k + 1] += (uint32_t)(n - kept); }
-                if (k == 0) r1_kept = kept >= 5;
+                vp_count(cnt, k, rec < K.accum_limit && r1_kept, n, kept);
+                if (k == 0) r1_kept = vp_read1_kept(kept);
             }
         }
     }
-    if (K.stats) {
-        if (g == 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (cnt[j]) atomicAdd(&tot[j], (unsigned long long)cnt[j]);
-        }
-        __syncthreads();
-        if (threadIdx.x < 4 && tot[threadIdx.x]) atomicAdd(&K.stats[threadIdx.x], tot[threadIdx.x]);
-    }
+    if (K.stats) vp_flush(cnt, tot, K.stats, g);
 }
 
 }  // namespace aqc

@@ -220,16 +220,15 @@ void aqc_destroy(aqc_ctx* c) {
             }
         if (s.status) (void)hipFree(s.status);
         for (hipEvent_t e : s.census_ev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : s.cut_ev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : s.adapter_ev) if (e) (void)hipEventDestroy(e);
+        for (ViewPass& vp : s.pass)
+            for (hipEvent_t e : vp.ev) if (e) (void)hipEventDestroy(e);
         if (s.ev_main) (void)hipEventDestroy(s.ev_main);
         if (s.ev_qc) (void)hipEventDestroy(s.ev_qc);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
     if (c->qc_stream) (void)hipStreamDestroy(c->qc_stream);
     (void)hipFree(c->counters); (void)hipFree(c->ovl_hist); (void)hipFree(c->dist_hist);
-    if (c->cut_stats) (void)hipFree(c->cut_stats);
-    if (c->adapter_stats) (void)hipFree(c->adapter_stats);
+    for (PassCounts& pc : c->pass_stats) pc.free();
     for (int k = 0; k < 4; k++) {
         (void)hipFree(c->qc[k].acc);
         free_kmer(c->qc[k].kt);
@@ -318,24 +317,20 @@ int aqc_set_quality_cut(aqc_ctx* c, const aqc_cut_config* cut) {
     if (!qcut_on(o)) { c->cut = QcutOpts{}; return 0; }
     if (!qcut_opts_ok(o))
         return fail(AQC_ERR_ARG, "aqc_set_quality_cut: window %d (1 .. %d) / mean quality %d (0 .. %d)", o.window, AQC_MAX_READ_LEN, o.mean_quality, QCUT_MAX_QUALITY);
-    if (!c->cut_stats) {
-        // (the counts exist from the first time a cut is set: a context that never has one allocates what it always did)
-        HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(hipMalloc((void**)&c->cut_stats, sizeof(unsigned long long) * 4));
-        HIP_TRY(hipMemset(c->cut_stats, 0, sizeof(unsigned long long) * 4));
-    }
+    HIP_TRY(c->pass_stats[VP_CUT].ensure(c->device));
     c->cut = o;
     return 0;
 }
 
-int aqc_get_cut_stats(aqc_ctx* c, int64_t out[4]) {
+// the four counts of a view pass, once every slot's work is done
+static int get_pass_stats(aqc_ctx* c, ViewPassId which, int64_t out[4]) {
     if (!c || !out) return fail(AQC_ERR_ARG, "null argument");
     int rc = sync_all(c);
     if (rc) return rc;
-    for (int k = 0; k < 4; ++k) out[k] = 0;
-    if (c->cut_stats) HIP_TRY(hipMemcpy(out, c->cut_stats, sizeof(int64_t) * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c->pass_stats[which].get(out));
     return 0;
 }
+int aqc_get_cut_stats(aqc_ctx* c, int64_t out[4]) { return get_pass_stats(c, VP_CUT, out); }
 
 // the adapters to trim (aqc_adapter.hpp): NULL or both lengths 0 switches the pass off
 int aqc_set_adapter_trim(aqc_ctx* c, const aqc_adapter_config* adapter) {
@@ -345,24 +340,12 @@ int aqc_set_adapter_trim(aqc_ctx* c, const aqc_adapter_config* adapter) {
         return fail(AQC_ERR_ARG, "aqc_set_adapter_trim: adapter lengths %d / %d (0 or %d .. %d letters of ACGT), min overlap %d (1 .. the shorter adapter)",
                     adapter->len1, adapter->len2, ADP_MIN_LEN, ADP_MAX_LEN, adapter->min_overlap);
     if (!adp_on(a)) { c->adapter = AdapterOpts{}; return 0; }
-    if (!c->adapter_stats) {
-        // (like the cut's counts: a context that never has an adapter allocates what it always did)
-        HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(hipMalloc((void**)&c->adapter_stats, sizeof(unsigned long long) * 4));
-        HIP_TRY(hipMemset(c->adapter_stats, 0, sizeof(unsigned long long) * 4));
-    }
+    HIP_TRY(c->pass_stats[VP_ADAPTER].ensure(c->device));
     c->adapter = a;
     return 0;
 }
 
-int aqc_get_adapter_stats(aqc_ctx* c, int64_t out[4]) {
-    if (!c || !out) return fail(AQC_ERR_ARG, "null argument");
-    int rc = sync_all(c);
-    if (rc) return rc;
-    for (int k = 0; k < 4; ++k) out[k] = 0;
-    if (c->adapter_stats) HIP_TRY(hipMemcpy(out, c->adapter_stats, sizeof(int64_t) * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
+int aqc_get_adapter_stats(aqc_ctx* c, int64_t out[4]) { return get_pass_stats(c, VP_ADAPTER, out); }
 
 int aqc_set_circles(aqc_ctx* c, const double* cx, const double* cy, const double* r, const int32_t* lane,
                     const int32_t* tile, int32_t n) {
@@ -393,8 +376,7 @@ int aqc_reset_stats(aqc_ctx* c) {
     HIP_TRY(hipMemset(c->counters, 0, sizeof(unsigned long long) * (AQC_N_COUNTERS + 16)));
     HIP_TRY(hipMemset(c->ovl_hist, 0, sizeof(unsigned long long) * AQC_QC_COLS));
     HIP_TRY(hipMemset(c->dist_hist, 0, sizeof(unsigned long long) * AQC_QC_COLS));
-    if (c->cut_stats) HIP_TRY(hipMemset(c->cut_stats, 0, sizeof(unsigned long long) * 4));
-    if (c->adapter_stats) HIP_TRY(hipMemset(c->adapter_stats, 0, sizeof(unsigned long long) * 4));
+    for (PassCounts& pc : c->pass_stats) HIP_TRY(pc.zero());
     for (auto& sl : c->slots) { HIP_TRY(hipMemcpy(sl.status, &STATUS_CLEAR, sizeof(STATUS_CLEAR), hipMemcpyHostToDevice)); sl.err_record = UINT64_MAX; }
     for (int k = 0; k < 4; k++) {
         HIP_TRY(hipMemset(c->qc[k].acc, 0, sizeof(unsigned long long) * AQC_QC_ROWS * AQC_QC_COLS));

@@ -13,7 +13,8 @@
 //   aqc_upload.hpp   narrow_offsets_kernel, mark_irregular_kernel, quality_views_kernel
 //   aqc_record.hpp   filter_overlap_kernel, filter_overlap_list_kernel, filter_overlap_cut_kernel<LIST>
 //   aqc_fast.hpp     fast_filter_overlap_kernel<NW, PAIRED, WPBT, BARCODE, FUSE, CUT> (a template: the variants are instantiated here)
-//   aqc_qcut.hpp     quality_cut_kernel<G> (the quality cut's pass in front of the verdict kernel, and its function seam)
+//   aqc_viewpass.hpp no kernel of its own: the frame of the two view passes in front of the verdict kernel, and their dispatch on G
+//   aqc_qcut.hpp     quality_cut_kernel<G> (the quality cut's pass, and its function seam)
 //   aqc_adapter.hpp  adapter_cut_kernel<G> (the adapter pass behind it, a second producer of the same views, and its function seam)
 //   aqc_gzdev.hpp    gz_hist_kernel, gz_encode_wave_kernel, gz_encode_kernel, gz_offsets_kernel, gz_pack_kernel
 //   aqc_gzlz.hpp     gz_hist_lz_kernel, gz_encode_lz_kernel (levels 6 - 9)
@@ -23,6 +24,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -286,31 +288,10 @@ static int launch_cut(aqc_ctx* c, Slot& s, const QcutOpts& o, const int32_t trim
     QcutArgs A{};
     A.b = s.view; A.o = o; A.n_mates = n_mates; A.view = view; A.stats = stats; A.accum_limit = accum_limit; A.status = s.status;
     for (int k = 0; k < 2; ++k) { A.trim_front[k] = trim_front[k]; A.trim_tail[k] = trim_tail[k]; }
-    const int G = view_pass_lanes(s);
-    uint64_t blocks = (s.n + (QCUT_THREADS / G) - 1) / (QCUT_THREADS / G);
-    const uint64_t cap = (uint64_t)c->n_cu * 16;
-    if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)blocks), block(QCUT_THREADS);
-    if (G == 8) hipLaunchKernelGGL(quality_cut_kernel<8>, grid, block, 0, s.stream, A);
-    else if (G == 16) hipLaunchKernelGGL(quality_cut_kernel<16>, grid, block, 0, s.stream, A);
-    else if (G == 32) hipLaunchKernelGGL(quality_cut_kernel<32>, grid, block, 0, s.stream, A);
-    else hipLaunchKernelGGL(quality_cut_kernel<64>, grid, block, 0, s.stream, A);
+    vp_dispatch(view_pass_lanes(s), s.n, c->n_cu, [&](auto G, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(quality_cut_kernel<decltype(G)::value>, grid, block, 0, s.stream, A);
+    });
     HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// the cut pass of an aqc_run: both mates' views into the slot's arrays, timed by an event pair of its own
-static int run_cut(aqc_ctx* c, Slot& s, const aqc_config& cfg, uint64_t accum_limit) {
-    const int nm = cfg.paired ? 2 : 1;
-    if (s.cut.reserve(sizeof(uint32_t) * s.n * nm)) return fail(AQC_ERR_HIP, "hipMalloc failed");
-    for (hipEvent_t& e : s.cut_ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-    const int32_t tf[2] = {cfg.trim_front, cfg.trim_front2}, tt[2] = {cfg.trim_tail, cfg.trim_tail2};
-    HIP_TRY(hipEventRecord(s.cut_ev[0], s.stream));
-    const int rc = launch_cut(c, s, c->cut, tf, tt, nm, (uint32_t*)s.cut.p, c->cut_stats, accum_limit);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(s.cut_ev[1], s.stream));
-    s.cut_ran = true;
     return 0;
 }
 
@@ -325,33 +306,35 @@ static int launch_adapter(aqc_ctx* c, Slot& s, const AdapterOpts& a, const int32
         M.trim_front = trim_front[k]; M.trim_tail = trim_tail[k]; M.alen = a.len[k];
         for (int j = 0; j < ADP_WORDS; ++j) M.w[j] = a.w[k][j];
     }
-    const int G = view_pass_lanes(s);
-    uint64_t blocks = (s.n + (ADP_THREADS / G) - 1) / (ADP_THREADS / G);
-    const uint64_t cap = (uint64_t)c->n_cu * 16;
-    if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)blocks), block(ADP_THREADS);
-    if (G == 8) hipLaunchKernelGGL(adapter_cut_kernel<8>, grid, block, 0, s.stream, A);
-    else if (G == 16) hipLaunchKernelGGL(adapter_cut_kernel<16>, grid, block, 0, s.stream, A);
-    else if (G == 32) hipLaunchKernelGGL(adapter_cut_kernel<32>, grid, block, 0, s.stream, A);
-    else hipLaunchKernelGGL(adapter_cut_kernel<64>, grid, block, 0, s.stream, A);
+    vp_dispatch(view_pass_lanes(s), s.n, c->n_cu, [&](auto G, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(adapter_cut_kernel<decltype(G)::value>, grid, block, 0, s.stream, A);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// the adapter pass of an aqc_run, behind the cut pass: it updates the cut's views in place, or fills the array itself
-static int run_adapter(aqc_ctx* c, Slot& s, const aqc_config& cfg, uint64_t accum_limit) {
+// A view pass of an aqc_run: both mates' views into the slot's array, timed by an event pair of its own.  The cut pass fills the
+// array; the adapter pass behind it updates the cut's views in place, or fills the array itself.
+static int run_view_pass(aqc_ctx* c, Slot& s, ViewPassId which, const aqc_config& cfg, uint64_t accum_limit) {
+    ViewPass& vp = s.pass[which];
     const int nm = cfg.paired ? 2 : 1;
     if (s.cut.reserve(sizeof(uint32_t) * s.n * nm)) return fail(AQC_ERR_HIP, "hipMalloc failed");
-    for (hipEvent_t& e : s.adapter_ev)
+    for (hipEvent_t& e : vp.ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
     const int32_t tf[2] = {cfg.trim_front, cfg.trim_front2}, tt[2] = {cfg.trim_tail, cfg.trim_tail2};
-    AdapterOpts a = c->adapter;
-    if (nm == 1) a.len[1] = 0;
-    HIP_TRY(hipEventRecord(s.adapter_ev[0], s.stream));
-    const int rc = launch_adapter(c, s, a, tf, tt, nm, s.cut_ran ? (const uint32_t*)s.cut.p : nullptr, (uint32_t*)s.cut.p, c->adapter_stats, accum_limit);
+    uint32_t* const view = (uint32_t*)s.cut.p;
+    unsigned long long* const stats = c->pass_stats[which].p;
+    HIP_TRY(hipEventRecord(vp.ev[0], s.stream));
+    int rc;
+    if (which == VP_CUT) rc = launch_cut(c, s, c->cut, tf, tt, nm, view, stats, accum_limit);
+    else {
+        AdapterOpts a = c->adapter;
+        if (nm == 1) a.len[1] = 0;
+        rc = launch_adapter(c, s, a, tf, tt, nm, s.pass[VP_CUT].ran ? view : nullptr, view, stats, accum_limit);
+    }
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(s.adapter_ev[1], s.stream));
-    s.adapter_ran = true;
+    HIP_TRY(hipEventRecord(vp.ev[1], s.stream));
+    vp.ran = true;
     return 0;
 }
 
@@ -364,22 +347,19 @@ int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
     if (cut && c->cfg.barcode) return fail(AQC_ERR_UNSUPPORTED, "aqc_run: the quality cut or an adapter together with a barcode is not implemented");
     s->fused = false;
     s->verdict_words = 0;
-    s->cut_ran = false;
-    s->adapter_ran = false;
+    for (ViewPass& vp : s->pass) vp.ran = false;
     if (s->n == 0) { s->ran = true; return 0; }
     aqc_config cfg = c->cfg;
     if (!cfg.paired) cfg.no_overlap = 1;
     DevStats st{c->counters, c->ovl_hist, c->dist_hist, s->status, err_key_of(*s)};
     s->err_record = UINT64_MAX;
     if (s->qc.pending()) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_qc, 0));      // (statRead of the previous run still reads the results)
-    if (qcut_on(c->cut)) {
-        const int rc = run_cut(c, *s, cfg, accum_limit);
-        if (rc) return rc;
-    }
-    if (adp_on(c->adapter)) {
-        const int rc = run_adapter(c, *s, cfg, accum_limit);
-        if (rc) return rc;
-    }
+    const bool pass_on[VP_N] = {qcut_on(c->cut), adp_on(c->adapter)};
+    for (int p = 0; p < VP_N; ++p)
+        if (pass_on[p]) {
+            const int rc = run_view_pass(c, *s, (ViewPassId)p, cfg, accum_limit);
+            if (rc) return rc;
+        }
     HIP_TRY(hipEventRecord(launch_event(*s, AQC_K_FILTER_OVERLAP, 0), s->stream));
     const Verdict k = choose_verdict_kernel(c, *s, cfg);
     s->used_fast = k != Verdict::GENERAL;
@@ -442,25 +422,19 @@ int aqc_fetch_quality_views(aqc_ctx* c, int slot, int mate, uint32_t* out, uint6
     return 0;
 }
 
-int aqc_cut_ms(aqc_ctx* c, int slot, float* ms) {
+// the time of a view pass of the slot's last aqc_run; 0: it launched none
+static int view_pass_ms(aqc_ctx* c, int slot, ViewPassId which, float* ms, const char* who) {
     GET_SLOT(s);
-    if (!ms) return fail(AQC_ERR_ARG, "aqc_cut_ms: null argument");
+    if (!ms) return fail(AQC_ERR_ARG, "%s: null argument", who);
     *ms = 0.f;
-    if (!s->cut_ran) return 0;
+    const ViewPass& vp = s->pass[which];
+    if (!vp.ran) return 0;
     HIP_TRY(slot_sync(*s));
-    HIP_TRY(hipEventElapsedTime(ms, s->cut_ev[0], s->cut_ev[1]));
+    HIP_TRY(hipEventElapsedTime(ms, vp.ev[0], vp.ev[1]));
     return 0;
 }
-
-int aqc_adapter_ms(aqc_ctx* c, int slot, float* ms) {
-    GET_SLOT(s);
-    if (!ms) return fail(AQC_ERR_ARG, "aqc_adapter_ms: null argument");
-    *ms = 0.f;
-    if (!s->adapter_ran) return 0;
-    HIP_TRY(slot_sync(*s));
-    HIP_TRY(hipEventElapsedTime(ms, s->adapter_ev[0], s->adapter_ev[1]));
-    return 0;
-}
+int aqc_cut_ms(aqc_ctx* c, int slot, float* ms) { return view_pass_ms(c, slot, VP_CUT, ms, "aqc_cut_ms"); }
+int aqc_adapter_ms(aqc_ctx* c, int slot, float* ms) { return view_pass_ms(c, slot, VP_ADAPTER, ms, "aqc_adapter_ms"); }
 
 // (host state only: set by aqc_run when it chose the kernel, so there is nothing to wait for)
 int aqc_last_verdict_words(aqc_ctx* c, int slot) {
@@ -653,22 +627,30 @@ int aqc_edit_distance(aqc_ctx* c, const aqc_batch* b, int32_t* dist) {
     return check_status(*s);
 }
 
-int aqc_quality_cut_views(aqc_ctx* c, const aqc_batch* b, const aqc_cut_config* cut, int32_t trim_front, int32_t trim_tail, uint32_t* view) {
-    if (!cut || !view) return fail(AQC_ERR_ARG, "aqc_quality_cut_views: null argument");
-    const QcutOpts o{cut->front ? 1 : 0, cut->tail ? 1 : 0, cut->right ? 1 : 0, cut->window, cut->mean_quality};
-    if (!qcut_opts_ok(o) || trim_front < 0 || trim_tail < 0) return fail(AQC_ERR_ARG, "aqc_quality_cut_views: window / mean quality / trim out of range");
+// The function seam of a view pass: read 1 of the batch through the pass alone, one view per record out.  view_in (may be NULL): the
+// views the reads come with, uploaded into the array the pass then updates in place.  launch(slot, device views) starts the kernel.
+static int view_seam(aqc_ctx* c, const aqc_batch* b, bool need_qual, const uint32_t* view_in, uint32_t* view,
+                     const std::function<int(Slot&, uint32_t*)>& launch) {
     Slot* s;
-    int rc = seam_prepare(c, b, true, false, &s);
+    int rc = seam_prepare(c, b, need_qual, false, &s);
     if (rc) return rc;
     const uint64_t n = b->n;
     if (n == 0) return 0;
     DevBuf out;
     if (out.reserve(4 * n)) return fail(AQC_ERR_HIP, "hipMalloc failed");
-    const int32_t tf[2] = {trim_front, 0}, tt[2] = {trim_tail, 0};
-    if ((rc = launch_cut(c, *s, o, tf, tt, 1, (uint32_t*)out.p, nullptr, UINT64_MAX))) return rc;
+    if (view_in) HIP_TRY(hipMemcpyAsync(out.p, view_in, 4 * n, hipMemcpyHostToDevice, s->stream));
+    if ((rc = launch(*s, (uint32_t*)out.p))) return rc;
     if ((rc = seam_out(s, out, view, n))) return rc;
     HIP_TRY(slot_sync(*s));
     return check_status(*s);
+}
+
+int aqc_quality_cut_views(aqc_ctx* c, const aqc_batch* b, const aqc_cut_config* cut, int32_t trim_front, int32_t trim_tail, uint32_t* view) {
+    if (!cut || !view) return fail(AQC_ERR_ARG, "aqc_quality_cut_views: null argument");
+    const QcutOpts o{cut->front ? 1 : 0, cut->tail ? 1 : 0, cut->right ? 1 : 0, cut->window, cut->mean_quality};
+    if (!qcut_opts_ok(o) || trim_front < 0 || trim_tail < 0) return fail(AQC_ERR_ARG, "aqc_quality_cut_views: window / mean quality / trim out of range");
+    const int32_t tf[2] = {trim_front, 0}, tt[2] = {trim_tail, 0};
+    return view_seam(c, b, true, nullptr, view, [&](Slot& s, uint32_t* v) { return launch_cut(c, s, o, tf, tt, 1, v, nullptr, UINT64_MAX); });
 }
 
 int aqc_adapter_views(aqc_ctx* c, const aqc_batch* b, const aqc_adapter_config* adapter, int32_t trim_front, int32_t trim_tail, const uint32_t* view_in,
@@ -677,20 +659,10 @@ int aqc_adapter_views(aqc_ctx* c, const aqc_batch* b, const aqc_adapter_config* 
     AdapterOpts a{};
     if (!adp_from_config(adapter, a) || trim_front < 0 || trim_tail < 0) return fail(AQC_ERR_ARG, "aqc_adapter_views: adapter / min overlap / trim out of range");
     a.len[1] = 0;
-    Slot* s;
-    // (the search reads sequence lines only; a batch that brings quality lines is taken as aqc_run takes it, LEN_IRR marks included)
-    int rc = seam_prepare(c, b, b && b->qual1 != nullptr, false, &s);
-    if (rc) return rc;
-    const uint64_t n = b->n;
-    if (n == 0) return 0;
-    DevBuf out;
-    if (out.reserve(4 * n)) return fail(AQC_ERR_HIP, "hipMalloc failed");
-    if (view_in) HIP_TRY(hipMemcpyAsync(out.p, view_in, 4 * n, hipMemcpyHostToDevice, s->stream));
     const int32_t tf[2] = {trim_front, 0}, tt[2] = {trim_tail, 0};
-    if ((rc = launch_adapter(c, *s, a, tf, tt, 1, view_in ? (const uint32_t*)out.p : nullptr, (uint32_t*)out.p, nullptr, UINT64_MAX))) return rc;
-    if ((rc = seam_out(s, out, view, n))) return rc;
-    HIP_TRY(slot_sync(*s));
-    return check_status(*s);
+    // (the search reads sequence lines only; a batch that brings quality lines is taken as aqc_run takes it, LEN_IRR marks included)
+    return view_seam(c, b, b && b->qual1 != nullptr, view_in, view,
+                     [&](Slot& s, uint32_t* v) { return launch_adapter(c, s, a, tf, tt, 1, view_in ? v : nullptr, v, nullptr, UINT64_MAX); });
 }
 
 // ---- the reference's existing native seam: libed.so (editdistance/_editdistance.h:16,23, loaded by util.py:16-24) ----

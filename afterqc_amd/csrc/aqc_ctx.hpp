@@ -17,6 +17,28 @@
 
 namespace aqc {
 
+// The passes in front of the verdict kernel that leave a view per mate and record in Slot::cut (aqc_viewpass.hpp), in launch order
+enum ViewPassId { VP_CUT = 0, VP_ADAPTER = 1, VP_N = 2 };
+// ... what a slot keeps of each: the event pair around the pass of the last aqc_run (aqc_cut_ms / aqc_adapter_ms), if it launched one
+struct ViewPass { hipEvent_t ev[2] = {nullptr, nullptr}; bool ran = false; };
+// ... and what the context keeps: [4] reads of R1 the pass made shorter, bases it took from them, the same for R2.  On the device
+// from the first time the pass is switched on: a context that never sets it allocates what it always did.
+struct __attribute__((visibility("hidden"))) PassCounts {
+    unsigned long long* p = nullptr;
+    hipError_t ensure(int device) {
+        if (p) return hipSuccess;
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = hipMalloc((void**)&p, sizeof(unsigned long long) * 4);
+        return e == hipSuccess ? zero() : e;
+    }
+    hipError_t zero() { return p ? hipMemset(p, 0, sizeof(unsigned long long) * 4) : hipSuccess; }
+    hipError_t get(int64_t out[4]) const {
+        for (int k = 0; k < 4; ++k) out[k] = 0;
+        return p ? hipMemcpy(out, p, sizeof(int64_t) * 4, hipMemcpyDeviceToHost) : hipSuccess;
+    }
+    void free() { if (p) (void)hipFree(p); p = nullptr; }
+};
+
 // What a slot holds once per input file (mate 0 = read 1, mate 1 = read 2), grouped like the slot itself by the unit that fills it.
 struct __attribute__((visibility("hidden"))) Mate {
     // ---- upload and verdicts (aqc_capi_run.hip; aqc_frame fills the same arena and tables from text) ----
@@ -77,11 +99,8 @@ struct __attribute__((visibility("hidden"))) Slot {
     uint64_t n = 0;
     bool paired = false, ran = false, used_fast = false;
     int verdict_words = 0;         // words per read of the lane-per-pair instance the last aqc_run launched, 0: the general kernel
-    DevBuf cut;                                  // the quality cut's views (aqc_qcut.hpp: one per mate and record), filled by aqc_run in front of the verdict kernel
-    hipEvent_t cut_ev[2] = {nullptr, nullptr};   // around the cut pass of the last aqc_run (aqc_cut_ms) ...
-    bool cut_ran = false;                        // ... if it launched one
-    hipEvent_t adapter_ev[2] = {nullptr, nullptr};   // the same for the adapter pass (aqc_adapter.hpp, aqc_adapter_ms): it writes its views into `cut` too
-    bool adapter_ran = false;
+    DevBuf cut;                    // the views (aqc_viewpass.hpp: one per mate and record), filled by aqc_run's view passes in front of the verdict kernel
+    ViewPass pass[VP_N];
     // AQC_FUSED=1: the verdict kernel placed the slot's records in their streams and copied the whole good ones (aqc_fast.hpp, FUSE)
     DevBuf fz_state, fz_misc;                 // look-back words per batch (Mate::fz_rec: position words per record); ticket | abort | totals[4]
     bool fused = false;                       // ... for the records the slot holds now (aqc_format checks fz_misc's abort word)
@@ -133,9 +152,8 @@ struct __attribute__((visibility("hidden"))) aqc_ctx {
     aqc_config cfg{};
     bool has_cfg = false;
     aqc::QcutOpts cut{};               // aqc_set_quality_cut: the quality cut (all modes 0: off, no kernel of it is launched)
-    unsigned long long* cut_stats = nullptr;   // [4] reads of R1 the cut made shorter, bases it took from them, the same for R2
     aqc::AdapterOpts adapter{};        // aqc_set_adapter_trim: the adapters to trim (both lengths 0: off, no kernel of it is launched)
-    unsigned long long* adapter_stats = nullptr;   // [4] the same counts for the adapter pass
+    aqc::PassCounts pass_stats[aqc::VP_N];
     aqc::DevBuf circ[5];
     aqc::DevBuf kmer_partial;          // per-round u16 count slices of kmer_count_kernel
     aqc::DevBuf gz_crc;                // GzCrcTables (aqc_compress)

@@ -41,7 +41,7 @@
 #include "afterqc_hip.h"
 #include "aqc_prim.hpp"
 #include "aqc_batch.hpp"
-#include "aqc_qcut.hpp"
+#include "aqc_viewpass.hpp"
 
 namespace aqc {
 
@@ -838,7 +838,7 @@ __global__ __launch_bounds__(WPBT * WAVE, (WPBT + 3) / 4 < FAST_MIN_WAVES ? (WPB
                 // the cut pass's view of this read, relative to the trimmed read: [c0:c1] the python way
                 const FastCutArgsRare Rc = (FastCutArgsRare)R;
                 const uint32_t cv = valid ? Rc->cut[PAIRED ? 2u * rec + (uint32_t)role : rec] : 0u;
-                qcut_slice(len_own, (int)(cv & 0xffffu), (int)(cv >> 16), st_, nl_);
+                view_slice(len_own, cv, st_, nl_);
                 a_own += st_; len_own = nl_;
             }
         }

@@ -2,68 +2,35 @@
 // mate of a batch, which part [c0, c1) of its TRIMMED quality line the cut keeps.  The rule is tests/cut_rule.py (cut_window):
 // integers only, a window of w = min(W, n) bases is good when its sum of (byte - 33) is at least Q * w.
 //
-//   groups   G neighbouring lanes (8, 16, 32 or 64, by the slot's longest quality line) own one read; a workgroup of four waves
-//            owns 256 / G consecutive records and takes read 1, then read 2 of each (read 2's counts need read 1's outcome).
-//   load     one 16-byte load per lane, at the quality line's own alignment (the arenas are padded: aqc_batch), the bytes outside
-//            the line count as nothing.  The length comes from the length word, or — a record marked LEN_IRR — from its
-//            quality-length word: no address is ever formed from a word that carries the mark.
+// The frame — lanes per read, the 16-byte load, the view word, the counts — is that of every view pass: aqc_viewpass.hpp.  Here:
+//
+//   line     the quality line.  Its length comes from the length word, or — a record marked LEN_IRR — from its quality-length
+//            word: no address is ever formed from a word that carries the mark.  The bytes outside the line count as nothing.
 //   sums     W is a run-time value of up to AQC_MAX_READ_LEN, so no window sum is built directly: 16 running sums per lane, a
 //            segmented scan of the lane totals over the group, and the prefix sums P[0 .. n] of the line stand in LDS.
 //   windows  pass k tests the windows that start at i = k * G + lane: P[i + w] - P[i] >= Q * w, neighbouring lanes read neighbouring
 //            words.  A lane keeps one bit per pass: 16 bits.
 //   ends     first good and last good start by find-first-set / count-leading-zeros and a min / max over the group, then the
 //            first bad start at or behind c0 the same way.
-//   out      c0 | c1 << 16 per mate and record (the mates of a record side by side), relative to the trimmed quality line.  The verdict kernels apply it to every
-//            string by the string's own length (qcut_apply): a record whose quality line is not as long as its sequence line
-//            is sliced the python way, like upstream's trim().
+//   out      the view (c0, c1), relative to the trimmed quality line; the counts are what it takes from the SEQUENCE line.
 //
 // The per-read functions are __host__ __device__: tests/native/qcut_selftest.cpp includes this header without HIP, deals the
 // lanes of a group out by plain loops and compares with vectors the model wrote.
 #pragma once
 #include <stdint.h>
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define QCUT_HD __host__ __device__ __forceinline__
-#else
-#define QCUT_HD inline
-#endif
+
+#include "aqc_viewpass.hpp"
 
 namespace aqc {
 
 constexpr int QCUT_NONE = 0x7fffffff;
-constexpr int QCUT_MAX_LEN = 1000;          // AQC_MAX_READ_LEN (afterqc_hip.h), restated: the self-test includes nothing else
 constexpr int QCUT_MAX_QUALITY = 93;
 
 // the option struct of the C API, as the kernels take it (aqc_cut_config has the same five words)
 struct QcutOpts { int32_t front, tail, right, window, mean_quality; };
 
-QCUT_HD int qcut_min(int a, int b) { return a < b ? a : b; }
-QCUT_HD int qcut_max(int a, int b) { return a > b ? a : b; }
-
-// trim() of preprocesser.py:19-28 on a string of `len` bytes -> (start, length)
-QCUT_HD void qcut_trim(int len, int front, int tail, int& st, int& nl) {
-    const int end = tail > 0 ? qcut_max(len - tail, 0) : len;
-    st = qcut_min(front, len);
-    nl = qcut_max(end - st, 0);
-}
-
-// s[c0:c1] of a string of `len` bytes, python slice semantics (0 <= c0 <= c1) -> (start, length)
-QCUT_HD void qcut_slice(int len, int c0, int c1, int& st, int& nl) {
-    st = qcut_min(c0, len);
-    nl = qcut_max(qcut_min(c1, len) - st, 0);
-}
-
-// trim() and then the cut's view (c0 | c1 << 16) on a string of `len` bytes: moves (a, l), the view the caller holds of it
-QCUT_HD void qcut_apply(int& a, int& l, int front, int tail, uint32_t view) {
-    int st, nl, st2, nl2;
-    qcut_trim(l, front, tail, st, nl);
-    qcut_slice(nl, (int)(view & 0xffffu), (int)(view >> 16), st2, nl2);
-    a += st + st2;
-    l = nl2;
-}
-
 // the running sums of (byte - 33) over the first `nvalid` of 16 bytes (little-endian dwords); bytes behind them add nothing
-QCUT_HD void qcut_sum16(uint32_t x, uint32_t y, uint32_t z, uint32_t w, int nvalid, int p[16]) {
+VP_HD void qcut_sum16(uint32_t x, uint32_t y, uint32_t z, uint32_t w, int nvalid, int p[16]) {
     const uint32_t d[4] = {x, y, z, w};
     int run = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -78,7 +45,7 @@ QCUT_HD void qcut_sum16(uint32_t x, uint32_t y, uint32_t z, uint32_t w, int nval
 
 // Pass k of lane g in a group of G lanes: the window that starts at i = k * G + g.  Bit k of the low half: the window exists
 // (i <= n - w); of the high half: it exists and is good.  P: the prefix sums P[0 .. n] of the line, thr = Q * w.
-QCUT_HD uint32_t qcut_lane_bits(const int* P, int n, int w, int thr, int g, int G, int passes) {
+VP_HD uint32_t qcut_lane_bits(const int* P, int n, int w, int thr, int g, int G, int passes) {
     uint32_t bits = 0;
     for (int k = 0; k < passes; ++k) {
         const int i = k * G + g;
@@ -87,7 +54,7 @@ QCUT_HD uint32_t qcut_lane_bits(const int* P, int n, int w, int thr, int g, int 
     return bits;
 }
 
-QCUT_HD int qcut_ffs16(uint32_t m) {          // lowest set bit of a 16-bit mask, m != 0
+VP_HD int qcut_ffs16(uint32_t m) {          // lowest set bit of a 16-bit mask, m != 0
 #if defined(__HIP_DEVICE_COMPILE__)
     return __ffs((int)m) - 1;
 #else
@@ -96,7 +63,7 @@ QCUT_HD int qcut_ffs16(uint32_t m) {          // lowest set bit of a 16-bit mask
     return k;
 #endif
 }
-QCUT_HD int qcut_fls16(uint32_t m) {          // highest set bit, m != 0
+VP_HD int qcut_fls16(uint32_t m) {          // highest set bit, m != 0
 #if defined(__HIP_DEVICE_COMPILE__)
     return 31 - __clz((int)m);
 #else
@@ -107,43 +74,39 @@ QCUT_HD int qcut_fls16(uint32_t m) {          // highest set bit, m != 0
 }
 
 // the lane's first / last window start whose bit is set in the 16-bit mask m; `from`: only starts >= from count
-QCUT_HD int qcut_lane_first(uint32_t m, int g, int G, int from) {
+VP_HD int qcut_lane_first(uint32_t m, int g, int G, int from) {
     const int k0 = from > g ? (from - g + G - 1) / G : 0;          // first pass whose start is >= from
     m = k0 >= 16 ? 0u : (m >> k0) << k0;
     return m ? qcut_ffs16(m) * G + g : QCUT_NONE;
 }
-QCUT_HD int qcut_lane_last(uint32_t m, int g, int G) { return m ? qcut_fls16(m) * G + g : -1; }
+VP_HD int qcut_lane_last(uint32_t m, int g, int G) { return m ? qcut_fls16(m) * G + g : -1; }
 
 // what the group's reductions leave: c0 from the first good start (QCUT_NONE: no good window)
-QCUT_HD int qcut_front(const QcutOpts& o, int first_good) { return o.front ? first_good : 0; }
+VP_HD int qcut_front(const QcutOpts& o, int first_good) { return o.front ? first_good : 0; }
 // ... and the view: last good start (-1: none), first bad start at or behind c0 (QCUT_NONE: none)
-QCUT_HD uint32_t qcut_view(const QcutOpts& o, int n, int w, int first_good, int last_good, int first_bad) {
+VP_HD uint32_t qcut_view(const QcutOpts& o, int n, int w, int first_good, int last_good, int first_bad) {
     if (n == 0) return 0u;
     if ((o.front || o.tail) && first_good == QCUT_NONE) return 0u;
     const int c0 = qcut_front(o, first_good);
     int c1 = o.tail ? last_good + w : n;
-    if (o.right && first_bad != QCUT_NONE) c1 = qcut_min(c1, first_bad);
-    c1 = qcut_max(c1, c0);
-    return (uint32_t)c0 | ((uint32_t)c1 << 16);
+    if (o.right && first_bad != QCUT_NONE) c1 = vp_min(c1, first_bad);
+    c1 = vp_max(c1, c0);
+    return view_word(c0, c1);
 }
 
 // the window and threshold of a line of n bytes
-QCUT_HD int qcut_window(const QcutOpts& o, int n) { return qcut_min(o.window, n); }
-QCUT_HD bool qcut_opts_ok(const QcutOpts& o) {
-    return o.window >= 1 && o.window <= QCUT_MAX_LEN && o.mean_quality >= 0 && o.mean_quality <= QCUT_MAX_QUALITY;
+VP_HD int qcut_window(const QcutOpts& o, int n) { return vp_min(o.window, n); }
+VP_HD bool qcut_opts_ok(const QcutOpts& o) {
+    return o.window >= 1 && o.window <= VP_MAX_LEN && o.mean_quality >= 0 && o.mean_quality <= QCUT_MAX_QUALITY;
 }
-QCUT_HD bool qcut_on(const QcutOpts& o) { return o.front || o.tail || o.right; }
+VP_HD bool qcut_on(const QcutOpts& o) { return o.front || o.tail || o.right; }
 
 }  // namespace aqc
 
 #if defined(__HIPCC__)
-#include "afterqc_hip.h"
-#include "aqc_prim.hpp"
 #include "aqc_batch.hpp"
 
 namespace aqc {
-
-static_assert(QCUT_MAX_LEN == AQC_MAX_READ_LEN, "the cut pass takes every read the verdict kernels take");
 
 struct QcutArgs {
     DevBatch b;
@@ -156,27 +119,10 @@ struct QcutArgs {
     int* status;
 };
 
-constexpr int QCUT_THREADS = 256;
-
-// min / max over the G lanes of a group (every lane of the wave runs it)
 template <int G>
-__device__ __forceinline__ int qcut_group_min(int v) {
-#pragma unroll
-    for (int d = 1; d < G; d <<= 1) v = min(v, __shfl_xor(v, d, WAVE));
-    return v;
-}
-template <int G>
-__device__ __forceinline__ int qcut_group_max(int v) {
-#pragma unroll
-    for (int d = 1; d < G; d <<= 1) v = max(v, __shfl_xor(v, d, WAVE));
-    return v;
-}
-
-template <int G>
-__global__ __launch_bounds__(QCUT_THREADS) void quality_cut_kernel(QcutArgs K) {
+__global__ __launch_bounds__(VP_THREADS) void quality_cut_kernel(QcutArgs K) {
     static_assert(G == 8 || G == 16 || G == 32 || G == 64, "a group is a power-of-two part of a wave");
-    constexpr int CAP = 16 * G;                     // longest line a group takes
-    constexpr int GROUPS = QCUT_THREADS / G;        // records per workgroup and round
+    constexpr int CAP = vp_cap(G), GROUPS = vp_groups(G);
     constexpr int AREA = CAP + 4;                   // words per group: three unused, P[0], then P[1 ..] on a 16-byte boundary
     __shared__ __attribute__((aligned(16))) int lds[GROUPS * AREA];
     __shared__ unsigned long long tot[4];
@@ -207,19 +153,18 @@ __global__ __launch_bounds__(QCUT_THREADS) void quality_cut_kernel(QcutArgs K) {
             const int L = (int)(lw[k] & LEN_MASK);
             int n_line = L;
             if (irr) n_line = (int)((k ? b.qlen2[rec] : b.qlen1[rec]) & QLEN_MASK);
-            bool too_long = n_line > CAP || n_line > AQC_MAX_READ_LEN;
+            const bool too_long = vp_too_long<G>(n_line);
             if (!have || too_long) n_line = 0;
             int q0 = 0, n = 0;
-            qcut_trim(n_line, K.trim_front[k], K.trim_tail[k], q0, n);
+            vp_trim(n_line, K.trim_front[k], K.trim_tail[k], q0, n);
             const uint8_t* q = nullptr;
             if (have && n > 0) {
                 const uint32_t* const qo = k ? (b.qoff2 ? b.qoff2 : b.off2) : (b.qoff1 ? b.qoff1 : b.off1);
                 q = (k ? b.qual2 : b.qual1) + qo[rec] + q0;
             }
             // ---- 16 bytes per lane, their running sums, the scan over the group
-            const int nvalid = min(max(n - 16 * g, 0), 16);
-            uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if (nvalid > 0) v = load16u(q + 16 * g);
+            const int nvalid = vp_nvalid(n, g);
+            const uint4 v = vp_load16(q, nvalid, g);
             int p[16];
             qcut_sum16(v.x, v.y, v.z, v.w, nvalid, p);
             const int incl = wave_incl_sum(p[15], lane);
@@ -235,9 +180,7 @@ __global__ __launch_bounds__(QCUT_THREADS) void quality_cut_kernel(QcutArgs K) {
             S[1] = make_int4(base + p[4], base + p[5], base + p[6], base + p[7]);
             S[2] = make_int4(base + p[8], base + p[9], base + p[10], base + p[11]);
             S[3] = make_int4(base + p[12], base + p[13], base + p[14], base + p[15]);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            vp_publish_row();
             // ---- the windows: one bit per pass and lane
             const int w = qcut_window(K.o, n);
             const int thr = K.o.mean_quality * w;
@@ -245,33 +188,25 @@ __global__ __launch_bounds__(QCUT_THREADS) void quality_cut_kernel(QcutArgs K) {
             const int passes = (wave_max_i(starts) + G - 1) / G;                    // (wave-uniform, <= 16)
             const uint32_t bits = qcut_lane_bits(P, n, w, thr, g, G, passes);
             const uint32_t good = bits >> 16, bad = (bits & 0xffffu) & ~good;
-            const int first_good = qcut_group_min<G>(qcut_lane_first(good, g, G, 0));
-            const int last_good = qcut_group_max<G>(qcut_lane_last(good, g, G));
+            const int first_good = vp_group_min<G>(qcut_lane_first(good, g, G, 0));
+            const int last_good = vp_group_max<G>(qcut_lane_last(good, g, G));
             const int c0 = first_good == QCUT_NONE ? 0 : qcut_front(K.o, first_good);
-            const int first_bad = qcut_group_min<G>(qcut_lane_first(bad, g, G, c0));
+            const int first_bad = vp_group_min<G>(qcut_lane_first(bad, g, G, c0));
             const uint32_t view = qcut_view(K.o, n, w, first_good, last_good, first_bad);
-            __builtin_amdgcn_wave_barrier();                                        // (the next line's sums overwrite P)
+            vp_release_row();                                                       // (the next line's sums overwrite P)
             if (have && g == 0) {
                 K.view[rec * (uint64_t)K.n_mates + (uint64_t)k] = view;
-                if (too_long) atomicCAS(K.status, 0, AQC_ERR_READ_TOO_LONG);
+                if (too_long) vp_raise_too_long(K.status);
                 // what the cut takes from the SEQUENCE line (sliced by its own length, like the quality line)
                 int st, tl, st2, kept;
-                qcut_trim(L, K.trim_front[k], K.trim_tail[k], st, tl);
-                qcut_slice(tl, (int)(view & 0xffffu), (int)(view >> 16), st2, kept);
-                if (rec < K.accum_limit && r1_kept && kept < tl) { cnt[2 * k] += 1u; cnt[2 * k + 1] += (uint32_t)(tl - kept); }
-                if (k == 0) r1_kept = kept >= 5;
+                vp_trim(L, K.trim_front[k], K.trim_tail[k], st, tl);
+                view_slice(tl, view, st2, kept);
+                vp_count(cnt, k, rec < K.accum_limit && r1_kept, tl, kept);
+                if (k == 0) r1_kept = vp_read1_kept(kept);
             }
         }
     }
-    if (K.stats) {
-        if (g == 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (cnt[j]) atomicAdd(&tot[j], (unsigned long long)cnt[j]);
-        }
-        __syncthreads();
-        if (threadIdx.x < 4 && tot[threadIdx.x]) atomicAdd(&K.stats[threadIdx.x], tot[threadIdx.x]);
-    }
+    if (K.stats) vp_flush(cnt, tot, K.stats, g);
 }
 
 }  // namespace aqc

@@ -11,7 +11,7 @@
 #include "afterqc_hip.h"
 #include "aqc_prim.hpp"
 #include "aqc_batch.hpp"
-#include "aqc_qcut.hpp"
+#include "aqc_viewpass.hpp"
 
 namespace aqc {
 
@@ -242,7 +242,7 @@ struct WaveLds {
     uint8_t *rs1, *rs2;                // 2 x 64 bytes (barcode readStart strings)
 };
 
-// CUT: the trim stage also applies the per-read views of the quality cut (aqc_qcut.hpp: c0 | c1 << 16, the mates of a record side by side)
+// CUT: the trim stage also applies the per-read views of the passes in front (aqc_viewpass.hpp: the quality cut, the adapter pass; the mates of a record side by side)
 template <bool CUT = false, class Cfg>      // aqc_config, or aqc_config in the kernarg segment (address space 4: its fields are scalar loads where they are used)
 __device__ __forceinline__ void process_record_wave(const DevBatch& b, uint64_t rec, const Cfg& cfg, const DevCircles& circ,
                                            const WaveLds& w, aqc_result* __restrict__ results, BlockAcc& acc,
@@ -339,13 +339,13 @@ __device__ __forceinline__ void process_record_wave(const DevBatch& b, uint64_t 
             // ... and the quality cut: every string is sliced by its own length, trim() first, then [c0:c1] of the cut pass
             if (flag < 0) {
                 const uint32_t v1 = cut[paired ? 2 * rec : rec];
-                qcut_apply(a1, len1, cfg.trim_front, cfg.trim_tail, v1);
-                qcut_apply(qa1, ql1, cfg.trim_front, cfg.trim_tail, v1);
+                view_apply(a1, len1, cfg.trim_front, cfg.trim_tail, v1);
+                view_apply(qa1, ql1, cfg.trim_front, cfg.trim_tail, v1);
                 if (len1 < 5) flag = AQC_BADTRIM1;
                 else if (paired) {
                     const uint32_t v2 = cut[2 * rec + 1];
-                    qcut_apply(a2, len2, cfg.trim_front2, cfg.trim_tail2, v2);
-                    qcut_apply(qa2, ql2, cfg.trim_front2, cfg.trim_tail2, v2);
+                    view_apply(a2, len2, cfg.trim_front2, cfg.trim_tail2, v2);
+                    view_apply(qa2, ql2, cfg.trim_front2, cfg.trim_tail2, v2);
                     if (len2 < 5) flag = AQC_BADTRIM2;
                 }
             }

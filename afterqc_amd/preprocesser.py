@@ -108,14 +108,6 @@ def cut_config(opt):
     return capi.CutConfig(int(modes[0]), int(modes[1]), int(modes[2]), int(getattr(opt, "cut_window_size", 4)), int(getattr(opt, "cut_mean_quality", 20)))
 
 
-def set_cut(engine, cut):
-    """the cut on an engine — only ever called with a mode on: an engine that cannot cut is an error, never a run without the cut"""
-    if not hasattr(engine, "set_quality_cut"):
-        raise RuntimeError("afterqc_amd: --cut_front / --cut_tail / --cut_right need an engine with set_quality_cut; %s has none"
-                           % type(engine).__name__)
-    engine.set_quality_cut(cut)
-
-
 def adapter_config(opt):
     """--adapter_sequence / --adapter_sequence_r2 / --adapter_min_overlap as the engine takes them; None: no adapter is given
     (options objects built without the adapter options count as off).  Single-end input has no read 2 to search."""
@@ -128,13 +120,20 @@ def adapter_config(opt):
     return capi.AdapterConfig(a1, a2, int(getattr(opt, "adapter_min_overlap", 4)))
 
 
-def set_adapter(engine, adapter):
-    """the adapters on an engine — only ever called with one given: an engine that cannot trim adapters is an error, never a run
-    without the option"""
-    if not hasattr(engine, "set_adapter_trim"):
-        raise RuntimeError("afterqc_amd: --adapter_sequence / --adapter_sequence_r2 need an engine with set_adapter_trim; %s has none"
-                           % type(engine).__name__)
-    engine.set_adapter_trim(adapter)
+# the passes in front of the verdict kernel that an option switches on: the engine's setter, the options it stands for
+VIEW_PASSES = (("set_quality_cut", "--cut_front / --cut_tail / --cut_right"),
+               ("set_adapter_trim", "--adapter_sequence / --adapter_sequence_r2"))
+
+
+def set_view_passes(engine, configs, clear=False):
+    """the quality cut and the adapters (configs: one per entry of VIEW_PASSES, None: off) on an engine.  A pass that is on needs
+    an engine that has it: an error, never a run without the option.  clear: a pass that is off is switched off on an engine that
+    has it (an engine the caller handed over may come from a run that had it on)"""
+    for (setter, options), config in zip(VIEW_PASSES, configs):
+        if config is not None and not hasattr(engine, setter):
+            raise RuntimeError("afterqc_amd: %s need an engine with %s; %s has none" % (options, setter, type(engine).__name__))
+        if config is not None or (clear and hasattr(engine, setter)):
+            getattr(engine, setter)(config)
 
 
 def build_config(opt, paired, has_index2):
@@ -461,10 +460,7 @@ class seqFilter:
                 e = capi.Engine(d, max(2, self.pipe_slots))
                 e.set_config(cfg)
                 e.set_circles(circles)
-                if self.cut is not None:
-                    set_cut(e, self.cut)
-                if self.adapter is not None:
-                    set_adapter(e, self.adapter)
+                set_view_passes(e, (self.cut, self.adapter))
                 e.reset_stats()
                 self.extra_engines.append(e)
         return [eng] + self.extra_engines
@@ -534,14 +530,7 @@ class seqFilter:
         self._last_cfg = (build_config(opt, self.paired, opt.index2_file is not None), self.bubbleCircles)
         for e in self._engines():
             e.set_config(self._last_cfg[0])
-            if self.cut is not None:
-                set_cut(e, self.cut)
-            elif hasattr(e, "set_quality_cut"):
-                e.set_quality_cut(None)          # (an engine the caller handed over may come from a run that had the cut on)
-            if self.adapter is not None:
-                set_adapter(e, self.adapter)
-            elif hasattr(e, "set_adapter_trim"):
-                e.set_adapter_trim(None)
+            set_view_passes(e, (self.cut, self.adapter), clear=True)
             if first:
                 e.set_circles(self.bubbleCircles)
                 e.reset_stats()

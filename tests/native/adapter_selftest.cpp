@@ -21,14 +21,14 @@ static int group_first(const uint8_t* read, int n, const AdapterOpts& a) {
     std::vector<uint32_t> row(CAP / 4 + ADP_ROW_TAIL, 0xA5A5A5A5u);
     for (int j = 0; j < ADP_ROW_TAIL; ++j) row[CAP / 4 + j] = 0u;        // (the kernel clears the words behind the row once)
     for (int g = 0; g < G; ++g) {
-        const int nvalid = qcut_min(qcut_max(n - 16 * g, 0), 16);
+        const int nvalid = vp_nvalid(n, g);
         uint32_t d[4] = {0, 0, 0, 0};
         if (nvalid > 0) memcpy(d, read + 16 * g, 16);                    // (a whole 16-byte load: the padding is read)
         adp_keep16(d, nvalid);
         memcpy(row.data() + 4 * g, d, 16);
     }
     int p = ADP_NONE;
-    for (int g = 0; g < G; ++g) p = qcut_min(p, adp_lane_first<G>(row.data(), n, a.w[0], a.len[0], a.min_overlap, g));
+    for (int g = 0; g < G; ++g) p = vp_min(p, adp_lane_first<G>(row.data(), n, a.w[0], a.len[0], a.min_overlap, g));
     return p;
 }
 
@@ -65,10 +65,10 @@ int main(int argc, char** argv) {
         } else if (buf[0] == 'V') {
             int c0, c1, p, o0, o1;
             if (sscanf(buf, "V %d %d %d %d %d", &c0, &c1, &p, &o0, &o1) != 5) { fprintf(stderr, "bad line: %s", buf); return 2; }
-            const uint32_t v = adp_view((uint32_t)c0 | ((uint32_t)c1 << 16), p < 0 ? ADP_NONE : p);
+            const uint32_t v = adp_view(view_word(c0, c1), p < 0 ? ADP_NONE : p);
             ++views;
-            if ((int)(v & 0xffffu) != o0 || (int)(v >> 16) != o1) {
-                if (++failed <= 20) printf("FAIL view: %s got %u %u\n", buf, v & 0xffffu, v >> 16);
+            if (view_c0(v) != o0 || view_c1(v) != o1) {
+                if (++failed <= 20) printf("FAIL view: %s got %d %d\n", buf, view_c0(v), view_c1(v));
             }
         } else if (buf[0] == 'M') {
             unsigned x;

@@ -23,7 +23,7 @@ static uint32_t group_view(const std::vector<uint8_t>& line, int n, const QcutOp
     std::vector<int> total(G, 0);
     std::vector<std::vector<int>> p(G, std::vector<int>(16, 0));
     for (int g = 0; g < G; ++g) {
-        const int nvalid = qcut_min(qcut_max(n - 16 * g, 0), 16);
+        const int nvalid = vp_nvalid(n, g);
         uint32_t d[4] = {0, 0, 0, 0};
         if (nvalid > 0) memcpy(d, line.data() + 16 * g, 16);          // (a whole 16-byte load: the padding is read)
         qcut_sum16(d[0], d[1], d[2], d[3], nvalid, p[g].data());
@@ -41,12 +41,12 @@ static uint32_t group_view(const std::vector<uint8_t>& line, int n, const QcutOp
     for (int g = 0; g < G; ++g) bits[g] = qcut_lane_bits(P, n, w, thr, g, G, passes);
     int first_good = QCUT_NONE, last_good = -1;
     for (int g = 0; g < G; ++g) {
-        first_good = qcut_min(first_good, qcut_lane_first(bits[g] >> 16, g, G, 0));
-        last_good = qcut_max(last_good, qcut_lane_last(bits[g] >> 16, g, G));
+        first_good = vp_min(first_good, qcut_lane_first(bits[g] >> 16, g, G, 0));
+        last_good = vp_max(last_good, qcut_lane_last(bits[g] >> 16, g, G));
     }
     const int c0 = first_good == QCUT_NONE ? 0 : qcut_front(o, first_good);
     int first_bad = QCUT_NONE;
-    for (int g = 0; g < G; ++g) first_bad = qcut_min(first_bad, qcut_lane_first((bits[g] & 0xffffu) & ~(bits[g] >> 16), g, G, c0));
+    for (int g = 0; g < G; ++g) first_bad = vp_min(first_bad, qcut_lane_first((bits[g] & 0xffffu) & ~(bits[g] >> 16), g, G, c0));
     return qcut_view(o, n, w, first_good, last_good, first_bad);
 }
 
@@ -74,15 +74,15 @@ int main(int argc, char** argv) {
                 if (n > 16 * G) continue;
                 const uint32_t view = group_view(line, n, o, G);
                 ++windows;
-                if ((int)(view & 0xffffu) != c0 || (int)(view >> 16) != c1) {
-                    if (++failed <= 20) printf("FAIL G=%d: %.60s ... got %u %u want %d %d\n", G, buf, view & 0xffffu, view >> 16, c0, c1);
+                if (view_c0(view) != c0 || view_c1(view) != c1) {
+                    if (++failed <= 20) printf("FAIL G=%d: %.60s ... got %d %d want %d %d\n", G, buf, view_c0(view), view_c1(view), c0, c1);
                 }
             }
         } else if (buf[0] == 'S') {
             int len, tf, tt, c0, c1, st, nl;
             if (sscanf(buf, "S %d %d %d %d %d %d %d", &len, &tf, &tt, &c0, &c1, &st, &nl) != 7) { fprintf(stderr, "bad line: %s", buf); return 2; }
             int a = 7, l = len;                     // (a view that already starts 7 bytes in: the function moves it)
-            qcut_apply(a, l, tf, tt, (uint32_t)c0 | ((uint32_t)c1 << 16));
+            view_apply(a, l, tf, tt, view_word(c0, c1));
             ++slices;
             if (l != nl || (nl > 0 && a != 7 + st)) {
                 if (++failed <= 20) printf("FAIL slice: %s got %d %d\n", buf, a - 7, l);

@@ -29,13 +29,13 @@ for _p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golde
 
 import adapter_rule
 import cut_rule
-import test_gpu_qcut as tq
+import viewpass_cases as vc
 from afterqc_amd import after, capi, preprocesser
 
 pytestmark = pytest.mark.gpu
 
-ERR_UNSUPPORTED, ERR_READ_TOO_LONG = -7, -3
-GROUP_LENGTHS, GROUP_RANGE = tq.GROUP_LENGTHS, tq.GROUP_RANGE
+ERR_UNSUPPORTED, ERR_READ_TOO_LONG = vc.ERR_UNSUPPORTED, -3
+GROUP_LENGTHS, GROUP_RANGE = vc.GROUP_LENGTHS, vc.GROUP_RANGE
 SEAM_ADAPTER_LENGTHS = [4, 8, 9, 17, 33, 64]
 A1 = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"          # 33 bases
 A2 = b"CTGTCTCTTATACACATCT"                        # 19
@@ -58,7 +58,7 @@ def test_seam_against_the_model(m, G, gpu_engine):
     A = adapter_rule.make_adapter(rng, m)
     for K in sorted({1, 4, m}):
         reads = [s for n in GROUP_LENGTHS[G] for _, s in adapter_rule.placements(n, A, K, rng)]
-        batch = tq.pack(reads, [b"I" * len(s) for s in reads])
+        batch = vc.pack(reads, [b"I" * len(s) for s in reads])
         assert batch.qlen1 is None and GROUP_RANGE[G][0] <= batch.max_len() <= GROUP_RANGE[G][1]
         got = views(*gpu_engine.adapter_views(batch, adcfg(A, b"", K)))
         want = [adapter_rule.compose(adapter_rule.VIEW_ALL, s, A, K) for s in reads]
@@ -85,7 +85,7 @@ def test_seam_fixed_trim_irregular_lines_and_an_incoming_view(trim, gpu_engine):
            for i, c0 in enumerate(rng.choice([0, 0, 1, 3, 9, 29, 100, 149, 150, 151, 400]) for _ in range(600))]
     arrays = (np.array([v[0] for v in vin]), np.array([v[1] for v in vin]))
     for irregular in (True, False):
-        batch = tq.pack(seqs, quals if irregular else [b"I" * 150] * 600)
+        batch = vc.pack(seqs, quals if irregular else [b"I" * 150] * 600)
         assert (batch.qlen1 is not None) == irregular
         for K, a in ((4, A1), (1, A1[:9])):
             got = views(*gpu_engine.adapter_views(batch, adcfg(a, b"", K), trim[0], trim[1]))
@@ -95,7 +95,7 @@ def test_seam_fixed_trim_irregular_lines_and_an_incoming_view(trim, gpu_engine):
 
 
 def test_seam_refuses_bad_options_and_long_reads(gpu_engine):
-    batch = tq.pack([b"ACGTACGTAC"], [b"IIIIIIIIII"])
+    batch = vc.pack([b"ACGTACGTAC"], [b"IIIIIIIIII"])
     for a, K in ((b"ACG", 1), (b"A" * 65, 4), (b"ACGN", 4), (b"acgt", 4), (b"ACGT", 0), (b"ACGT", 5)):
         with pytest.raises(capi.AqcError) as e:
             gpu_engine.adapter_views(batch, adcfg(a, b"", K))
@@ -110,31 +110,18 @@ def test_seam_refuses_bad_options_and_long_reads(gpu_engine):
     gpu_engine.set_adapter_trim(None)
     long_read = adapter_rule.bases(random.Random(1), 1001)
     with pytest.raises(capi.AqcError) as e:
-        gpu_engine.adapter_views(tq.pack([b"ACGT", long_read], [b"IIII", b"I" * 1001]), adcfg(b"ACGT"))
+        gpu_engine.adapter_views(vc.pack([b"ACGT", long_read], [b"IIII", b"I" * 1001]), adcfg(b"ACGT"))
     assert e.value.code == ERR_READ_TOO_LONG
 
 
 # ---- verdicts: the adapter on against a run on the pre-cut records --------------------------------------------------------------
 def adapter_pairs(n, L, seed, a1, a2, short=()):
-    """tq.tailed_pairs with adapters written over 30 % of the mates (adapter_rule.with_adapters: from place 20 on, a third of
+    """vc.tailed_pairs with adapters written over 30 % of the mates (adapter_rule.with_adapters: from place 20 on, a third of
     them 4 .. 20 adapter bases at the very end, some bases substituted)"""
-    return adapter_rule.with_adapters(random.Random(seed), tq.tailed_pairs(n, L, seed, short), a1, a2)
+    return adapter_rule.with_adapters(random.Random(seed), vc.tailed_pairs(n, L, seed, short), a1, a2)
 
 
-def run_pairs(eng, pairs, paired, cfg, cut, adapter, slot=0, accum_limit=capi.UINT64_MAX):
-    """one upload + run -> what the comparison looks at (tq.run_pairs with the adapter set as well)"""
-    batch = tq.pack([p[0] for p in pairs], [p[1] for p in pairs], [p[2] for p in pairs] if paired else None, [p[3] for p in pairs] if paired else None)
-    eng.set_config(cfg)
-    eng.set_quality_cut(cut)
-    eng.set_adapter_trim(adapter)
-    eng.reset_stats()
-    eng.upload(slot, batch)
-    eng.run(slot, accum_limit)
-    res = eng.fetch_results(slot)
-    qv = [eng.fetch_quality_views(slot, m) for m in ((0, 1) if paired else (0,))]
-    ovl, dist = eng.histograms()
-    return dict(res=res, qv=qv, counters=eng.counters(), ovl=ovl, dist=dist, words=eng.last_verdict_words(slot), deferred=eng.last_deferred(slot),
-                cut_ms=eng.cut_ms(slot), cut_stats=eng.cut_stats(), adapter_ms=eng.adapter_ms(slot), adapter_stats=eng.adapter_stats())
+run_pairs = vc.run_pairs
 
 
 def model_of(a1, a2, K, modes=None, trim=(0, 0)):
@@ -153,11 +140,11 @@ def check_against_precut(eng, pairs, paired, trim, a1, a2, K, words):
         model = model_of(a1, a2, K, modes, trim)
         pre = adapter_rule.precut_pairs(pairs, model, paired)
         assert min(len(p[0]) for p in pre) >= 5 and (not paired or min(len(p[2]) for p in pre) >= 5)
-        A = run_pairs(eng, pairs, paired, tq.base_config(paired, trim), tq.cutcfg(modes) if modes else None, adcfg(a1, a2 if paired else b"", K))
-        B = run_pairs(eng, pre, paired, tq.base_config(paired), None, None)
+        A = run_pairs(eng, pairs, paired, vc.base_config(paired, trim), vc.cutcfg(modes) if modes else None, adcfg(a1, a2 if paired else b"", K))
+        B = run_pairs(eng, pre, paired, vc.base_config(paired), None, None)
         assert A["words"] == words
         assert A["adapter_ms"] > 0 and B["adapter_ms"] == 0 and (A["cut_ms"] > 0) == bool(modes)
-        tq.compare_runs(pairs, pre, A, B, paired)
+        vc.compare_runs(pairs, pre, A, B, paired)
         want = adapter_rule.adapter_counts(se(pairs, paired), model)
         assert A["adapter_stats"].tolist() == want and want[0] > len(pairs) // 8
         # the quality cut's own counts are what they are without the adapter
@@ -187,9 +174,9 @@ def test_only_read_2_is_searched(gpu_engine):
     model = model_of(b"", A2, 5)
     pre = adapter_rule.precut_pairs(pairs, model, True)
     assert all(p[0] == q[0] for p, q in zip(pairs, pre)) and sum(1 for p, q in zip(pairs, pre) if p[2] != q[2]) > 100
-    A = run_pairs(gpu_engine, pairs, True, tq.base_config(True), None, adcfg(b"", A2, 5))
-    B = run_pairs(gpu_engine, pre, True, tq.base_config(True), None, None)
-    tq.compare_runs(pairs, pre, A, B, True)
+    A = run_pairs(gpu_engine, pairs, True, vc.base_config(True), None, adcfg(b"", A2, 5))
+    B = run_pairs(gpu_engine, pre, True, vc.base_config(True), None, None)
+    vc.compare_runs(pairs, pre, A, B, True)
     want = adapter_rule.adapter_counts(pairs, model)
     assert A["adapter_stats"].tolist() == want and want[:2] == [0, 0] and want[2] > 100
 
@@ -210,7 +197,7 @@ def sub5_pairs(n=400, L=150, seed=5):
 def test_reads_trimmed_below_five_bases(gpu_engine):
     pairs = sub5_pairs()
     model = model_of(A1, A2, 4)
-    A = run_pairs(gpu_engine, pairs, True, tq.base_config(True), None, adcfg(A1, A2, 4), accum_limit=300)
+    A = run_pairs(gpu_engine, pairs, True, vc.base_config(True), None, adcfg(A1, A2, 4), accum_limit=300)
     gpu_engine.set_adapter_trim(None)
     n1 = n2 = 0
     for p, r in zip(pairs, A["res"]):
@@ -236,11 +223,11 @@ def test_bad_file_text_of_reads_trimmed_below_five_bases(gpu_engine):
     """text in, text out: every record goes to the bad streams as @BADTRIM1... / @BADTRIM2..., read 1 trimmed, read 2 only under BADTRIM2"""
     pairs = sub5_pairs(300, 150, 6)
     model = model_of(A1, A2, 4)
-    gpu_engine.set_config(tq.base_config(True))
+    gpu_engine.set_config(vc.base_config(True))
     gpu_engine.set_quality_cut(None)
     gpu_engine.set_adapter_trim(adcfg(A1, A2, 4))
     gpu_engine.reset_stats()
-    t = [tq.fastq_text(pairs, 0), tq.fastq_text(pairs, 1)]
+    t = [vc.fastq_text(pairs, 0), vc.fastq_text(pairs, 1)]
     pad = lambda b: np.frombuffer(b + b"\0" * 4096, dtype=np.uint8).copy()
     info = gpu_engine.frame(1, pad(t[0]), len(t[0]), True, pad(t[1]), len(t[1]), True)
     assert int(info.n) == len(pairs)
@@ -270,19 +257,19 @@ def test_adapter_stats_over_two_contexts_with_a_cut_on(gpu_engine):
     model = model_of(A1, A2, 4, modes)
     other = capi.Engine(0, 2)
     try:
-        a = run_pairs(gpu_engine, pairs[:350], True, tq.base_config(True), tq.cutcfg(modes), adcfg(A1, A2, 4))
-        b = run_pairs(other, pairs[350:], True, tq.base_config(True), tq.cutcfg(modes), adcfg(A1, A2, 4))
+        a = run_pairs(gpu_engine, pairs[:350], True, vc.base_config(True), vc.cutcfg(modes), adcfg(A1, A2, 4))
+        b = run_pairs(other, pairs[350:], True, vc.base_config(True), vc.cutcfg(modes), adcfg(A1, A2, 4))
         both = capi.MergedEngines([gpu_engine, other])
         merged, merged_cut = both.adapter_stats().tolist(), both.cut_stats().tolist()
         assert merged == adapter_rule.adapter_counts(pairs, model) and merged[0] > 50 and merged[2] > 50
         assert (a["adapter_stats"] + b["adapter_stats"]).tolist() == merged
         # the quality cut's counts of the same run: those of a run without the adapter
-        c = run_pairs(gpu_engine, pairs[:350], True, tq.base_config(True), tq.cutcfg(modes), None)
-        d = run_pairs(other, pairs[350:], True, tq.base_config(True), tq.cutcfg(modes), None)
+        c = run_pairs(gpu_engine, pairs[:350], True, vc.base_config(True), vc.cutcfg(modes), None)
+        d = run_pairs(other, pairs[350:], True, vc.base_config(True), vc.cutcfg(modes), None)
         assert merged_cut == (c["cut_stats"] + d["cut_stats"]).tolist() == cut_rule.cut_counts(pairs, model.cut)
         assert c["adapter_stats"].tolist() == [0, 0, 0, 0] and c["adapter_ms"] == 0
         # an accum_limit
-        e = run_pairs(gpu_engine, pairs, True, tq.base_config(True), tq.cutcfg(modes), adcfg(A1, A2, 4), accum_limit=211)
+        e = run_pairs(gpu_engine, pairs, True, vc.base_config(True), vc.cutcfg(modes), adcfg(A1, A2, 4), accum_limit=211)
         assert e["adapter_stats"].tolist() == adapter_rule.adapter_counts(pairs, model, accum_limit=211)
         gpu_engine.reset_stats()
         assert gpu_engine.adapter_stats().tolist() == [0, 0, 0, 0]
@@ -295,7 +282,7 @@ def test_adapter_stats_over_two_contexts_with_a_cut_on(gpu_engine):
 # ---- off is off -------------------------------------------------------------------------------------------------------------
 def test_off_after_an_adapter_run_is_the_run_without_it(gpu_engine):
     pairs = adapter_pairs(1200, 150, 44, A1, A2)
-    cfg = tq.base_config(True, (2, 3))
+    cfg = vc.base_config(True, (2, 3))
     fresh = capi.Engine(0, 2)
     try:
         want = run_pairs(fresh, pairs, True, cfg, None, None)          # a context that never had an adapter
@@ -311,8 +298,8 @@ def test_off_after_an_adapter_run_is_the_run_without_it(gpu_engine):
 
 
 def test_barcode_with_an_adapter_is_unsupported(gpu_engine):
-    pairs = tq.tailed_pairs(64, 150, 3)
-    cfg = tq.base_config(True)
+    pairs = vc.tailed_pairs(64, 150, 3)
+    cfg = vc.base_config(True)
     cfg.barcode = 1
     with pytest.raises(capi.AqcError) as e:
         run_pairs(gpu_engine, pairs, True, cfg, None, adcfg(A1, A2, 4))
@@ -379,20 +366,20 @@ def test_cli_equals_a_run_on_precut_files(name, tmp_path, gpu_engine):
     pre = adapter_rule.precut_pairs(pairs, model, paired)
     assert min(len(p[0]) for p in pre) >= 5 and (not paired or min(len(p[2]) for p in pre) >= 5)
     assert any(len(p[0]) != len(p[1]) for p in pairs)
-    kw = tq.thg.MODES[driver] if driver in tq.thg.MODES else tq.thg.PIPE_MODES[driver]
+    kw = vc.driver_kw(driver)
     work = [os.path.join(str(tmp_path), "a"), os.path.join(str(tmp_path), "b")]
-    fa = tq.write_inputs(work[0], "raw", pairs, paired, gz, index)
-    fb = tq.write_inputs(work[1], "pre", [p if paired else (p[0], p[1], b"", b"") for p in pre], paired, gz, index)
+    fa = vc.write_inputs(work[0], "raw", pairs, paired, gz, index)
+    fb = vc.write_inputs(work[1], "pre", [p if paired else (p[0], p[1], b"", b"") for p in pre], paired, gz, index)
     extra = []
     if "--debubble" in argv_on:
         with open(os.path.join(str(tmp_path), "circles.csv"), "w") as f:
             f.write("x,y,radius,lane,tile\n1100,2100,30,1,101\n")
         extra = ["--debubble_dir", str(tmp_path)]
-    sa, pipe_a = tq.run_cli(work[0], fa, paired, ["-f", str(trim[0]), "-t", str(trim[1]), "--adapter_sequence", A1.decode().lower()] + argv_on + extra, kw, gpu_engine, index)
-    sb, pipe_b = tq.run_cli(work[1], fb, paired, ["-f", "0", "-t", "0"] + argv_pre + extra, kw, gpu_engine, index)
+    sa, pipe_a = vc.run_cli(work[0], fa, paired, ["-f", str(trim[0]), "-t", str(trim[1]), "--adapter_sequence", A1.decode().lower()] + argv_on + extra, kw, gpu_engine, index)
+    sb, pipe_b = vc.run_cli(work[1], fb, paired, ["-f", "0", "-t", "0"] + argv_pre + extra, kw, gpu_engine, index)
     # the driver the case names is the driver that ran: no quiet fall-back to the serial loop with the adapter on
     assert pipe_a == pipe_b == name.startswith("pipe_"), (pipe_a, pipe_b)
-    oa, ob = tq.read_outputs(work[0]), tq.read_outputs(work[1])
+    oa, ob = vc.read_outputs(work[0]), vc.read_outputs(work[1])
     assert sorted(oa) == sorted(ob)
     if "--qc_only" in argv_on:
         assert not oa
@@ -416,7 +403,7 @@ def test_cli_equals_a_run_on_precut_files(name, tmp_path, gpu_engine):
     assert (at["adapter_sequence"], at["adapter_sequence_r2"], at["adapter_min_overlap"]) == (A1.decode(), a2.decode() if paired else "", K)
     if "--cut_tail" in argv_on:
         # the same bytes as the same run without the adapter options
-        sc, _ = tq.run_cli(os.path.join(str(tmp_path), "c"), fa, paired, ["-f", str(trim[0]), "-t", str(trim[1])] + argv_on, kw, gpu_engine, index)
+        sc, _ = vc.run_cli(os.path.join(str(tmp_path), "c"), fa, paired, ["-f", str(trim[0]), "-t", str(trim[1])] + argv_on, kw, gpu_engine, index)
         assert json.dumps(sa["quality_cut"], sort_keys=True) == json.dumps(sc["quality_cut"], sort_keys=True)
         assert sa["quality_cut"]["read1_cut_reads"] > 100
     assert sorted(k for k in sa if k not in ("adapter_trim", "quality_cut")) == sorted(sb)
@@ -446,12 +433,12 @@ def test_folder_mode_with_debubble(tmp_path):
     stats = []
     for tag, recs, extra in (("raw", pairs, ["--adapter_sequence", A1.decode()]), ("pre", pre, [])):
         work = os.path.join(str(tmp_path), tag)
-        tq.write_inputs(os.path.join(work, "in"), tag, recs, True, "")
+        vc.write_inputs(os.path.join(work, "in"), tag, recs, True, "")
         after.main(["-d", os.path.join(work, "in"), "--debubble", "--debubble_dir", bubbles, "-f", "0", "-t", "0", "--qc_sample", "0", "--barcode", "off",
                     "-g", os.path.join(work, "good"), "-b", os.path.join(work, "bad"), "-r", os.path.join(work, "QC")] + extra)
         with open(os.path.join(work, "QC", "%s_R1.fq.json" % tag)) as f:
             stats.append(json.load(f))
-    oa, ob = tq.read_outputs(os.path.join(str(tmp_path), "raw")), tq.read_outputs(os.path.join(str(tmp_path), "pre"))
+    oa, ob = vc.read_outputs(os.path.join(str(tmp_path), "raw")), vc.read_outputs(os.path.join(str(tmp_path), "pre"))
     assert sorted(oa) == sorted(ob) and any(k.startswith("good/") and oa[k] for k in oa) and any(k.startswith("bad/") and oa[k] for k in oa)
     for k in oa:
         assert oa[k] == ob[k], k
@@ -465,8 +452,8 @@ def test_folder_mode_with_debubble(tmp_path):
 
 
 def test_cli_refuses_barcoded_input(tmp_path, gpu_engine):
-    pairs = tq.tailed_pairs(64, 150, 3)
-    files = tq.write_inputs(str(tmp_path), "raw", pairs, True, "")
+    pairs = vc.tailed_pairs(64, 150, 3)
+    files = vc.write_inputs(str(tmp_path), "raw", pairs, True, "")
     options, _ = after.parseCommand(["-1", files[0], "-2", files[1], "-g", os.path.join(str(tmp_path), "good"), "--adapter_sequence", A1.decode()])
     after.finalize_options(options)
     options.barcode = True

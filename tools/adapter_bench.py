@@ -20,10 +20,10 @@ Results: profiles/r17_adapter.txt."""
 import argparse
 import os
 import sys
-import time
+
+import viewpass_bench as vb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PEAK = 8.0e12          # HBM_PEAK_GBS of bench.py
 A1 = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"
 A2 = b"AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT"
 LOADS = {"se150": (150, False), "pe150": (150, True), "pe300": (300, True)}
@@ -53,18 +53,6 @@ def make_input(n, L, frac=0.3):
     return d
 
 
-def config(paired):
-    from afterqc_amd import capi
-    cfg = capi.Config()
-    cfg.paired = 1 if paired else 0
-    cfg.seq_len_req, cfg.poly_size_limit, cfg.allow_mismatch_in_poly = 35, 35, 2
-    cfg.qualified_quality_phred, cfg.unqualified_base_limit, cfg.n_base_limit = 15, 60, 5
-    cfg.barcode_length = 12
-    cfg.set_verify("CAGTA")
-    cfg.qc_kmer = 8
-    return cfg
-
-
 def batch_of(d, paired):
     from afterqc_amd import capi
     if paired:
@@ -87,29 +75,12 @@ def kernels(a):
         batch = batch_of(make_input(a.records, L), paired)
         engines = (("plain", plain), ("adapter", adp))
         for tag, eng in engines:
-            eng.set_config(config(paired))
+            eng.set_config(vb.base_config(paired))
             eng.set_adapter_trim(capi.AdapterConfig(A1, A2 if paired else b"", 4) if tag == "adapter" else None)
             eng.reset_stats()
             eng.upload(0, batch)
-        ms, ams = {}, []
-        for k in range(a.warmup + a.reps):
-            for tag, eng in engines:
-                eng.timing_reset(0)
-                eng.run(0)
-                t, cnt = eng.timing_mean(0)
-                assert cnt[capi.K_FILTER_OVERLAP] == 1
-                if k >= a.warmup:
-                    ms.setdefault(tag, []).append(float(t[capi.K_FILTER_OVERLAP]))
-                    if tag == "adapter":
-                        ams.append(eng.adapter_ms(0))
-        for tag, eng in engines:
-            v = np.array(ms[tag])
-            row = "  %-6s %-8s %5d %10.4f %9.4f %7.3f %9.5f" % (load, tag, eng.last_verdict_words(0), float(np.median(v)), float(v.min()), float(v.max() / v.min()),
-                                                               eng.last_deferred(0) / batch.n)
-            if tag == "adapter":
-                c = np.array(ams)
-                row += " | %10.4f %9.4f %8.4f" % (float(np.median(c)), float(c.min()), moved_bytes(L, paired, batch.n) / (float(np.median(c)) * 1e-3) / PEAK)
-            print(row, flush=True)
+        ms, ams = vb.alternate(engines, a, "adapter", lambda eng: eng.adapter_ms(0))
+        vb.verdict_rows(engines, ms, ams, "adapter", load, batch.n, moved_bytes(L, paired, batch.n), 8, 10)
         st = adp.adapter_stats() // (a.warmup + a.reps)
         print("  %-6s the CUT instance takes %.3f x the plain instance's time (medians); adapter pass + CUT instance %.4f ms against %.4f ms; reads trimmed %d + %d of %d records, bases %d + %d"
               % (load, float(np.median(ms["adapter"]) / np.median(ms["plain"])), float(np.median(ms["adapter"]) + np.median(ams)), float(np.median(ms["plain"])),
@@ -126,7 +97,7 @@ def early_exit(a):
     print("# adapter_bench exit on %s: %d pairs of 2 x 150, the adapter pass (aqc_adapter_ms), %d warm-up + %d timed aqc_run" % (eng.device_name(), a.records, a.warmup, a.reps), flush=True)
     for frac in (0.0, 0.3, 1.0):
         batch = batch_of(make_input(a.records, L, frac), paired)
-        eng.set_config(config(paired))
+        eng.set_config(vb.base_config(paired))
         eng.set_adapter_trim(capi.AdapterConfig(A1, A2, 4))
         eng.reset_stats()
         eng.upload(0, batch)
@@ -138,42 +109,21 @@ def early_exit(a):
         st = eng.adapter_stats() // (a.warmup + a.reps)
         v = np.array(t)
         print("  adapter in %3d %% of the reads: adapter_ms median %.4f min %.4f  of_peak %.4f  reads trimmed %d + %d"
-              % (round(100 * frac), float(np.median(v)), float(v.min()), moved_bytes(L, paired, batch.n) / (float(np.median(v)) * 1e-3) / PEAK, int(st[0]), int(st[2])), flush=True)
+              % (round(100 * frac), float(np.median(v)), float(v.min()), vb.of_peak(moved_bytes(L, paired, batch.n), float(np.median(v))), int(st[0]), int(st[2])), flush=True)
     eng.close()
 
 
 def step(a):
-    import numpy as np
-    from afterqc_amd import capi, synth
+    from afterqc_amd import capi
     eng = capi.Engine(0, 2)
     label = "this adapter" if a.adapter else "this"
     for L in (150, 300):
         d = make_input(a.records, L)
-        n_rec = len(d["len1"])
-        eng.set_config(config(True))
+        eng.set_config(vb.base_config())
         eng.set_adapter_trim(capi.AdapterConfig(A1, A2, 4) if a.adapter else None)
         eng.reset_stats()
-        w = synth.fixed_record_width(L)
-        texts = []
-        for mate in (1, 2):
-            hb = eng.host_buffer(n_rec * w + 4096)
-            _, nbytes = synth.render_fastq_fixed(d["seq%d" % mate], d["qual%d" % mate], mate, out=hb.array)
-            texts.append((hb, nbytes))
-        info = eng.frame(0, texts[0][0].array, texts[0][1], True, texts[1][0].array, texts[1][1], True)
-        assert int(info.n) == n_rec
-        t = []
-        for k in range(a.warmup + a.reps):
-            eng.sync(0)
-            t0 = time.perf_counter()
-            eng.reframe(0)
-            eng.run(0)
-            sizes = eng.format(0, n_rec, False)
-            eng.sync(0)
-            if k >= a.warmup:
-                t.append(1000.0 * (time.perf_counter() - t0))
-        v = np.array(t)
-        print("%-16s pe%-4d device_step ms min %.4f median %.4f max %.4f  good bytes %d  adapter_ms %.4f" % (label, L, float(v.min()), float(np.median(v)), float(v.max()),
-                                                                                                         int(sizes[0] + sizes[3]), eng.adapter_ms(0)), flush=True)
+        v, sizes, _ = vb.device_step(eng, d, L, a)
+        print("%s  adapter_ms %.4f" % (vb.step_line(label, L, v, sizes), eng.adapter_ms(0)), flush=True)
     eng.close()
 
 
@@ -181,7 +131,7 @@ def once(a):
     from afterqc_amd import capi
     L, paired = LOADS[a.load]
     eng = capi.Engine(0, 1)
-    eng.set_config(config(paired))
+    eng.set_config(vb.base_config(paired))
     eng.set_adapter_trim(capi.AdapterConfig(A1, A2 if paired else b"", 4))
     eng.reset_stats()
     eng.upload(0, batch_of(make_input(a.records, L), paired))

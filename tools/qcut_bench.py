@@ -18,8 +18,9 @@ import os
 import sys
 import time
 
+import viewpass_bench as vb
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PEAK = 8.0e12          # HBM_PEAK_GBS of bench.py
 
 
 def make_input(n, L):
@@ -37,20 +38,6 @@ def make_input(n, L):
     return d
 
 
-def config(trim=(0, 0)):
-    from afterqc_amd import capi
-    cfg = capi.Config()
-    cfg.paired = 1
-    cfg.seq_len_req, cfg.poly_size_limit, cfg.allow_mismatch_in_poly = 35, 35, 2
-    cfg.qualified_quality_phred, cfg.unqualified_base_limit, cfg.n_base_limit = 15, 60, 5
-    cfg.barcode_length = 12
-    cfg.set_verify("CAGTA")
-    cfg.qc_kmer = 8
-    cfg.trim_front = cfg.trim_front2 = trim[0]
-    cfg.trim_tail = cfg.trim_tail2 = trim[1]
-    return cfg
-
-
 def kernels(a):
     import numpy as np
     from afterqc_amd import capi
@@ -63,30 +50,12 @@ def kernels(a):
         batch = capi.Batch.from_matrices(d["seq1"], d["qual1"], d["len1"], d["seq2"], d["qual2"], d["len2"])
         engines = (("plain", plain), ("cut", cut))
         for tag, eng in engines:
-            eng.set_config(config((2, 3)))
+            eng.set_config(vb.base_config(trim=(2, 3)))
             eng.set_quality_cut(capi.CutConfig(0, 1, 0, 4, 20) if tag == "cut" else None)
             eng.reset_stats()
             eng.upload(0, batch)
-        ms, cms = {}, []
-        for k in range(a.warmup + a.reps):
-            for tag, eng in engines:
-                eng.timing_reset(0)
-                eng.run(0)
-                t, cnt = eng.timing_mean(0)
-                assert cnt[capi.K_FILTER_OVERLAP] == 1
-                if k >= a.warmup:
-                    ms.setdefault(tag, []).append(float(t[capi.K_FILTER_OVERLAP]))
-                    if tag == "cut":
-                        cms.append(eng.cut_ms(0))
-        for tag, eng in engines:
-            v = np.array(ms[tag])
-            row = "  pe%-4d %-6s %5d %10.4f %9.4f %7.3f %9.5f" % (L, tag, eng.last_verdict_words(0), float(np.median(v)), float(v.min()), float(v.max() / v.min()),
-                                                                 eng.last_deferred(0) / batch.n)
-            if tag == "cut":
-                c = np.array(cms)
-                moved = (2 * L + 8) * batch.n
-                row += " | %9.4f %9.4f %8.4f" % (float(np.median(c)), float(c.min()), moved / (float(np.median(c)) * 1e-3) / PEAK)
-            print(row, flush=True)
+        ms, cms = vb.alternate(engines, a, "cut", lambda eng: eng.cut_ms(0))
+        vb.verdict_rows(engines, ms, cms, "cut", "pe%d" % L, batch.n, (2 * L + 8) * batch.n, 6, 9)
         st = cut.cut_stats()
         print("  pe%-4d the CUT instance takes %.3f x the plain instance's time (medians); cut pass + CUT instance %.4f ms against %.4f ms; reads cut %d + %d of %d pairs, bases %d + %d"
               % (L, float(np.median(ms["cut"]) / np.median(ms["plain"])), float(np.median(ms["cut"]) + np.median(cms)), float(np.median(ms["plain"])),
@@ -98,34 +67,16 @@ def kernels(a):
 def step(a):
     sys.path.insert(0, os.path.abspath(a.tree) if a.tree else ROOT)
     import numpy as np
-    from afterqc_amd import capi, synth
+    from afterqc_amd import capi
     eng = capi.Engine(0, 2)
     label = ("parent" if a.tree else "this") + (" cut_tail" if a.cut_tail else "")
     for L in (150, 300):
         d = make_input(a.pairs, L)
-        n_rec = len(d["len1"])
-        eng.set_config(config())
+        eng.set_config(vb.base_config())
         if a.cut_tail:
             eng.set_quality_cut(capi.CutConfig(0, 1, 0, 4, 20))
         eng.reset_stats()
-        w = synth.fixed_record_width(L)
-        texts = []
-        for mate in (1, 2):
-            hb = eng.host_buffer(n_rec * w + 4096)
-            _, nbytes = synth.render_fastq_fixed(d["seq%d" % mate], d["qual%d" % mate], mate, out=hb.array)
-            texts.append((hb, nbytes))
-        info = eng.frame(0, texts[0][0].array, texts[0][1], True, texts[1][0].array, texts[1][1], True)
-        assert int(info.n) == n_rec
-        t = []
-        for k in range(a.warmup + a.reps):
-            eng.sync(0)
-            t0 = time.perf_counter()
-            eng.reframe(0)
-            eng.run(0)
-            sizes = eng.format(0, n_rec, False)
-            eng.sync(0)
-            if k >= a.warmup:
-                t.append(1000.0 * (time.perf_counter() - t0))
+        v, sizes, n_rec = vb.device_step(eng, d, L, a)
         if a.detail:
             # where a step's time goes: each call synced on its own, and the verdict kernel by its HIP events
             parts = {"reframe": [], "run": [], "format": [], "verdict_kernel": []}
@@ -137,8 +88,7 @@ def step(a):
                     parts[name].append(1000.0 * (time.perf_counter() - t0))
                 parts["verdict_kernel"].append(float(eng.kernel_ms(0)[capi.K_FILTER_OVERLAP]))
             print("%-16s pe%-4d medians, each call synced: %s" % (label, L, "  ".join("%s %.4f" % (k, float(np.median(v))) for k, v in parts.items())), flush=True)
-        v = np.array(t)
-        print("%-16s pe%-4d device_step ms min %.4f median %.4f max %.4f  good bytes %d" % (label, L, float(v.min()), float(np.median(v)), float(v.max()), int(sizes[0] + sizes[3])), flush=True)
+        print(vb.step_line(label, L, v, sizes), flush=True)
     eng.close()
 
 
