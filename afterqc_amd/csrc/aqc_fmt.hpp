@@ -16,6 +16,7 @@
 #include "aqc_prim.hpp"       // WAVE, lane_id, load16u, wave_sum_dpp, block_excl_scan
 #include "aqc_batch.hpp"      // the marks in a framed chunk's length words: LEN_IRR, LEN_MASK, QLEN_MASK, QLEN_CONTIG
 #include "aqc_textin.hpp"     // the text stage's workgroup size (TXT_BLOCK): the sizing and base passes run with it
+#include "aqc_fmtwin.hpp"     // the piece list of a record (FmtPiece, FmtTask), piece_items: compiles without HIP, for the CPU selftest
 
 namespace aqc {
 
@@ -311,26 +312,7 @@ __global__ __launch_bounds__(TXT_BLOCK) void fmt_tile_bases_kernel(unsigned long
 // each copied from a source: the chunk's text, or a small table of literals ("@BADPOL", "\n", "@").  Neighbouring pieces
 // that are neighbours in the text as well are merged while the list is built, so an untrimmed good record is ONE piece
 // (the record's own bytes), a tail-trimmed one three, a renamed (bad) one two more.
-constexpr int FMT_MAXP = 10;
-constexpr uint32_t GRID_MIN = 48;      // the general copy kernel's pieces of >= GRID_MIN bytes: windows on the source's grid, one work item more per piece
-// work items of a piece of `len` bytes in the general copy kernel: a short piece is one, a long one a 16-byte window per item —
-// on the source's grid (head window + aligned windows, the last one end-aligned) that is one more than len / 16 rounded up
-__host__ __device__ constexpr uint32_t piece_items(uint32_t len) {
-    return len >= 16u ? ((len + 15u) >> 4) + (len >= GRID_MIN ? 1u : 0u) : (len > 0u ? 1u : 0u);
-}
-constexpr uint32_t FMT_LIT_BIT = 0x80000000u;
-struct FmtPiece {
-    uint32_t src;          // byte offset from the file's text base; FMT_LIT_BIT: offset into FMT_LIT instead
-    uint16_t dst, len;     // position in the output record, bytes
-};
-struct FmtTask {
-    uint32_t pos;          // offset of the record in its output stream
-    uint8_t stream;        // 0 good / 1 bad / 2 overlap, 0xff: not written in this pass
-    uint8_t np, n_patch, pad_;
-    uint16_t total, items; // bytes of the output record; work items (16-byte windows + short pieces)
-    uint32_t patch[6];     // the walk's edits: output position | new byte << 16
-    FmtPiece p[FMT_MAXP];
-};
+// (FmtPiece, FmtTask, FMT_MAXP, FMT_LIT_BIT, GRID_MIN and piece_items — the work items of a piece — are in aqc_fmtwin.hpp)
 
 // literals: row f < 12 = "@" + FLAG text, row 12 = "\n", row 13 = "@"
 __device__ uint8_t FMT_LIT[16][16] = {"@GOOD", "@BADBCD1", "@BADBCD2", "@BADTRIM1", "@BADTRIM2", "@BADBBL", "@BADLEN", "@BADPOL", "@BADLQC",

@@ -8,6 +8,7 @@
 #include "aqc_prim.hpp"       // WAVE, lane_id, gload_* / gstore_*, load16u / store16u, wave_incl_sum, block_excl_scan
 #include "aqc_batch.hpp"      // the marks in a framed chunk's length words: LEN_IRR, LEN_MASK, QLEN_CONTIG
 #include "aqc_fmt.hpp"        // the format model: FormatView, fmt_sizes, FmtTask, fmt_build, FormatOut, the FMT_* tile sizes
+#include "aqc_fmtwin.hpp"     // the forward copies' arithmetic: plan_words, the plan decode and the window rules (FMTW_*)
 #include "aqc_revcopy.hpp"    // the reversed 16-byte windows of the merged-read pass
 
 namespace aqc {
@@ -24,59 +25,9 @@ namespace aqc {
 // output) is done here once per record.  Records with more than eight pieces / four patches / 32 work items keep their
 // full FmtTask in an overflow array (q0.y bit 31).  A record that goes out as ONE piece — its own bytes — needs q0 only.
 // fmt_copy_whole_kernel takes those, fmt_copy_kernel everything else (listed by the plan kernel).
-constexpr uint32_t PLAN_SKIP = 0xffffffffu, PLAN_OVER = 0x80000000u;
 constexpr unsigned int GEN_LISTS = 256;      // lists of "general" records (capacity gen_cap each), see fmt_plan_kernel
-constexpr int PLAN_Q = 6;                    // 16-byte words per plan
-constexpr int PLAN_MAXP = 8;
-constexpr int GEN_PASSES = 2;                // work items per lane of the general copy kernel (32 lanes per record)
-
-// the plans fmt_copy_whole_kernel takes: one piece of 16..512 bytes from the text — the record's own bytes — with up to four
-// byte patches (a pair the correction walk edited is still its own bytes but for those: ~8 % of the records of a 2 x 150 run,
-// which used to go through the general kernel, 0.7 of the text step's 4.6 ms)
-__device__ __forceinline__ bool plan_is_whole(const uint4& q0) {
-    return (q0.y & 0xff00ff00u) == 0x100u && ((q0.y >> 16) & 0xffu) <= 4u && !(q0.z & FMT_LIT_BIT) && (q0.w & 0xffffu) >= 16u && (q0.w & 0xffffu) <= 512u;
-}
-
-// the six plan words of a record's piece list `t` placed at `pos` of its stream (layout: above); false: the record does not fit a
-// plan — more than eight pieces, four patches or 64 work items, or a patch inside a piece of < 16 bytes — q[0] then says PLAN_OVER
-// and the caller keeps the full FmtTask in the overflow array
-struct PlanWords { uint4 q0, q1, q2, q3, q4, q5; bool inline_ok; };
-__device__ __forceinline__ PlanWords plan_words(const FmtTask& t, uint32_t pos) {
-    const uint4 zero4 = make_uint4(0, 0, 0, 0);
-    uint4 q0 = zero4, q1 = zero4, q2 = zero4, q3 = zero4, q4 = zero4, q5 = zero4;
-    // inline: up to eight pieces, four byte patches (each inside a piece of >= 16 bytes), 64 work items (1 KiB)
-    bool inline_ok = t.np <= PLAN_MAXP && t.n_patch <= 4 && t.items <= 32 * GEN_PASSES;
-    for (int e = 0; e < (int)t.n_patch && inline_ok; ++e) {
-        const int pp = (int)(t.patch[e] & 0xffffu);
-        int o = 0;
-        for (int k = 0; k < (int)t.np; ++k) {
-            if (pp >= o && pp < o + (int)t.p[k].len && t.p[k].len < 16) inline_ok = false;
-            o += t.p[k].len;
-        }
-    }
-    if (inline_ok) {
-        uint32_t src[PLAN_MAXP], len[PLAN_MAXP], cum[PLAN_MAXP], off[PLAN_MAXP];
-        uint32_t ci = 0, doff = 0;
-        for (int k = 0; k < PLAN_MAXP; ++k) {
-            const bool in = k < (int)t.np;
-            src[k] = in ? t.p[k].src : 0u;
-            len[k] = in ? (uint32_t)t.p[k].len : 0u;
-            off[k] = doff;
-            ci += piece_items(len[k]);
-            cum[k] = ci;
-            doff += len[k];
-        }
-        q0 = make_uint4(pos, (uint32_t)t.stream | ((uint32_t)t.np << 8) | ((uint32_t)t.n_patch << 16), src[0], len[0] | (len[1] << 16));
-        q1 = make_uint4(src[1], src[2], src[3], src[4]);
-        q2 = make_uint4(src[5], src[6], src[7], len[2] | (len[3] << 16));
-        q3 = make_uint4(len[4] | (len[5] << 16), len[6] | (len[7] << 16), cum[0] | (cum[1] << 8) | (cum[2] << 16) | (cum[3] << 24),
-                          cum[4] | (cum[5] << 8) | (cum[6] << 16) | (cum[7] << 24));
-        q4 = make_uint4(off[1] | (off[2] << 16), off[3] | (off[4] << 16), off[5] | (off[6] << 16), off[7] | (ci << 16));
-        q5 = make_uint4(t.n_patch > 0 ? t.patch[0] : 0u, t.n_patch > 1 ? t.patch[1] : 0u, t.n_patch > 2 ? t.patch[2] : 0u,
-                          t.n_patch > 3 ? t.patch[3] : 0u);
-    } else q0 = make_uint4(pos, PLAN_OVER | (uint32_t)t.stream, 0, 0);
-    return PlanWords{q0, q1, q2, q3, q4, q5, inline_ok};
-}
+// (PLAN_SKIP, PLAN_OVER, PLAN_Q, PLAN_MAXP, GEN_PASSES, plan_is_whole — the plans fmt_copy_whole_kernel takes — and plan_words, which
+//  packs a piece list into the six words, are in aqc_fmtwin.hpp)
 
 // exclusive prefixes of two values per thread over the FMT_TILE threads of a plan workgroup (two waves): DPP lane scans, the other
 // wave's totals through LDS (`lds`: 2 x 2 words of its own per call site — one barrier, none for reuse)
@@ -244,22 +195,10 @@ __device__ __forceinline__ void copy_whole_tasks(const FormatView& v, const uint
         const int len = (int)(pa[u].w & 0xffffu);
         uint8_t* const d0 = outs.p[file * 3 + (int)(pa[u].y & 0xffu)] + pa[u].x;
         const uint8_t* const s0 = v.f[file].text + pa[u].z;
-        int nw = (len + 15) >> 4;
-        int off = 16 * lane32;
-        // round 6: the windows stand on the 16-byte grid of the SOURCE (on the destination's they measured slower than with no
-        // grid at all — profiles/r06_copy_window_grid.txt): lane 0 takes the record's first 16 bytes wherever they stand, lane k >= 1 the
-        // k-th aligned window behind them, the last window end-aligned as before.  A wave's load instruction then touches every 64-byte
-        // line once (off the grid each quad of lanes straddles two).  A record of > 496 bytes off the grid would take 33 windows: it
-        // keeps the plain ones
-        {
-            const int a = (16 - (int)((uintptr_t)s0 & 15u)) & 15;
-            const int nwa = 1 + ((len - a + 15) >> 4);
-            const bool grid = a != 0 && nwa <= 32;
-            nw = grid ? nwa : nw;
-            off = grid && lane32 ? a + 16 * (lane32 - 1) : off;
-        }
+        // the windows: head window + the source's 16-byte grid, the last one end-aligned (the rule's text: aqc_fmtwin.hpp)
+        FMTW_WHOLE_WINDOW_GRID(len, s0, lane32, nw, off)
         on[u] = plan_is_whole(pa[u]) && lane32 < nw;
-        off = min(off, len - 16);
+        FMTW_WHOLE_WINDOW_END(len, off)
         dptr[u] = d0 + off;
         if (on[u]) val[u] = load16u(s0 + off);
     }
@@ -400,8 +339,7 @@ __global__ __launch_bounds__(COPY_BLOCK) void fmt_copy_kernel(FormatView v, cons
             // third of this kernel's vector instructions
             const uint8_t* const pb = reinterpret_cast<const uint8_t*>(P);
             const uint4 q0 = P[0];
-            const uint2 cumw = *reinterpret_cast<const uint2*>(pb + 56);                                 // q3.z, q3.w: cumulative items, a byte per piece
-            const uint32_t q4w = *reinterpret_cast<const uint32_t*>(pb + 76);
+            FMTW_PLAN_HEAD(pb, cumw, q4w)                                                                // q3.z, q3.w: cumulative items, a byte per piece | q4.w
             const bool ovf = live && (q0.y & PLAN_OVER) != 0;
             more |= ovf ? 1u << u : 0u;
             const uint32_t file = nfiles == 2 ? (s_ti[live ? idx : 0u] & 1u) : 0u;
@@ -413,26 +351,10 @@ __global__ __launch_bounds__(COPY_BLOCK) void fmt_copy_kernel(FormatView v, cons
                 const int w = u * GEN_PASSES + j;
                 const uint32_t item = (uint32_t)lane32 + 32u * j;
                 const bool on = item < items;
-                // my piece: the pieces whose cumulative item count I am at or beyond (bytes 0..6; counts and items are < 128)
-                const uint32_t rep = (item * 0x01010101u) | 0x80808080u;
-                int k = __popc((rep - cumw.x) & 0x80808080u) + __popc((rep - cumw.y) & 0x00808080u);
-                k = on ? k : 0;
-                const int first_item = (int)(((cum << 8) >> (8 * k)) & 0xffu);
-                const int lk = (int)*reinterpret_cast<const uint16_t*>(pb + (k < 2 ? 12 : 40) + 2 * k);                    // lengths: q0.w | q2.w, q3.x, q3.y
-                const int dst_rd = (int)*reinterpret_cast<const uint16_t*>(pb + 62 + 2 * max(k, 1));                      // output offsets of pieces 1..7: q4
-                const int dst_off = k == 0 ? 0 : dst_rd;                                                                  // (read, then chosen: no branch around the read)
-                const uint32_t sk = *reinterpret_cast<const uint32_t*>(pb + (k == 0 ? 8 : 12 + 4 * k));                    // sources: q0.z | q1, q2.xyz
-                // a long piece: my 16-byte window of it, the last one aligned to the piece's end; a short piece: all of it
-                int off = 16 * ((int)item - first_item);
-                // (round 6) a piece of >= GRID_MIN bytes has one item more (piece_items): its first window where the piece starts, the
-                // others on the 16-byte grid of the SOURCE, so that a load instruction touches each 64-byte line once
-                {
-                    const uint32_t tb = (uint32_t)(uintptr_t)(file ? tp1 : tp0);
-                    const int a = (int)((0u - (tb + sk)) & 15u);
-                    const bool grid = lk >= (int)GRID_MIN && !(sk & FMT_LIT_BIT) && off;
-                    off += (a - 16) & -(int)grid;                                    // (arithmetic, not a branch around eight instructions)
-                }
-                off = lk >= 16 ? min(off, lk - 16) : 0;
+                // my piece, read from the plan in LDS at an address worked out from its number k ...
+                FMTW_PLAN_PIECE(pb, cumw, cum, item, on, k, first_item, lk, dst_off, sk)
+                // ... and my window of it: a long piece's 16-byte window, the last one aligned to the piece's end; a short piece: all of it
+                FMTW_GEN_WINDOW(lk, (uint32_t)(uintptr_t)(file ? tp1 : tp0), sk, (int)item - first_item, off)
                 so[w] = sk + (uint32_t)off;
                 dof[w] = q0.x + (uint32_t)(dst_off + off);
                 mw[w] = on ? ((uint32_t)min(lk, 16) | ((uint32_t)(dst_off + off) << 5) | (fs << 21) | (file << 24)) : 0u;

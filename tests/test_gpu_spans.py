@@ -116,3 +116,11 @@ def test_spans_single_end(gpu_engine):
     assert capi.assemble_spans(t1, int(info.consumed1), ev, fetch(eng, 0, sizes, 0)) == want
     assert sizes[1] == want_sizes[1] and fetch(eng, 0, sizes, 1) == want_bad
     eng.reset_stats()
+
+
+def test_spans_assemble_to_the_oracle_stream(gpu_engine):
+    """the assembled spans against the ORACLE's good stream (the cases above compare the device with the device), cuts included"""
+    import writer_cases
+    t1, t2 = texts(1500, 9191)
+    writer_cases.check(gpu_engine, cfg_default(), t1, t2, ("spans",))
+    gpu_engine.reset_stats()

@@ -2,8 +2,8 @@
 (use_text_path=False — seqFilter._write builds the merged reads from the verdicts), against tests/golden/merged_cases.json.gz, which
 tests/golden/make_merged.py derived from the REAL reference's good and overlap files by the rule of tests/merged_rule.py.
 Also: the option changes no other output, is refused together with --store_overlap on, does nothing for single-end input; and
-the per-window functions of the device's reversed copy (csrc/aqc_revcopy.hpp) as a stand-alone C++ program, plain and under
-ASan / UBSan (tests/native/revcopy_selftest.cpp)."""
+the per-window functions of the device's reversed copy (csrc/aqc_revcopy.hpp) and the window and plan rules of its forward copies
+(csrc/aqc_fmtwin.hpp) as stand-alone C++ programs, plain and under ASan / UBSan (tests/native/revcopy_selftest.cpp, fmtcopy_selftest.cpp)."""
 import json
 import os
 import subprocess
@@ -173,3 +173,20 @@ def test_reversed_copy_windows_on_the_cpu(tmp_path, flags):
     assert out.returncode == 0, out.stdout[-6000:] + out.stderr[-3000:]
     assert "all revcopy window checks passed" in out.stdout, out.stdout[-3000:]
     assert "25600 pieces" in out.stdout
+
+
+@pytest.mark.parametrize("flags", [["-O2"], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]], ids=["plain", "asan_ubsan"])
+def test_forward_copy_windows_and_plans_on_the_cpu(tmp_path, flags):
+    """csrc/aqc_fmtwin.hpp without HIP — the text of the rules the copy kernels expand: the whole-record windows for every length 16 .. 512
+    and the general kernel's for every piece length 16 .. 1100, at all 16 source alignments (inside, complete, on the grid, at most 32 /
+    piece_items of them), and packed plans decoded per work item against a linear search; once more as a stand-alone ASan / UBSan
+    binary, every copy into a heap block that ends with the record"""
+    exe = os.path.join(str(tmp_path), "fmtcopy_selftest")
+    # (the plan's bytes are read as 16- and 32-bit words, as the kernel reads them from LDS)
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-fno-strict-aliasing"] + flags + [os.path.join(ROOT, "tests", "native", "fmtcopy_selftest.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-6000:] + out.stderr[-3000:]
+    assert "all fmtcopy window and plan checks passed" in out.stdout, out.stdout[-3000:]
+    assert "whole records: 7952 (length, alignment) pairs" in out.stdout            # (512 - 16 + 1) x 16
+    assert "general pieces: 17360 (length, alignment) pairs" in out.stdout          # (1100 - 16 + 1) x 16
+    # (the plan cases are random: the program itself checks that every kind of them occurred)
