@@ -62,6 +62,10 @@ OPTIONS = [
     ("", "--adapter_sequence", dict(default=None, help="the adapter of read 1, 4 to 64 letters of A, C, G, T: each read is cut at the first place where the adapter (or, at the read's tail, its first adapter_min_overlap bases or more) lies with at most one mismatch per eight compared bases. Runs inside the trim stage, after -f / -t and after cut_front / cut_tail / cut_right. By default no adapter is searched")),
     ("", "--adapter_sequence_r2", dict(default=None, help="the adapter of read 2, by default the same as adapter_sequence; given alone, only read 2 is searched")),
     ("", "--adapter_min_overlap", dict(default=4, type="int", help="the fewest bases of an adapter that must lie on the read for a match at its tail, 1 to the length of the shorter adapter. Default is 4")),
+    ("", "--trim_poly_g", dict(default="off", help="specify whether to cut a poly-G tail from each read (a dark cycle of a two-colour instrument reads as G): from the read's end a run of G is followed while at most one base in eight, and at most five in all, is something else; a run of poly_g_min_len bases or more is cut off at its leftmost G. Runs inside the trim stage, after -f / -t, cut_front / cut_tail / cut_right and adapter_sequence. Default is off")),
+    ("", "--poly_g_min_len", dict(default=10, type="int", help="the shortest poly-G tail that is cut, 1 to 1000. Default is 10")),
+    ("", "--trim_poly_x", dict(default="off", help="specify whether to cut a tail of any one letter of A, C, G, T (poly-A tails included) from each read, by the rule of trim_poly_g with poly_x_min_len; the letter that cuts most wins. Default is off")),
+    ("", "--poly_x_min_len", dict(default=10, type="int", help="the shortest poly-X tail that is cut, 1 to 1000. Default is 10")),
     ("", "--qc_only", dict(action="store_true", default=False, help="if qconly is true, only QC result will be output, this can be much fast")),
     ("", "--qc_sample", dict(default=200000, type="int", help="sample up to qc_sample reads when do QC, 0 means sample all reads. Default is 200,000")),
     ("", "--qc_kmer", dict(default=8, type="int", help="specify the kmer length for KMER statistics for QC, default is 8")),
@@ -76,6 +80,7 @@ OPTIONS = [
 CUT_MAX_WINDOW = 1000       # AQC_MAX_READ_LEN
 CUT_MAX_QUALITY = 93
 ADAPTER_MIN_LEN, ADAPTER_MAX_LEN = 4, 64
+POLY_MAX_MIN_LEN = 1000     # AQC_MAX_READ_LEN
 
 
 def parseBool(s):
@@ -133,6 +138,10 @@ def finalize_options(options):
     if not 1 <= options.adapter_min_overlap <= shortest:
         raise SystemExit("afterqc_amd: --adapter_min_overlap %d is outside 1 .. %d%s" % (options.adapter_min_overlap, shortest,
                                                                                          " (the shorter adapter)" if given else ""))
+    for k, length in (("trim_poly_g", "poly_g_min_len"), ("trim_poly_x", "poly_x_min_len")):
+        setattr(options, k, parseBool(getattr(options, k)))
+        if not 1 <= getattr(options, length) <= POLY_MAX_MIN_LEN:
+            raise SystemExit("afterqc_amd: --%s %d is outside 1 .. %d" % (length, getattr(options, length), POLY_MAX_MIN_LEN))
     options.trim_front2 = options.trim_front
     options.trim_tail2 = options.trim_tail
     return options

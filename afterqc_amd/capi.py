@@ -124,6 +124,25 @@ class AdapterConfig(C.Structure):
         return bytes(self.seq1[:min(self.len1, 64)]), bytes(self.seq2[:min(self.len2, 64)])
 
 
+class PolyConfig(C.Structure):
+    """struct aqc_poly_config: the letters whose tails are cut from each read (--trim_poly_g / --trim_poly_x) and their minimum
+    lengths, in the order A, C, G, T; 0: that letter is not tried"""
+    _fields_ = [("min_len", C.c_int32 * 4)]
+
+    def __init__(self, a=0, c=0, g=0, t=0):
+        super().__init__()
+        # (a length the library refuses travels as it is)
+        for i, v in enumerate((a, c, g, t)):
+            self.min_len[i] = int(v)
+
+    @property
+    def on(self):
+        return any(self.min_len)
+
+    def lengths(self):
+        return tuple(int(v) for v in self.min_len)
+
+
 class BatchStruct(C.Structure):
     """struct aqc_batch"""
     _fields_ = [("n", C.c_uint64), ("first_index", C.c_uint64),
@@ -391,6 +410,10 @@ def load_library():
     lib.aqc_get_adapter_stats.argtypes = [P, P]
     lib.aqc_adapter_ms.argtypes = [P, C.c_int, C.POINTER(C.c_float)]
     lib.aqc_adapter_views.argtypes = [P, C.POINTER(BatchStruct), C.POINTER(AdapterConfig), C.c_int32, C.c_int32, P, P]
+    lib.aqc_set_poly_trim.argtypes = [P, C.POINTER(PolyConfig)]
+    lib.aqc_get_poly_stats.argtypes = [P, P]
+    lib.aqc_poly_ms.argtypes = [P, C.c_int, C.POINTER(C.c_float)]
+    lib.aqc_poly_views.argtypes = [P, C.POINTER(BatchStruct), C.POINTER(PolyConfig), C.c_int32, C.c_int32, P, P]
     lib.aqc_upload.argtypes = [P, C.c_int, C.POINTER(BatchStruct)]
     lib.aqc_run.argtypes = [P, C.c_int, C.c_uint64]
     lib.aqc_qc_stat.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int]
@@ -483,7 +506,8 @@ def load_library():
                  "aqc_overlap", "aqc_read_stats", "aqc_edit_distance", "aqc_frame", "aqc_frame_mixed", "aqc_reframe", "aqc_format", "aqc_format_plain",
                  "aqc_fetch_text", "aqc_fetch_quality_views", "aqc_error_record", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused",
                  "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms", "aqc_set_quality_cut", "aqc_get_cut_stats", "aqc_cut_ms", "aqc_quality_cut_views",
-                 "aqc_set_adapter_trim", "aqc_get_adapter_stats", "aqc_adapter_ms", "aqc_adapter_views"):
+                 "aqc_set_adapter_trim", "aqc_get_adapter_stats", "aqc_adapter_ms", "aqc_adapter_views",
+                 "aqc_set_poly_trim", "aqc_get_poly_stats", "aqc_poly_ms", "aqc_poly_views"):
         getattr(lib, name).restype = C.c_int
     if lib.aqc_abi_version() != 3:
         raise RuntimeError("libafterqc_hip.so ABI version mismatch")
@@ -504,6 +528,7 @@ EXPORTED_SYMBOLS = ["aqc_abi_version", "aqc_device_count", "aqc_device_index", "
                     "aqc_gz_deflate_block", "aqc_gz_inflate_raw", "aqc_gz_crc32",
                     "aqc_set_quality_cut", "aqc_get_cut_stats", "aqc_cut_ms", "aqc_quality_cut_views",
                     "aqc_set_adapter_trim", "aqc_get_adapter_stats", "aqc_adapter_ms", "aqc_adapter_views",
+                    "aqc_set_poly_trim", "aqc_get_poly_stats", "aqc_poly_ms", "aqc_poly_views",
                     # the reference's own native seam (editdistance/_editdistance.h:16,23), same names and signatures
                     "edit_distance", "seek_overlap"]
 
@@ -593,6 +618,18 @@ class Engine:
     def adapter_ms(self, slot):
         """device time of the adapter pass of the slot's last run(); 0.0: it launched none"""
         return self._pass_ms(self.lib.aqc_adapter_ms, slot)
+
+    def set_poly_trim(self, poly):
+        """poly: a PolyConfig, or None (off).  With every length 0 nothing of the pass runs."""
+        self._check(self.lib.aqc_set_poly_trim(self.h, C.byref(poly) if poly is not None else None))
+
+    def poly_stats(self):
+        """reads of R1 the poly-tail pass made shorter, bases it removed from them, the same for R2"""
+        return self._four_counts(self.lib.aqc_get_poly_stats)
+
+    def poly_ms(self, slot):
+        """device time of the poly-tail pass of the slot's last run(); 0.0: it launched none"""
+        return self._pass_ms(self.lib.aqc_poly_ms, slot)
 
     def upload(self, slot, batch):
         s = batch.as_struct()
@@ -808,6 +845,19 @@ class Engine:
         s = batch.as_struct()
         self._check(self.lib.aqc_adapter_views(self.h, C.byref(s), C.byref(adapter), int(trim_front), int(trim_tail),
                                                _ptr(vin) if vin is not None else None, _ptr(v)))
+        return (v & 0xffff).astype(np.int64), (v >> 16).astype(np.int64)
+
+    def poly_views(self, batch, poly, trim_front=0, trim_tail=0, view_in=None):
+        """the poly-tail pass alone on read 1 of the batch -> (c0, c1) arrays; view_in: (c0, c1) arrays of the views the reads come
+        with (an earlier pass's), None: everything"""
+        v = np.zeros(batch.n, dtype=np.uint32)
+        vin = None
+        if view_in is not None:
+            vin = (np.asarray(view_in[0], dtype=np.uint32) | (np.asarray(view_in[1], dtype=np.uint32) << 16)).astype(np.uint32)
+            assert vin.shape == (batch.n,)
+        s = batch.as_struct()
+        self._check(self.lib.aqc_poly_views(self.h, C.byref(s), C.byref(poly), int(trim_front), int(trim_tail),
+                                            _ptr(vin) if vin is not None else None, _ptr(v)))
         return (v & 0xffff).astype(np.int64), (v >> 16).astype(np.int64)
 
     def edit_distance(self, batch):
@@ -1083,6 +1133,9 @@ class MergedEngines:
 
     def adapter_stats(self):
         return sum(e.adapter_stats() for e in self.engines)
+
+    def poly_stats(self):
+        return sum(e.poly_stats() for e in self.engines)
 
     def histograms(self, n=AQC_QC_COLS):
         hs = [e.histograms(n) for e in self.engines]

@@ -347,6 +347,21 @@ int aqc_set_adapter_trim(aqc_ctx* c, const aqc_adapter_config* adapter) {
 
 int aqc_get_adapter_stats(aqc_ctx* c, int64_t out[4]) { return get_pass_stats(c, VP_ADAPTER, out); }
 
+// the letters whose tails are cut (aqc_polytail.hpp): NULL or every length 0 switches the pass off
+int aqc_set_poly_trim(aqc_ctx* c, const aqc_poly_config* poly) {
+    if (!c) return fail(AQC_ERR_ARG, "aqc_set_poly_trim: null context");
+    PolyOpts o{};
+    if (!poly_from_config(poly, o))
+        return fail(AQC_ERR_ARG, "aqc_set_poly_trim: minimum lengths %d / %d / %d / %d of A / C / G / T (0: off, or 1 .. %d)", poly->min_len[0], poly->min_len[1],
+                    poly->min_len[2], poly->min_len[3], POLY_MAX_MIN_LEN);
+    if (!poly_on(o)) { c->poly = PolyOpts{}; return 0; }
+    HIP_TRY(c->pass_stats[VP_POLY].ensure(c->device));
+    c->poly = o;
+    return 0;
+}
+
+int aqc_get_poly_stats(aqc_ctx* c, int64_t out[4]) { return get_pass_stats(c, VP_POLY, out); }
+
 int aqc_set_circles(aqc_ctx* c, const double* cx, const double* cy, const double* r, const int32_t* lane,
                     const int32_t* tile, int32_t n) {
     if (!c || n < 0) return fail(AQC_ERR_ARG, "aqc_set_circles: bad arguments");

@@ -13,9 +13,10 @@
 //   aqc_upload.hpp   narrow_offsets_kernel, mark_irregular_kernel, quality_views_kernel
 //   aqc_record.hpp   filter_overlap_kernel, filter_overlap_list_kernel, filter_overlap_cut_kernel<LIST>
 //   aqc_fast.hpp     fast_filter_overlap_kernel<NW, PAIRED, WPBT, BARCODE, FUSE, CUT> (a template: the variants are instantiated here)
-//   aqc_viewpass.hpp no kernel of its own: the frame of the two view passes in front of the verdict kernel, and their dispatch on G
+//   aqc_viewpass.hpp no kernel of its own: the frame of the three view passes in front of the verdict kernel, and their dispatch on G
 //   aqc_qcut.hpp     quality_cut_kernel<G> (the quality cut's pass, and its function seam)
 //   aqc_adapter.hpp  adapter_cut_kernel<G> (the adapter pass behind it, a second producer of the same views, and its function seam)
+//   aqc_polytail.hpp poly_tail_kernel<G> (the poly-G / poly-X pass behind both, a third producer, and its function seam)
 //   aqc_gzdev.hpp    gz_hist_kernel, gz_encode_wave_kernel, gz_encode_kernel, gz_offsets_kernel, gz_pack_kernel
 //   aqc_gzlz.hpp     gz_hist_lz_kernel, gz_encode_lz_kernel (levels 6 - 9)
 //   aqc_seams.hpp    overlap_seam_kernel, read_stats_seam_kernel, edit_distance_seam_kernel, edit_distance_any_kernel,
@@ -41,8 +42,8 @@
 
 using namespace aqc;
 
-// a pass in front of the verdict kernel leaves a view per mate and record: the quality cut, the adapter pass, or both
-static bool views_on(const aqc_ctx* c) { return qcut_on(c->cut) || adp_on(c->adapter); }
+// a pass in front of the verdict kernel leaves a view per mate and record: the quality cut, the adapter pass, the poly-tail pass, or several
+static bool views_on(const aqc_ctx* c) { return qcut_on(c->cut) || adp_on(c->adapter) || poly_on(c->poly); }
 
 constexpr int FUSE_WPBT = 12;      // waves per workgroup of the fused verdict kernel
 // waves per workgroup of the 20-word tier's paired instances: 10 or 11 fit the CU's 160 KiB of LDS (144,048 / 157,568 bytes).  11 by
@@ -313,8 +314,26 @@ static int launch_adapter(aqc_ctx* c, Slot& s, const AdapterOpts& a, const int32
     return 0;
 }
 
-// A view pass of an aqc_run: both mates' views into the slot's array, timed by an event pair of its own.  The cut pass fills the
-// array; the adapter pass behind it updates the cut's views in place, or fills the array itself.
+// ---- the poly-tail pass (aqc_polytail.hpp): the view each mate leaves it with into `view`; view_in: the views they come with (may be `view`; NULL: everything)
+static int launch_poly(aqc_ctx* c, Slot& s, const PolyOpts& o, const int32_t trim_front[2], const int32_t trim_tail[2], int n_mates,
+                       const uint32_t* view_in, uint32_t* view, unsigned long long* stats, uint64_t accum_limit) {
+    PolyArgs A{};
+    A.n = s.view.n; A.n_mates = n_mates; A.view_in = view_in; A.view = view; A.stats = stats; A.accum_limit = accum_limit; A.status = s.status;
+    for (int x = 0; x < POLY_LETTERS; ++x) A.min_len[x] = o.min_len[x];
+    for (int k = 0; k < n_mates; ++k) {
+        PolyMate& M = A.m[k];
+        M.seq = k ? s.view.seq2 : s.view.seq1; M.off = k ? s.view.off2 : s.view.off1; M.len = k ? s.view.len2 : s.view.len1;
+        M.trim_front = trim_front[k]; M.trim_tail = trim_tail[k];
+    }
+    vp_dispatch(view_pass_lanes(s), s.n, c->n_cu, [&](auto G, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(poly_tail_kernel<decltype(G)::value>, grid, block, 0, s.stream, A);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// A view pass of an aqc_run: both mates' views into the slot's array, timed by an event pair of its own.  The first pass that runs
+// fills the array; a pass behind it updates the views in place.
 static int run_view_pass(aqc_ctx* c, Slot& s, ViewPassId which, const aqc_config& cfg, uint64_t accum_limit) {
     ViewPass& vp = s.pass[which];
     const int nm = cfg.paired ? 2 : 1;
@@ -327,6 +346,8 @@ static int run_view_pass(aqc_ctx* c, Slot& s, ViewPassId which, const aqc_config
     HIP_TRY(hipEventRecord(vp.ev[0], s.stream));
     int rc;
     if (which == VP_CUT) rc = launch_cut(c, s, c->cut, tf, tt, nm, view, stats, accum_limit);
+    else if (which == VP_POLY)
+        rc = launch_poly(c, s, c->poly, tf, tt, nm, (s.pass[VP_CUT].ran || s.pass[VP_ADAPTER].ran) ? view : nullptr, view, stats, accum_limit);
     else {
         AdapterOpts a = c->adapter;
         if (nm == 1) a.len[1] = 0;
@@ -344,7 +365,7 @@ int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
     if (c->cfg.paired && !s->paired) return fail(AQC_ERR_STATE, "config says paired but the slot holds single-end records");
     if (c->cfg.debubble && c->circles.n > 0 && !s->view.aux_ok) return fail(AQC_ERR_ARG, "debubble needs the aux_* arrays");
     const bool cut = views_on(c);           // the verdict kernels take views: the CUT instances
-    if (cut && c->cfg.barcode) return fail(AQC_ERR_UNSUPPORTED, "aqc_run: the quality cut or an adapter together with a barcode is not implemented");
+    if (cut && c->cfg.barcode) return fail(AQC_ERR_UNSUPPORTED, "aqc_run: the quality cut, an adapter or a poly-tail cut together with a barcode is not implemented");
     s->fused = false;
     s->verdict_words = 0;
     for (ViewPass& vp : s->pass) vp.ran = false;
@@ -354,7 +375,7 @@ int aqc_run(aqc_ctx* c, int slot, uint64_t accum_limit) {
     DevStats st{c->counters, c->ovl_hist, c->dist_hist, s->status, err_key_of(*s)};
     s->err_record = UINT64_MAX;
     if (s->qc.pending()) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_qc, 0));      // (statRead of the previous run still reads the results)
-    const bool pass_on[VP_N] = {qcut_on(c->cut), adp_on(c->adapter)};
+    const bool pass_on[VP_N] = {qcut_on(c->cut), adp_on(c->adapter), poly_on(c->poly)};
     for (int p = 0; p < VP_N; ++p)
         if (pass_on[p]) {
             const int rc = run_view_pass(c, *s, (ViewPassId)p, cfg, accum_limit);
@@ -435,6 +456,7 @@ static int view_pass_ms(aqc_ctx* c, int slot, ViewPassId which, float* ms, const
 }
 int aqc_cut_ms(aqc_ctx* c, int slot, float* ms) { return view_pass_ms(c, slot, VP_CUT, ms, "aqc_cut_ms"); }
 int aqc_adapter_ms(aqc_ctx* c, int slot, float* ms) { return view_pass_ms(c, slot, VP_ADAPTER, ms, "aqc_adapter_ms"); }
+int aqc_poly_ms(aqc_ctx* c, int slot, float* ms) { return view_pass_ms(c, slot, VP_POLY, ms, "aqc_poly_ms"); }
 
 // (host state only: set by aqc_run when it chose the kernel, so there is nothing to wait for)
 int aqc_last_verdict_words(aqc_ctx* c, int slot) {
@@ -663,6 +685,17 @@ int aqc_adapter_views(aqc_ctx* c, const aqc_batch* b, const aqc_adapter_config* 
     // (the search reads sequence lines only; a batch that brings quality lines is taken as aqc_run takes it, LEN_IRR marks included)
     return view_seam(c, b, b && b->qual1 != nullptr, view_in, view,
                      [&](Slot& s, uint32_t* v) { return launch_adapter(c, s, a, tf, tt, 1, view_in ? v : nullptr, v, nullptr, UINT64_MAX); });
+}
+
+int aqc_poly_views(aqc_ctx* c, const aqc_batch* b, const aqc_poly_config* poly, int32_t trim_front, int32_t trim_tail, const uint32_t* view_in,
+                   uint32_t* view) {
+    if (!poly || !view) return fail(AQC_ERR_ARG, "aqc_poly_views: null argument");
+    PolyOpts o{};
+    if (!poly_from_config(poly, o) || trim_front < 0 || trim_tail < 0) return fail(AQC_ERR_ARG, "aqc_poly_views: minimum length / trim out of range");
+    const int32_t tf[2] = {trim_front, 0}, tt[2] = {trim_tail, 0};
+    // (the pass reads sequence lines only; a batch that brings quality lines is taken as aqc_run takes it, LEN_IRR marks included)
+    return view_seam(c, b, b && b->qual1 != nullptr, view_in, view,
+                     [&](Slot& s, uint32_t* v) { return launch_poly(c, s, o, tf, tt, 1, view_in ? v : nullptr, v, nullptr, UINT64_MAX); });
 }
 
 // ---- the reference's existing native seam: libed.so (editdistance/_editdistance.h:16,23, loaded by util.py:16-24) ----

@@ -14,12 +14,13 @@
 #include "aqc_batch.hpp"
 #include "aqc_qcut.hpp"
 #include "aqc_adapter.hpp"
+#include "aqc_polytail.hpp"
 
 namespace aqc {
 
 // The passes in front of the verdict kernel that leave a view per mate and record in Slot::cut (aqc_viewpass.hpp), in launch order
-enum ViewPassId { VP_CUT = 0, VP_ADAPTER = 1, VP_N = 2 };
-// ... what a slot keeps of each: the event pair around the pass of the last aqc_run (aqc_cut_ms / aqc_adapter_ms), if it launched one
+enum ViewPassId { VP_CUT = 0, VP_ADAPTER = 1, VP_POLY = 2, VP_N = 3 };
+// ... what a slot keeps of each: the event pair around the pass of the last aqc_run (aqc_cut_ms / aqc_adapter_ms / aqc_poly_ms), if it launched one
 struct ViewPass { hipEvent_t ev[2] = {nullptr, nullptr}; bool ran = false; };
 // ... and what the context keeps: [4] reads of R1 the pass made shorter, bases it took from them, the same for R2.  On the device
 // from the first time the pass is switched on: a context that never sets it allocates what it always did.
@@ -153,6 +154,7 @@ struct __attribute__((visibility("hidden"))) aqc_ctx {
     bool has_cfg = false;
     aqc::QcutOpts cut{};               // aqc_set_quality_cut: the quality cut (all modes 0: off, no kernel of it is launched)
     aqc::AdapterOpts adapter{};        // aqc_set_adapter_trim: the adapters to trim (both lengths 0: off, no kernel of it is launched)
+    aqc::PolyOpts poly{};              // aqc_set_poly_trim: the letters whose tails are cut (every length 0: off, no kernel of it is launched)
     aqc::PassCounts pass_stats[aqc::VP_N];
     aqc::DevBuf circ[5];
     aqc::DevBuf kmer_partial;          // per-round u16 count slices of kmer_count_kernel

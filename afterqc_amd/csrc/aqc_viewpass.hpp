@@ -1,7 +1,7 @@
 // aqc_viewpass.hpp — what a view pass is: a kernel in front of the verdict kernel that decides, for every mate of a batch, which
-// part [c0, c1) of its trimmed line the verdict kernels see, and leaves that as one word per mate and record in Slot::cut.  Two
-// passes exist, the quality cut (aqc_qcut.hpp) and the adapter pass (aqc_adapter.hpp); the second takes the views of the first and
-// narrows them.  What both are made of stands here once, each pass's header holds its own middle.
+// part [c0, c1) of its trimmed line the verdict kernels see, and leaves that as one word per mate and record in Slot::cut.  Three
+// passes exist, the quality cut (aqc_qcut.hpp), the adapter pass (aqc_adapter.hpp) and the poly-tail pass (aqc_polytail.hpp); a later
+// one takes the views of the earlier ones and narrows them.  What all are made of stands here once, each pass's header holds its own middle.
 //
 //   view     c0 | c1 << 16, relative to the line behind trim(); VIEW_ALL (0, 0xffff) is the view of a mate nothing has cut.  The
 //            mates of a record lie side by side: mate k of record r at [r * n_mates + k].  The verdict kernels apply it to every
@@ -23,7 +23,7 @@
 // kernel, 4 KiB more LDS in the adapter kernel (profiles/r18_viewpass.txt).  A kernel reads: frame (rows, counters, the two loops), its own middle, frame (view out, too long,
 // counts, flush).
 //
-// Host-includable without HIP: tests/native/qcut_selftest.cpp and adapter_selftest.cpp take the per-read functions from here with a
+// Host-includable without HIP: tests/native/qcut_selftest.cpp, adapter_selftest.cpp and polytail_selftest.cpp take the per-read functions from here with a
 // plain C++ compiler and deal the lanes of a group out by loops.
 #pragma once
 #include <stdint.h>

@@ -120,13 +120,25 @@ def adapter_config(opt):
     return capi.AdapterConfig(a1, a2, int(getattr(opt, "adapter_min_overlap", 4)))
 
 
+def poly_config(opt):
+    """--trim_poly_g / --trim_poly_x and their minimum lengths as the engine takes them; None: both are off (options objects built
+    without the poly options count as off).  --trim_poly_x tries A, C, G and T; with both on, G takes the smaller length."""
+    on_g, on_x = bool(getattr(opt, "trim_poly_g", False)), bool(getattr(opt, "trim_poly_x", False))
+    if not on_g and not on_x:
+        return None
+    lg = int(getattr(opt, "poly_g_min_len", 10)) if on_g else 0
+    lx = int(getattr(opt, "poly_x_min_len", 10)) if on_x else 0
+    return capi.PolyConfig(lx, lx, min(lg, lx) if on_g and on_x else lg or lx, lx)
+
+
 # the passes in front of the verdict kernel that an option switches on: the engine's setter, the options it stands for
 VIEW_PASSES = (("set_quality_cut", "--cut_front / --cut_tail / --cut_right"),
-               ("set_adapter_trim", "--adapter_sequence / --adapter_sequence_r2"))
+               ("set_adapter_trim", "--adapter_sequence / --adapter_sequence_r2"),
+               ("set_poly_trim", "--trim_poly_g / --trim_poly_x"))
 
 
 def set_view_passes(engine, configs, clear=False):
-    """the quality cut and the adapters (configs: one per entry of VIEW_PASSES, None: off) on an engine.  A pass that is on needs
+    """the quality cut, the adapters and the poly tails (configs: one per entry of VIEW_PASSES, None: off) on an engine.  A pass that is on needs
     an engine that has it: an error, never a run without the option.  clear: a pass that is off is switched off on an engine that
     has it (an engine the caller handed over may come from a run that had it on)"""
     for (setter, options), config in zip(VIEW_PASSES, configs):
@@ -441,6 +453,7 @@ class seqFilter:
         self.stat = None
         self.cut = cut_config(opt)
         self.adapter = adapter_config(opt)
+        self.poly = poly_config(opt)
 
     # ---- helpers ---------------------------------------------------------------------------------
     def _engine(self):
@@ -460,7 +473,7 @@ class seqFilter:
                 e = capi.Engine(d, max(2, self.pipe_slots))
                 e.set_config(cfg)
                 e.set_circles(circles)
-                set_view_passes(e, (self.cut, self.adapter))
+                set_view_passes(e, (self.cut, self.adapter, self.poly))
                 e.reset_stats()
                 self.extra_engines.append(e)
         return [eng] + self.extra_engines
@@ -488,6 +501,9 @@ class seqFilter:
         if opt.barcode and self.adapter is not None:
             raise SystemExit("afterqc_amd: --adapter_sequence / --adapter_sequence_r2 are not implemented for barcoded input "
                              "(%s); run it with --barcode off or without the adapter" % opt.read1_file)
+        if opt.barcode and self.poly is not None:
+            raise SystemExit("afterqc_amd: --trim_poly_g / --trim_poly_x are not implemented for barcoded input "
+                             "(%s); run it with --barcode off or without the poly-tail cut" % opt.read1_file)
         t_init = time.perf_counter()
         eng = self._engine()
         self.timing = {"init_s": time.perf_counter() - t_init}       # (a fresh process: HIP runtime start + the library's code object)
@@ -530,7 +546,7 @@ class seqFilter:
         self._last_cfg = (build_config(opt, self.paired, opt.index2_file is not None), self.bubbleCircles)
         for e in self._engines():
             e.set_config(self._last_cfg[0])
-            set_view_passes(e, (self.cut, self.adapter), clear=True)
+            set_view_passes(e, (self.cut, self.adapter, self.poly), clear=True)
             if first:
                 e.set_circles(self.bubbleCircles)
                 e.reset_stats()
@@ -1046,6 +1062,13 @@ class seqFilter:
             a1, a2 = self.adapter.adapters()
             stat["adapter_trim"] = {
                 'adapter_sequence': a1.decode(), 'adapter_sequence_r2': a2.decode(), 'adapter_min_overlap': int(self.adapter.min_overlap),
+                'read1_trimmed_reads': n[0], 'read1_trimmed_bases': n[1], 'read2_trimmed_reads': n[2], 'read2_trimmed_bases': n[3],
+            }
+        if self.poly is not None:
+            n = [int(v) for v in eng.poly_stats()]
+            stat["poly_trim"] = {
+                'trim_poly_g': bool(getattr(opt, "trim_poly_g", False)), 'poly_g_min_len': int(getattr(opt, "poly_g_min_len", 10)),
+                'trim_poly_x': bool(getattr(opt, "trim_poly_x", False)), 'poly_x_min_len': int(getattr(opt, "poly_x_min_len", 10)),
                 'read1_trimmed_reads': n[0], 'read1_trimmed_bases': n[1], 'read2_trimmed_reads': n[2], 'read2_trimmed_bases': n[3],
             }
         return stat

@@ -263,6 +263,25 @@ int aqc_get_adapter_stats(aqc_ctx* ctx, int64_t out[4]);
 /* device time of the adapter pass of the slot's last aqc_run (HIP events on the slot's stream); 0: it launched none */
 int aqc_adapter_ms(aqc_ctx* ctx, int slot, float* ms);
 
+/* ---- cutting poly-G / poly-X tails from each read (--trim_poly_g / --trim_poly_x) -------------- */
+/* Inside the same trim stage, behind the fixed trim, the quality cut and the adapter pass: let s be the part of a mate's SEQUENCE
+ * line that those keep, n its length.  For a letter X with minimum length L, mm(u) is the number of bytes among the last u of s
+ * that are not exactly X (an N or a lower-case base is a mismatch); fail(u) holds when mm(u) > 5, or when u >= L and
+ * mm(u) > (u >> 3); scanned is the smallest u of 1 .. n with fail(u), minus 1 (n: there is none).  With scanned >= L the mate ends
+ * at its leftmost X inside the scanned tail.  Every enabled letter is tried on the same line, the smallest end wins, once; sequence
+ * and quality line are each sliced by their own length.  The stage's `< 5` tests then run as they stand.
+ * min_len: A, C, G, T in this order; 0: the letter is off, 1 .. 1000: on with that L. */
+typedef struct aqc_poly_config { int32_t min_len[4]; } aqc_poly_config;
+/* NULL or all zero: off — no kernel of the pass is launched and aqc_run is what it is without it.  A length outside 0 .. 1000:
+ * AQC_ERR_ARG.  With a letter on, aqc_run of a configuration that has `barcode` set returns AQC_ERR_UNSUPPORTED. */
+int aqc_set_poly_trim(aqc_ctx* ctx, const aqc_poly_config* poly);
+/* out[0..3]: reads of R1 the pass made shorter, bases it removed from them (on the sequence line, beyond what trim, quality cut
+ * and adapter took), the same for R2.  Records below accum_limit only; R2 is counted only where read 1 leaves the stage with 5
+ * bases or more.  Zeroed by aqc_reset_stats; contexts add up. */
+int aqc_get_poly_stats(aqc_ctx* ctx, int64_t out[4]);
+/* device time of the poly-tail pass of the slot's last aqc_run (HIP events on the slot's stream); 0: it launched none */
+int aqc_poly_ms(aqc_ctx* ctx, int slot, float* ms);
+
 /* ---- the hot path: preprocesser.py:411-631 over a batch --------------------------------------- */
 /* copy a batch into slot `slot` (async on the slot's stream; see the note on host buffers above) */
 int aqc_upload(aqc_ctx* ctx, int slot, const aqc_batch* batch);
@@ -525,6 +544,11 @@ int aqc_quality_cut_views(aqc_ctx* ctx, const aqc_batch* reads, const aqc_cut_co
  * "everything"; a read without a match keeps the view it came with */
 int aqc_adapter_views(aqc_ctx* ctx, const aqc_batch* reads, const aqc_adapter_config* adapter, int32_t trim_front, int32_t trim_tail,
                       const uint32_t* view_in /* may be NULL */, uint32_t* view);
+/* the poly-tail pass alone: for every read of the batch (seq1) the view it leaves the pass with, view[i] = c0 | c1 << 16 relative
+ * to the TRIMMED lines.  view_in: the view each read comes with (an earlier pass's), NULL: 0 | 0xffff << 16, "everything"; a read
+ * without a tail keeps the view it came with */
+int aqc_poly_views(aqc_ctx* ctx, const aqc_batch* reads, const aqc_poly_config* poly, int32_t trim_front, int32_t trim_tail,
+                   const uint32_t* view_in /* may be NULL */, uint32_t* view);
 
 /* ---- whole-input pipeline: the byte path of seqFilter.run's main loop (preprocesser.py:411-631) --------------------- */
 /* Reads one input (a read file, or a pair of mate files; plain, .gz, or text already in host memory), cuts it into chunks
