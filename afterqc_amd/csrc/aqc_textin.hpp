@@ -363,17 +363,25 @@ __global__ void frame_finish_kernel(const unsigned long long* __restrict__ d_tot
 // kernels turn 2 into AQC_ERR_ARG only if the record actually reaches the bubble stage, like the exception upstream.
 __device__ __forceinline__ bool is_digit(uint8_t c) { return c >= '0' && c <= '9'; }
 
-// int() of name[a:b): digits only; returns false for anything else; values beyond int32 saturate (no circle can
-// match such a lane / tile, and such a coordinate is outside every circle)
-__device__ __forceinline__ bool parse_uint(const uint8_t* name, int a, int b, int32_t& out) {
+// int() of name[a:b) as CPython 3 — the interpreter the golden vectors were recorded with — reads a field that holds no blanks: an
+// optional sign, then digits with single underscores between them ("+5", "-5", "1_0", "007"); returns false for anything else;
+// values beyond int32 saturate and set `big` (such a coordinate is outside every circle; such a lane or tile is no circle's, but
+// its saturated value may be one's: the caller must not compare it)
+__device__ __forceinline__ bool parse_int(const uint8_t* name, int a, int b, int32_t& out, bool& big) {
     if (b <= a) return false;
+    const bool neg = name[a] == '-';
+    if (neg || name[a] == '+') ++a;
     unsigned long long v = 0;
+    bool after_digit = false;                         // an underscore stands between two digits
     for (int i = a; i < b; ++i) {
+        if (name[i] == '_' && after_digit) { after_digit = false; continue; }
         if (!is_digit(name[i])) return false;
+        after_digit = true;
         v = v * 10ull + (unsigned long long)(name[i] - '0');
-        if (v > 0x7fffffffull) v = 0x7fffffffull;
+        if (v > 0x7fffffffull) { v = 0x7fffffffull; big = true; }
     }
-    out = (int32_t)v;
+    if (!after_digit) return false;                   // nothing behind the sign, or an underscore at the end
+    out = neg ? -(int32_t)v : (int32_t)v;
     return true;
 }
 
@@ -423,10 +431,11 @@ __global__ __launch_bounds__(TXT_BLOCK) void parse_names_kernel(const uint8_t* _
         for (int i = m_s; i <= m_e && nf < 8; ++i) {
             if (i == m_e || name[i] == ':') { fs[nf] = a; fe[nf] = i; ++nf; a = i + 1; }
         }
-        ok = 1;
-        if (!parse_uint(name, fs[3], fe[3], lane) || !parse_uint(name, fs[4] + 1, fe[4], tile) || !parse_uint(name, fs[5], fe[5], x) ||
-            !parse_uint(name, fs[6], fe[6], y))
-            ok = 2;
+        // (all four fields are converted before any is used: one that int() rejects raises whatever the others hold)
+        bool big_id = false, big_xy = false;
+        const bool p3 = parse_int(name, fs[3], fe[3], lane, big_id), p4 = parse_int(name, fs[4] + 1, fe[4], tile, big_id);
+        const bool p5 = parse_int(name, fs[5], fe[5], x, big_xy), p6 = parse_int(name, fs[6], fe[6], y, big_xy);      // (saturated: outside)
+        ok = !(p3 && p4 && p5 && p6) ? 2 : big_id ? 0 : 1;          // a lane or tile beyond int32 is in no circle: as good as no match
     }
     lane_out[r] = lane; tile_out[r] = tile; x_out[r] = x; y_out[r] = y; ok_out[r] = ok;
 }
