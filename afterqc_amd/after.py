@@ -16,6 +16,8 @@ import sys
 import time
 from optparse import OptionParser
 
+from . import adapter_detect
+
 AFTERQC_VERSION = "0.9.6"
 USAGE = ("Automatic Filtering, Trimming, Error Removing and Quality Control for Illumina fastq data \n\n"
          "Simplest usage:\ncd to the folder containing your fastq data, run <python after.py>")
@@ -59,8 +61,8 @@ OPTIONS = [
     ("", "--cut_right", dict(default="off", help="specify whether to cut each read at the first window (from the front, or from where cut_front starts the read) whose mean quality is below cut_mean_quality, dropping that window and everything behind it. Default is off")),
     ("", "--cut_window_size", dict(default=4, type="int", help="the window size of cut_front / cut_tail / cut_right, 1 to 1000. Default is 4")),
     ("", "--cut_mean_quality", dict(default=20, type="int", help="the mean phred quality a window needs to be good, 0 to 93. Default is 20")),
-    ("", "--adapter_sequence", dict(default=None, help="the adapter of read 1, 4 to 64 letters of A, C, G, T: each read is cut at the first place where the adapter (or, at the read's tail, its first adapter_min_overlap bases or more) lies with at most one mismatch per eight compared bases. Runs inside the trim stage, after -f / -t and after cut_front / cut_tail / cut_right. By default no adapter is searched")),
-    ("", "--adapter_sequence_r2", dict(default=None, help="the adapter of read 2, by default the same as adapter_sequence; given alone, only read 2 is searched")),
+    ("", "--adapter_sequence", dict(default=None, help="the adapter of read 1, 4 to 64 letters of A, C, G, T: each read is cut at the first place where the adapter (or, at the read's tail, its first adapter_min_overlap bases or more) lies with at most one mismatch per eight compared bases. Runs inside the trim stage, after -f / -t and after cut_front / cut_tail / cut_right. 'auto' finds it in the QC sample among TruSeq, Nextera, Illumina small RNA and BGI / MGI (the first 12 bases of a candidate, in at least 10 reads and 0.1 % of the sample). By default no adapter is searched")),
+    ("", "--adapter_sequence_r2", dict(default=None, help="the adapter of read 2, or 'auto'; by default the same as adapter_sequence ('auto': found in read 2's own sample); given alone, only read 2 is searched")),
     ("", "--adapter_min_overlap", dict(default=4, type="int", help="the fewest bases of an adapter that must lie on the read for a match at its tail, 1 to the length of the shorter adapter. Default is 4")),
     ("", "--trim_poly_g", dict(default="off", help="specify whether to cut a poly-G tail from each read (a dark cycle of a two-colour instrument reads as G): from the read's end a run of G is followed while at most one base in eight, and at most five in all, is something else; a run of poly_g_min_len bases or more is cut off at its leftmost G. Runs inside the trim stage, after -f / -t, cut_front / cut_tail / cut_right and adapter_sequence. Default is off")),
     ("", "--poly_g_min_len", dict(default=10, type="int", help="the shortest poly-G tail that is cut, 1 to 1000. Default is 10")),
@@ -116,25 +118,32 @@ def finalize_options(options):
     # (a run of one single-end file, -1 without -2, has no read 2: its adapter takes no part, and given alone it is refused below
     #  and in seqFilter.run, which also sees the single-end files of a folder)
     single = options.read1_file is not None and options.read2_file is None
-    given = []
-    for k in ("adapter_sequence", "adapter_sequence_r2"):
+    given = []                                                          # the lengths --adapter_min_overlap is held to
+    for mate, k in enumerate(("adapter_sequence", "adapter_sequence_r2")):
         a = getattr(options, k)
         if a is None:
             continue
-        a = a.upper()
-        if not ADAPTER_MIN_LEN <= len(a) <= ADAPTER_MAX_LEN:
-            raise SystemExit("afterqc_amd: --%s has %d letters, outside %d .. %d" % (k, len(a), ADAPTER_MIN_LEN, ADAPTER_MAX_LEN))
-        if set(a) - set("ACGT"):
-            raise SystemExit("afterqc_amd: --%s %s holds letters other than A, C, G, T" % (k, a))
+        if adapter_detect.is_auto(a):
+            # (found in the pass-1 sample, seqFilter.run; until then the shortest candidate of the mate's column stands for it)
+            a, length = adapter_detect.AUTO, adapter_detect.shortest(mate)
+        else:
+            a = a.upper()
+            length = len(a)
+            if not ADAPTER_MIN_LEN <= len(a) <= ADAPTER_MAX_LEN:
+                raise SystemExit("afterqc_amd: --%s has %d letters, outside %d .. %d" % (k, len(a), ADAPTER_MIN_LEN, ADAPTER_MAX_LEN))
+            if set(a) - set("ACGT"):
+                raise SystemExit("afterqc_amd: --%s %s holds letters other than A, C, G, T" % (k, a))
         setattr(options, k, a)
         if not (single and k == "adapter_sequence_r2"):
-            given.append(a)
+            given.append(length)
     if single and options.adapter_sequence_r2 is not None and options.adapter_sequence is None:
         raise SystemExit("afterqc_amd: --adapter_sequence_r2 is given alone but the input is single-end (no -2): there is no read 2 to search; "
                          "give the adapter as --adapter_sequence")
     if options.adapter_sequence_r2 is None:
-        options.adapter_sequence_r2 = options.adapter_sequence          # (read 2 takes read 1's adapter)
-    shortest = min(len(a) for a in given) if given else ADAPTER_MAX_LEN
+        options.adapter_sequence_r2 = options.adapter_sequence          # (read 2 takes read 1's adapter; `auto`: its own detection)
+        if options.adapter_sequence == adapter_detect.AUTO and not single:
+            given.append(adapter_detect.shortest(1))
+    shortest = min(given) if given else ADAPTER_MAX_LEN
     if not 1 <= options.adapter_min_overlap <= shortest:
         raise SystemExit("afterqc_amd: --adapter_min_overlap %d is outside 1 .. %d%s" % (options.adapter_min_overlap, shortest,
                                                                                          " (the shorter adapter)" if given else ""))

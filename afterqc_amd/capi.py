@@ -124,6 +124,27 @@ class AdapterConfig(C.Structure):
         return bytes(self.seq1[:min(self.len1, 64)]), bytes(self.seq2[:min(self.len2, 64)])
 
 
+ADP_PROBE_LEN, ADP_MAX_PROBES = 12, 16
+
+
+class AdapterProbes(C.Structure):
+    """struct aqc_adapter_probes: the probes of the adapter census of one pre-filter file (--adapter_sequence auto), each
+    ADP_PROBE_LEN letters of ACGT"""
+    _fields_ = [("n", C.c_int32), ("seq", (C.c_uint8 * ADP_PROBE_LEN) * ADP_MAX_PROBES)]
+
+    def __init__(self, probes=()):
+        super().__init__()
+        probes = [p.encode() if isinstance(p, str) else bytes(p) for p in probes]
+        # (a number or a length the library refuses travels as it is, with the bytes that fit)
+        self.n = len(probes)
+        for i, p in enumerate(probes[:ADP_MAX_PROBES]):
+            for j, ch in enumerate(p[:ADP_PROBE_LEN]):
+                self.seq[i][j] = ch
+
+    def probes(self):
+        return [bytes(self.seq[i]) for i in range(min(max(self.n, 0), ADP_MAX_PROBES))]
+
+
 class PolyConfig(C.Structure):
     """struct aqc_poly_config: the letters whose tails are cut from each read (--trim_poly_g / --trim_poly_x) and their minimum
     lengths, in the order A, C, G, T; 0: that letter is not tried"""
@@ -410,6 +431,10 @@ def load_library():
     lib.aqc_get_adapter_stats.argtypes = [P, P]
     lib.aqc_adapter_ms.argtypes = [P, C.c_int, C.POINTER(C.c_float)]
     lib.aqc_adapter_views.argtypes = [P, C.POINTER(BatchStruct), C.POINTER(AdapterConfig), C.c_int32, C.c_int32, P, P]
+    lib.aqc_set_adapter_probes.argtypes = [P, C.c_int, C.POINTER(AdapterProbes)]
+    lib.aqc_adapter_census.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64]
+    lib.aqc_get_adapter_census.argtypes = [P, C.c_int, P]
+    lib.aqc_adapter_census_ms.argtypes = [P, C.c_int, C.POINTER(C.c_float)]
     lib.aqc_set_poly_trim.argtypes = [P, C.POINTER(PolyConfig)]
     lib.aqc_get_poly_stats.argtypes = [P, P]
     lib.aqc_poly_ms.argtypes = [P, C.c_int, C.POINTER(C.c_float)]
@@ -507,6 +532,7 @@ def load_library():
                  "aqc_fetch_text", "aqc_fetch_quality_views", "aqc_error_record", "aqc_format_spans", "aqc_fetch_span_events", "aqc_span_end", "aqc_format_fused",
                  "aqc_poly_census", "aqc_fetch_census", "aqc_census_ms", "aqc_set_quality_cut", "aqc_get_cut_stats", "aqc_cut_ms", "aqc_quality_cut_views",
                  "aqc_set_adapter_trim", "aqc_get_adapter_stats", "aqc_adapter_ms", "aqc_adapter_views",
+                 "aqc_set_adapter_probes", "aqc_adapter_census", "aqc_get_adapter_census", "aqc_adapter_census_ms",
                  "aqc_set_poly_trim", "aqc_get_poly_stats", "aqc_poly_ms", "aqc_poly_views"):
         getattr(lib, name).restype = C.c_int
     if lib.aqc_abi_version() != 3:
@@ -528,6 +554,7 @@ EXPORTED_SYMBOLS = ["aqc_abi_version", "aqc_device_count", "aqc_device_index", "
                     "aqc_gz_deflate_block", "aqc_gz_inflate_raw", "aqc_gz_crc32",
                     "aqc_set_quality_cut", "aqc_get_cut_stats", "aqc_cut_ms", "aqc_quality_cut_views",
                     "aqc_set_adapter_trim", "aqc_get_adapter_stats", "aqc_adapter_ms", "aqc_adapter_views",
+                    "aqc_set_adapter_probes", "aqc_adapter_census", "aqc_get_adapter_census", "aqc_adapter_census_ms",
                     "aqc_set_poly_trim", "aqc_get_poly_stats", "aqc_poly_ms", "aqc_poly_views",
                     # the reference's own native seam (editdistance/_editdistance.h:16,23), same names and signatures
                     "edit_distance", "seek_overlap"]
@@ -618,6 +645,27 @@ class Engine:
     def adapter_ms(self, slot):
         """device time of the adapter pass of the slot's last run(); 0.0: it launched none"""
         return self._pass_ms(self.lib.aqc_adapter_ms, slot)
+
+    def set_adapter_probes(self, which, probes):
+        """the probes of the adapter census of one pre-filter file (which: QC_R1_PRE / QC_R2_PRE): a list of ADP_PROBE_LEN-letter
+        strings or an AdapterProbes, or None (off).  The file's counts start at zero."""
+        if probes is not None and not isinstance(probes, AdapterProbes):
+            probes = AdapterProbes(probes)
+        self._check(self.lib.aqc_set_adapter_probes(self.h, which, C.byref(probes) if probes is not None else None))
+
+    def adapter_census(self, slot, which, mate, first, count):
+        """records [first, first + count) of the slot, their read 1 / read 2 (mate), added to the census of `which`"""
+        self._check(self.lib.aqc_adapter_census(self.h, slot, which, mate, first, count))
+
+    def adapter_census_counts(self, which):
+        """[0] reads looked at, [1 + i] reads that hold probe i"""
+        out = np.zeros(1 + ADP_MAX_PROBES, dtype=np.int64)
+        self._check(self.lib.aqc_get_adapter_census(self.h, which, _ptr(out)))
+        return out
+
+    def adapter_census_ms(self, slot):
+        """device time of the slot's last adapter_census(); 0.0: it launched nothing"""
+        return self._pass_ms(self.lib.aqc_adapter_census_ms, slot)
 
     def set_poly_trim(self, poly):
         """poly: a PolyConfig, or None (off).  With every length 0 nothing of the pass runs."""

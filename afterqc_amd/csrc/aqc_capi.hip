@@ -220,6 +220,7 @@ void aqc_destroy(aqc_ctx* c) {
             }
         if (s.status) (void)hipFree(s.status);
         for (hipEvent_t e : s.census_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : s.adp_census_ev) if (e) (void)hipEventDestroy(e);
         for (ViewPass& vp : s.pass)
             for (hipEvent_t e : vp.ev) if (e) (void)hipEventDestroy(e);
         if (s.ev_main) (void)hipEventDestroy(s.ev_main);
@@ -229,6 +230,7 @@ void aqc_destroy(aqc_ctx* c) {
     if (c->qc_stream) (void)hipStreamDestroy(c->qc_stream);
     (void)hipFree(c->counters); (void)hipFree(c->ovl_hist); (void)hipFree(c->dist_hist);
     for (PassCounts& pc : c->pass_stats) pc.free();
+    for (AdpCensus& ac : c->adp_census) ac.free();
     for (int k = 0; k < 4; k++) {
         (void)hipFree(c->qc[k].acc);
         free_kmer(c->qc[k].kt);
@@ -392,6 +394,7 @@ int aqc_reset_stats(aqc_ctx* c) {
     HIP_TRY(hipMemset(c->ovl_hist, 0, sizeof(unsigned long long) * AQC_QC_COLS));
     HIP_TRY(hipMemset(c->dist_hist, 0, sizeof(unsigned long long) * AQC_QC_COLS));
     for (PassCounts& pc : c->pass_stats) HIP_TRY(pc.zero());
+    for (AdpCensus& ac : c->adp_census) HIP_TRY(ac.zero());
     for (auto& sl : c->slots) { HIP_TRY(hipMemcpy(sl.status, &STATUS_CLEAR, sizeof(STATUS_CLEAR), hipMemcpyHostToDevice)); sl.err_record = UINT64_MAX; }
     for (int k = 0; k < 4; k++) {
         HIP_TRY(hipMemset(c->qc[k].acc, 0, sizeof(unsigned long long) * AQC_QC_ROWS * AQC_QC_COLS));

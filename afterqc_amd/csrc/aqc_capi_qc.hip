@@ -1,8 +1,10 @@
 // aqc_capi_qc.hip — the C API's statRead stage: the k-mer tables of a context (built on first use, freed with it), aqc_qc_stat, and
-// the getters of what it accumulates (aqc_get_qc, aqc_get_kmers).  The context, its slots and the shared helpers: aqc_ctx.hpp.
+// the getters of what it accumulates (aqc_get_qc, aqc_get_kmers); and the second census of the same pass-1 sample, the adapter
+// census (aqc_set_adapter_probes, aqc_adapter_census and its getters).  The context, its slots and the shared helpers: aqc_ctx.hpp.
 //
-// Kernels launched here, and nowhere else (this is the one unit that includes aqc_qcstat.hpp):
-//   qc_stat_kernel, kmer_count_kernel, kmer_reduce_kernel, kmer_compact_kernel, kmer_compact_dense_kernel
+// Kernels launched here, and nowhere else (this is the one unit that includes aqc_qcstat.hpp, and the one that instantiates
+// aqc_adpcensus.hpp's kernel):
+//   qc_stat_kernel, kmer_count_kernel, kmer_reduce_kernel, kmer_compact_kernel, kmer_compact_dense_kernel, adapter_census_kernel<G>
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -186,6 +188,71 @@ int aqc_get_kmers(aqc_ctx* c, int which, uint64_t* keys, int64_t* counts, uint64
     }
     *n = m;
     if (m > dcap) return fail(AQC_ERR_ARG, "aqc_get_kmers: %llu entries exceed cap %llu", m, (unsigned long long)dcap);
+    return 0;
+}
+
+// ---- the adapter census (aqc_adpcensus.hpp) ----------------------------------------------------------------------------
+static_assert(AQC_ADP_PROBE_LEN == CEN_PROBE_LEN && AQC_ADP_MAX_PROBES == CEN_MAX_PROBES, "the C API's probes fill the kernel's");
+
+static bool census_which(int which) { return which == AQC_QC_R1_PRE || which == AQC_QC_R2_PRE; }
+
+// the probes of one pre-filter file (NULL: off); the file's counts start at zero
+int aqc_set_adapter_probes(aqc_ctx* c, int which, const aqc_adapter_probes* probes) {
+    if (!c || !census_which(which)) return fail(AQC_ERR_ARG, "aqc_set_adapter_probes: null context or `which` is no pre-filter file");
+    AdpCensus& ac = c->adp_census[which];
+    CensusProbes p{};
+    if (probes && !cen_from_letters(probes->n, probes->seq, p))
+        return fail(AQC_ERR_ARG, "aqc_set_adapter_probes: %d probes (1 .. %d, each %d letters of ACGT)", probes->n, CEN_MAX_PROBES, CEN_PROBE_LEN);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());                 // (a census of the probes that go may still count)
+    if (probes) HIP_TRY(ac.ensure(c->device));
+    HIP_TRY(ac.zero());
+    ac.probes = p;
+    return 0;
+}
+
+int aqc_adapter_census(aqc_ctx* c, int slot, int which, int mate, uint64_t first, uint64_t count) {
+    GET_SLOT(s);
+    if (!census_which(which) || mate < 0 || mate > 1) return fail(AQC_ERR_ARG, "aqc_adapter_census: bad which/mate");
+    AdpCensus& ac = c->adp_census[which];
+    if (ac.probes.n == 0) return fail(AQC_ERR_STATE, "aqc_adapter_census before aqc_set_adapter_probes");
+    if (first > s->n || count > s->n - first) return fail(AQC_ERR_ARG, "aqc_adapter_census: range exceeds the slot's %llu records", (unsigned long long)s->n);
+    if (mate == 1 && !s->paired) return fail(AQC_ERR_ARG, "aqc_adapter_census: mate 1 of a single-end slot");
+    s->adp_census_ran = false;
+    if (count == 0) return 0;
+    // on the slot's own stream, behind what filled it: the statRead kernels of the same records run beside it on the QC stream
+    CensusArgs A{};
+    A.seq = mate ? s->view.seq2 : s->view.seq1; A.off = mate ? s->view.off2 : s->view.off1; A.len = mate ? s->view.len2 : s->view.len1;
+    A.first = first; A.count = count; A.acc = ac.acc; A.status = s->status; A.probes = ac.probes;
+    for (hipEvent_t& e : s->adp_census_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(s->adp_census_ev[0], s->stream));
+    vp_dispatch(view_pass_lanes(*s), count, c->n_cu, [&](auto G, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(adapter_census_kernel<decltype(G)::value>, grid, block, 0, s->stream, A);
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s->adp_census_ev[1], s->stream));
+    s->adp_census_ran = true;
+    return 0;
+}
+
+int aqc_get_adapter_census(aqc_ctx* c, int which, int64_t out[1 + AQC_ADP_MAX_PROBES]) {
+    if (!c || !out || !census_which(which)) return fail(AQC_ERR_ARG, "aqc_get_adapter_census: null argument or `which` is no pre-filter file");
+    int rc = sync_all(c);
+    if (rc) return rc;
+    for (int k = 0; k < CEN_COUNTS; ++k) out[k] = 0;
+    if (c->adp_census[which].acc) HIP_TRY(hipMemcpy(out, c->adp_census[which].acc, sizeof(int64_t) * CEN_COUNTS, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// device time of the slot's last aqc_adapter_census; 0: it launched nothing
+int aqc_adapter_census_ms(aqc_ctx* c, int slot, float* ms) {
+    GET_SLOT(s);
+    if (!ms) return fail(AQC_ERR_ARG, "aqc_adapter_census_ms: null argument");
+    *ms = 0.f;
+    if (!s->adp_census_ran) return 0;
+    HIP_TRY(slot_sync(*s));
+    HIP_TRY(hipEventElapsedTime(ms, s->adp_census_ev[0], s->adp_census_ev[1]));
     return 0;
 }
 

@@ -276,13 +276,6 @@ static int prepare_fuse(Slot& s, FuseArgs& fz) {
     return 0;
 }
 
-// lanes per read of the passes in front of the verdict kernel, by the slot's longest line: a quality line of its own length (or a
-// length nobody has looked at) may be anything up to AQC_MAX_READ_LEN
-static int view_pass_lanes(const Slot& s) {
-    const uint32_t longest = (s.has_irregular || s.raw_max_len == 0) ? (uint32_t)AQC_MAX_READ_LEN : s.raw_max_len;
-    return longest <= 128 ? 8 : longest <= 256 ? 16 : longest <= 512 ? 32 : 64;
-}
-
 // ---- the quality cut's pass (aqc_qcut.hpp): one view per mate and record into `view` (n_mates per record), the four counts into `stats` (may be NULL)
 static int launch_cut(aqc_ctx* c, Slot& s, const QcutOpts& o, const int32_t trim_front[2], const int32_t trim_tail[2], int n_mates, uint32_t* view,
                       unsigned long long* stats, uint64_t accum_limit) {

@@ -15,6 +15,7 @@
 #include "aqc_qcut.hpp"
 #include "aqc_adapter.hpp"
 #include "aqc_polytail.hpp"
+#include "aqc_adpcensus.hpp"
 
 namespace aqc {
 
@@ -120,6 +121,10 @@ struct __attribute__((visibility("hidden"))) Slot {
     uint64_t n_census = 0;
     hipEvent_t census_ev[2] = {nullptr, nullptr};   // around the census kernels of the last aqc_poly_census (aqc_census_ms)
 
+    // ---- the adapter census of pass 1 (aqc_capi_qc.hip) ----
+    hipEvent_t adp_census_ev[2] = {nullptr, nullptr};   // around the kernel of the slot's last aqc_adapter_census (aqc_adapter_census_ms) ...
+    bool adp_census_ran = false;                        // ... if there was one
+
     // ---- .gz out (aqc_capi_run.hip: it is compiled beside the verdict kernels, see there) ----
     // gzip members built on the device (aqc_compress)
     DevBuf g_stage, g_sizes, g_offsets, g_total, g_hist, g_code, g_packed[6];
@@ -141,6 +146,22 @@ struct __attribute__((visibility("hidden"))) QcDev {
     unsigned long long last_end = 0, epoch = 0;
 };
 
+// The adapter census of one pre-filter file (AQC_QC_R1_PRE / AQC_QC_R2_PRE): the probes aqc_set_adapter_probes gave (n 0: none) and
+// the counts on the device, [0] reads looked at, [1 + i] reads that hold probe i.  Allocated when probes are first set: a context
+// that never asks for the census allocates what it always did.
+struct __attribute__((visibility("hidden"))) AdpCensus {
+    CensusProbes probes{};
+    unsigned long long* acc = nullptr;
+    hipError_t ensure(int device) {
+        if (acc) return hipSuccess;
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = hipMalloc((void**)&acc, sizeof(unsigned long long) * CEN_COUNTS);
+        return e;
+    }
+    hipError_t zero() { return acc ? hipMemset(acc, 0, sizeof(unsigned long long) * CEN_COUNTS) : hipSuccess; }
+    void free() { if (acc) (void)hipFree(acc); acc = nullptr; }
+};
+
 }  // namespace aqc
 
 struct __attribute__((visibility("hidden"))) aqc_ctx {
@@ -156,6 +177,7 @@ struct __attribute__((visibility("hidden"))) aqc_ctx {
     aqc::AdapterOpts adapter{};        // aqc_set_adapter_trim: the adapters to trim (both lengths 0: off, no kernel of it is launched)
     aqc::PolyOpts poly{};              // aqc_set_poly_trim: the letters whose tails are cut (every length 0: off, no kernel of it is launched)
     aqc::PassCounts pass_stats[aqc::VP_N];
+    aqc::AdpCensus adp_census[2];      // aqc_set_adapter_probes: the census of read 1's / read 2's pre-filter sample (no probes: no kernel of it is launched)
     aqc::DevBuf circ[5];
     aqc::DevBuf kmer_partial;          // per-round u16 count slices of kmer_count_kernel
     aqc::DevBuf gz_crc;                // GzCrcTables (aqc_compress)
@@ -188,6 +210,12 @@ AQC_INTERNAL int check_status(Slot& sl);
 AQC_INTERNAL int get_slot(aqc_ctx* c, int slot, Slot** out);
 AQC_INTERNAL int fetch_out(Slot& s, const void* src, uint64_t bytes, void* dst, uint64_t cap, const char* who);
 AQC_INTERNAL int sync_all(aqc_ctx* c);
+// lanes per read of a pass in the frame of aqc_viewpass.hpp, by the slot's longest line: a quality line of its own length (or a
+// length nobody has looked at) may be anything up to AQC_MAX_READ_LEN
+static inline int view_pass_lanes(const Slot& s) {
+    const uint32_t longest = (s.has_irregular || s.raw_max_len == 0) ? (uint32_t)AQC_MAX_READ_LEN : s.raw_max_len;
+    return longest <= 128 ? 8 : longest <= 256 ? 16 : longest <= 512 ? 32 : 64;
+}
 // aqc_capi_qc.hip, for aqc_create / aqc_destroy: the LDS the k-mer kernel may ask for; a context's k-mer tables freed
 AQC_INTERNAL int allow_kmer_lds();
 AQC_INTERNAL void free_kmer(KmerTable& t);

@@ -31,7 +31,7 @@ import time
 
 import numpy as np
 
-from . import capi, fastq
+from . import adapter_detect, capi, fastq
 from .qc import QualityControl, ALL_BASES
 
 FLAG_BYTES = [b"", b"BADBCD1", b"BADBCD2", b"BADTRIM1", b"BADTRIM2", b"BADBBL", b"BADLEN", b"BADPOL", b"BADLQC",
@@ -108,11 +108,19 @@ def cut_config(opt):
     return capi.CutConfig(int(modes[0]), int(modes[1]), int(modes[2]), int(getattr(opt, "cut_window_size", 4)), int(getattr(opt, "cut_mean_quality", 20)))
 
 
-def adapter_config(opt):
+def adapter_auto(opt):
+    """which mates' adapters are to be found in the pass-1 sample (--adapter_sequence auto / --adapter_sequence_r2 auto) -> (read 1,
+    read 2); single-end input has no read 2"""
+    a1, a2 = (adapter_detect.is_auto(getattr(opt, k, None)) for k in ("adapter_sequence", "adapter_sequence_r2"))
+    return a1, a2 and getattr(opt, "read2_file", None) is not None
+
+
+def adapter_config(opt, found=("", "")):
     """--adapter_sequence / --adapter_sequence_r2 / --adapter_min_overlap as the engine takes them; None: no adapter is given
-    (options objects built without the adapter options count as off).  Single-end input has no read 2 to search."""
-    a1 = getattr(opt, "adapter_sequence", None) or ""
-    a2 = getattr(opt, "adapter_sequence_r2", None) or ""
+    (options objects built without the adapter options count as off).  Single-end input has no read 2 to search.  A mate whose
+    option says `auto` takes what was found for it; nothing found, or nothing looked for yet: it is not searched."""
+    given = [getattr(opt, k, None) or "" for k in ("adapter_sequence", "adapter_sequence_r2")]
+    a1, a2 = (f if adapter_detect.is_auto(a) else a for a, f in zip(given, found))
     if getattr(opt, "read2_file", None) is None:
         a2 = ""
     if not a1 and not a2:
@@ -452,7 +460,9 @@ class seqFilter:
         self.bubbleCircles = []
         self.stat = None
         self.cut = cut_config(opt)
-        self.adapter = adapter_config(opt)
+        self.adapter = adapter_config(opt)           # (a mate that says `auto` is not searched until run() has looked at the sample)
+        self.adapter_auto = adapter_auto(opt)
+        self.adapter_detect = None                   # what the census found, as the statistics JSON says it
         self.poly = poly_config(opt)
 
     # ---- helpers ---------------------------------------------------------------------------------
@@ -494,11 +504,11 @@ class seqFilter:
             # (the barcode stage moves the view before the trim stage: that combination is not implemented; refused before anything is created)
             raise SystemExit("afterqc_amd: --cut_front / --cut_tail / --cut_right are not implemented for barcoded input "
                              "(%s); run it with --barcode off or without the cut" % opt.read1_file)
-        if self.adapter is None and getattr(opt, "adapter_sequence_r2", None) and not self.paired:
+        if not self.paired and not getattr(opt, "adapter_sequence", None) and getattr(opt, "adapter_sequence_r2", None):
             # (never a silent run without the option: only read 2's adapter is given and this input has no read 2)
             raise SystemExit("afterqc_amd: --adapter_sequence_r2 is given alone but %s is single-end: there is no read 2 to search; "
                              "give the adapter as --adapter_sequence" % opt.read1_file)
-        if opt.barcode and self.adapter is not None:
+        if opt.barcode and (self.adapter is not None or any(self.adapter_auto)):
             raise SystemExit("afterqc_amd: --adapter_sequence / --adapter_sequence_r2 are not implemented for barcoded input "
                              "(%s); run it with --barcode off or without the adapter" % opt.read1_file)
         if opt.barcode and self.poly is not None:
@@ -517,6 +527,7 @@ class seqFilter:
         r1pre, r2pre = self._sample(eng)
         self.timing["pass1_s"] = time.perf_counter() - t_run
         self._auto_trim(r1pre, r2pre)
+        self._detect_adapters(eng)
         print(opt.read1_file + " options:")
         print(opt)
         qc_dir, gzip_out, paths = self._layout()
@@ -554,8 +565,16 @@ class seqFilter:
     def _sample(self, eng):
         """Pass 1: pre-filter QC on a sample of each file (preprocesser.py:247-251) -> the QC objects of R1 and R2."""
         opt = self.options
-        r1pre = QualityControl(opt.qc_sample, opt.qc_kmer, eng, capi.QC_R1_PRE)
-        r2pre = QualityControl(opt.qc_sample, opt.qc_kmer, eng, capi.QC_R2_PRE)
+        # --adapter_sequence auto: the census of the same reads, with the probes of the mate's column.  Without it nothing of the
+        # census is called (probes an engine the caller handed over still has from another run are never looked at)
+        if any(self.adapter_auto):
+            if not hasattr(eng, "adapter_census"):
+                raise RuntimeError("afterqc_amd: --adapter_sequence auto / --adapter_sequence_r2 auto need an engine with adapter_census; "
+                                   "%s has none" % type(eng).__name__)
+            for mate, which in enumerate((capi.QC_R1_PRE, capi.QC_R2_PRE)):
+                eng.set_adapter_probes(which, adapter_detect.probes(mate) if self.adapter_auto[mate] else None)
+        r1pre = QualityControl(opt.qc_sample, opt.qc_kmer, eng, capi.QC_R1_PRE, census=self.adapter_auto[0])
+        r2pre = QualityControl(opt.qc_sample, opt.qc_kmer, eng, capi.QC_R2_PRE, census=self.adapter_auto[1])
         if not (self.use_text_path and hasattr(eng, "frame")):
             r1pre.statFile(opt.read1_file, fastq.Reader, capi.Batch.from_raw, self.batch_records)
             if self.paired:
@@ -602,6 +621,29 @@ class seqFilter:
                 opt.trim_front2 = tf2
             if opt.trim_tail2 == -1:
                 opt.trim_tail2 = tt2
+
+    def _detect_adapters(self, eng):
+        """--adapter_sequence auto: each asked mate's adapter from the census of its pass-1 sample (adapter_detect) -> self.adapter
+        as pass 2 runs it, self.adapter_detect for the statistics.  Nothing found for any mate and none given: no adapter pass."""
+        if not any(self.adapter_auto):
+            return
+        opt = self.options
+        n = len(adapter_detect.CANDIDATES)
+        self.adapter_detect = {"probe_len": adapter_detect.PROBE_LEN, "min_reads": adapter_detect.MIN_READS,
+                               "min_per_mille": adapter_detect.MIN_PER_MILLE}
+        found = ["", ""]
+        for mate, which in enumerate((capi.QC_R1_PRE, capi.QC_R2_PRE)):
+            if not self.adapter_auto[mate]:
+                continue
+            counts = [int(v) for v in eng.adapter_census_counts(which)]
+            rep = adapter_detect.report(mate, counts[1:1 + n], counts[0])
+            self.adapter_detect["read%d" % (mate + 1)] = rep
+            found[mate] = rep["adapter"]
+            held = dict(rep["candidates"]).get(rep["detected"], 0)
+            print("%s: read %d adapter %s" % (opt.read2_file if mate else opt.read1_file, mate + 1,
+                                              "%s %s (in %d of %d sampled reads)" % (rep["detected"], rep["adapter"], held, rep["sampled"])
+                                              if rep["detected"] else "not detected in %d sampled reads: not searched" % rep["sampled"]))
+        self.adapter = adapter_config(opt, found)
 
     def _layout(self):
         """Output layout (preprocesser.py:285-371): makes the folders -> (report folder, gzip the outputs?, per input file
@@ -1064,6 +1106,8 @@ class seqFilter:
                 'adapter_sequence': a1.decode(), 'adapter_sequence_r2': a2.decode(), 'adapter_min_overlap': int(self.adapter.min_overlap),
                 'read1_trimmed_reads': n[0], 'read1_trimmed_bases': n[1], 'read2_trimmed_reads': n[2], 'read2_trimmed_bases': n[3],
             }
+        if self.adapter_detect is not None:
+            stat["adapter_detect"] = self.adapter_detect
         if self.poly is not None:
             n = [int(v) for v in eng.poly_stats()]
             stat["poly_trim"] = {

@@ -44,9 +44,10 @@ class _KmerView:
 class QualityControl:
     """One of the four QC objects of preprocesser.py:247-254, backed by a device accumulator block."""
 
-    def __init__(self, qc_sample, qc_kmer, engine, which):
+    def __init__(self, qc_sample, qc_kmer, engine, which, census=False):
         self.engine = engine
         self.which = which
+        self.census = census            # the adapter census (--adapter_sequence auto) looks at every read statRead looks at
         self.sampleLimit = qc_sample
         self.kmerLen = qc_kmer
         self.readCount = 0
@@ -183,6 +184,8 @@ class QualityControl:
 
     def _stat(self, slot, first, count):
         self.engine.qc_stat(slot, self.which, 0, first, count, 0)
+        if self.census:
+            self.engine.adapter_census(slot, self.which, 0, first, count)
         self.engine.sync(slot)
 
     def _clip(self, seen, n):

@@ -263,6 +263,26 @@ int aqc_get_adapter_stats(aqc_ctx* ctx, int64_t out[4]);
 /* device time of the adapter pass of the slot's last aqc_run (HIP events on the slot's stream); 0: it launched none */
 int aqc_adapter_ms(aqc_ctx* ctx, int slot, float* ms);
 
+/* ---- finding a mate's adapter in the pass-1 sample (--adapter_sequence auto) ------------------- */
+/* A second census over the reads aqc_qc_stat sees, before pass 2 is configured: a read HOLDS a probe of 12 letters of A C G T when
+ * the 12 bytes stand somewhere in its raw SEQUENCE line (the line before any trim), byte for byte — any place 0 .. n - 12, an N or a
+ * lower-case letter is no match, a read under 12 bases holds nothing, a read that holds a probe twice counts once for it.  The
+ * counts are kept per pre-filter file (`which`: AQC_QC_R1_PRE or AQC_QC_R2_PRE) in device memory; what is done with them — which
+ * candidate a probe stands for, when one is detected — is the caller's (tests/detect_rule.py). */
+#define AQC_ADP_PROBE_LEN 12
+#define AQC_ADP_MAX_PROBES 16
+typedef struct aqc_adapter_probes { int32_t n; uint8_t seq[16][12]; } aqc_adapter_probes;
+/* the probes of one file, n of 1 .. 16; NULL: off.  Zeroes the file's counts.  A bad n, a letter outside A C G T: AQC_ERR_ARG. */
+int aqc_set_adapter_probes(aqc_ctx* ctx, int which /* AQC_QC_R1_PRE | AQC_QC_R2_PRE */, const aqc_adapter_probes* probes);
+/* records [first, first + count) of the slot's batch, their read 1 (mate 0) or read 2 (mate 1), added to the counts of `which`; on
+ * the slot's stream.  Without probes set: AQC_ERR_STATE.  A line longer than AQC_MAX_READ_LEN holds nothing and raises
+ * AQC_ERR_READ_TOO_LONG at the slot's next wait. */
+int aqc_adapter_census(aqc_ctx* ctx, int slot, int which, int mate, uint64_t first, uint64_t count);
+/* out[0]: reads looked at, out[1 + i]: reads that hold probe i.  Zeroed by aqc_set_adapter_probes and aqc_reset_stats. */
+int aqc_get_adapter_census(aqc_ctx* ctx, int which, int64_t out[1 + AQC_ADP_MAX_PROBES]);
+/* device time of the slot's last aqc_adapter_census (HIP events on the slot's stream); 0: it launched nothing */
+int aqc_adapter_census_ms(aqc_ctx* ctx, int slot, float* ms);
+
 /* ---- cutting poly-G / poly-X tails from each read (--trim_poly_g / --trim_poly_x) -------------- */
 /* Inside the same trim stage, behind the fixed trim, the quality cut and the adapter pass: let s be the part of a mate's SEQUENCE
  * line that those keep, n its length.  For a letter X with minimum length L, mm(u) is the number of bytes among the last u of s
