@@ -622,9 +622,24 @@ class Engine:
         self._check(getter(self.h, slot, C.byref(ms)))
         return float(ms.value)
 
+    def _set_pass(self, setter, config):
+        self._check(setter(self.h, C.byref(config) if config is not None else None))
+
+    def _views(self, seam, batch, config, trim_front, trim_tail, *view_in):
+        """a view pass alone on read 1 of the batch -> (c0, c1) arrays.  *view_in, for a pass that takes views: the (c0, c1) arrays
+        the reads come with, or None (everything)"""
+        v = np.zeros(batch.n, dtype=np.uint32)
+        vin = [w if w is None else (np.asarray(w[0], dtype=np.uint32) | (np.asarray(w[1], dtype=np.uint32) << 16)).astype(np.uint32)
+               for w in view_in]
+        assert all(w is None or w.shape == (batch.n,) for w in vin)
+        s = batch.as_struct()
+        self._check(seam(self.h, C.byref(s), C.byref(config), int(trim_front), int(trim_tail),
+                         *[w if w is None else _ptr(w) for w in vin], _ptr(v)))
+        return (v & 0xffff).astype(np.int64), (v >> 16).astype(np.int64)
+
     def set_quality_cut(self, cut):
         """cut: a CutConfig, or None (off).  With no mode set nothing of the cut runs."""
-        self._check(self.lib.aqc_set_quality_cut(self.h, C.byref(cut) if cut is not None else None))
+        self._set_pass(self.lib.aqc_set_quality_cut, cut)
 
     def cut_stats(self):
         """reads of R1 the cut made shorter, bases it removed from them, the same for R2"""
@@ -636,7 +651,7 @@ class Engine:
 
     def set_adapter_trim(self, adapter):
         """adapter: an AdapterConfig, or None (off).  With both adapters empty nothing of the pass runs."""
-        self._check(self.lib.aqc_set_adapter_trim(self.h, C.byref(adapter) if adapter is not None else None))
+        self._set_pass(self.lib.aqc_set_adapter_trim, adapter)
 
     def adapter_stats(self):
         """reads of R1 the adapter made shorter, bases it removed from them, the same for R2"""
@@ -669,7 +684,7 @@ class Engine:
 
     def set_poly_trim(self, poly):
         """poly: a PolyConfig, or None (off).  With every length 0 nothing of the pass runs."""
-        self._check(self.lib.aqc_set_poly_trim(self.h, C.byref(poly) if poly is not None else None))
+        self._set_pass(self.lib.aqc_set_poly_trim, poly)
 
     def poly_stats(self):
         """reads of R1 the poly-tail pass made shorter, bases it removed from them, the same for R2"""
@@ -877,36 +892,17 @@ class Engine:
 
     def quality_cut_views(self, batch, cut, trim_front=0, trim_tail=0):
         """cut_window() of trim(qual1) for every read of the batch -> (c0, c1) arrays"""
-        v = np.zeros(batch.n, dtype=np.uint32)
-        s = batch.as_struct()
-        self._check(self.lib.aqc_quality_cut_views(self.h, C.byref(s), C.byref(cut), int(trim_front), int(trim_tail), _ptr(v)))
-        return (v & 0xffff).astype(np.int64), (v >> 16).astype(np.int64)
+        return self._views(self.lib.aqc_quality_cut_views, batch, cut, trim_front, trim_tail)
 
     def adapter_views(self, batch, adapter, trim_front=0, trim_tail=0, view_in=None):
         """the adapter pass alone on read 1 of the batch -> (c0, c1) arrays; view_in: (c0, c1) arrays of the views the reads come
         with (a quality cut's), None: everything"""
-        v = np.zeros(batch.n, dtype=np.uint32)
-        vin = None
-        if view_in is not None:
-            vin = (np.asarray(view_in[0], dtype=np.uint32) | (np.asarray(view_in[1], dtype=np.uint32) << 16)).astype(np.uint32)
-            assert vin.shape == (batch.n,)
-        s = batch.as_struct()
-        self._check(self.lib.aqc_adapter_views(self.h, C.byref(s), C.byref(adapter), int(trim_front), int(trim_tail),
-                                               _ptr(vin) if vin is not None else None, _ptr(v)))
-        return (v & 0xffff).astype(np.int64), (v >> 16).astype(np.int64)
+        return self._views(self.lib.aqc_adapter_views, batch, adapter, trim_front, trim_tail, view_in)
 
     def poly_views(self, batch, poly, trim_front=0, trim_tail=0, view_in=None):
         """the poly-tail pass alone on read 1 of the batch -> (c0, c1) arrays; view_in: (c0, c1) arrays of the views the reads come
         with (an earlier pass's), None: everything"""
-        v = np.zeros(batch.n, dtype=np.uint32)
-        vin = None
-        if view_in is not None:
-            vin = (np.asarray(view_in[0], dtype=np.uint32) | (np.asarray(view_in[1], dtype=np.uint32) << 16)).astype(np.uint32)
-            assert vin.shape == (batch.n,)
-        s = batch.as_struct()
-        self._check(self.lib.aqc_poly_views(self.h, C.byref(s), C.byref(poly), int(trim_front), int(trim_tail),
-                                            _ptr(vin) if vin is not None else None, _ptr(v)))
-        return (v & 0xffff).astype(np.int64), (v >> 16).astype(np.int64)
+        return self._views(self.lib.aqc_poly_views, batch, poly, trim_front, trim_tail, view_in)
 
     def edit_distance(self, batch):
         d = np.zeros(batch.n, dtype=np.int32)
@@ -1173,24 +1169,18 @@ class MergedEngines:
     def __init__(self, engines):
         self.engines = list(engines)
 
-    def counters(self):
-        return sum(e.counters() for e in self.engines)
+    def _sum(self, what, *args):
+        return sum(getattr(e, what)(*args) for e in self.engines)
 
-    def cut_stats(self):
-        return sum(e.cut_stats() for e in self.engines)
-
-    def adapter_stats(self):
-        return sum(e.adapter_stats() for e in self.engines)
-
-    def poly_stats(self):
-        return sum(e.poly_stats() for e in self.engines)
+    def counters(self): return self._sum("counters")
+    def cut_stats(self): return self._sum("cut_stats")
+    def adapter_stats(self): return self._sum("adapter_stats")
+    def poly_stats(self): return self._sum("poly_stats")
+    def qc(self, which): return self._sum("qc", which)
 
     def histograms(self, n=AQC_QC_COLS):
         hs = [e.histograms(n) for e in self.engines]
         return sum(h[0] for h in hs), sum(h[1] for h in hs)
-
-    def qc(self, which):
-        return sum(e.qc(which) for e in self.engines)
 
     def kmers(self, which, cap=1 << 22):
         return merge_kmer_parts([e.kmers(which, cap) for e in self.engines])

@@ -7,9 +7,8 @@
 // The frame — lanes per read, the 16-byte load, the view word, the counts — is that of every view pass: aqc_viewpass.hpp.  Here:
 //
 //   line     the sequence line, its 16 bytes per lane stored into the LDS row of the group; the bytes behind the line, and the 80
-//            bytes behind the row that a comparison at the tail reaches, are 0 — no base.  The length comes from the length word
-//            (its LEN_IRR mark taken off: no address is formed with it), the part [c0, c1) of the trimmed line from the view that
-//            comes in — the quality cut's when a cut is on, else VIEW_ALL.
+//            bytes behind the row that a comparison at the tail reaches, are 0 — no base.  Where the line lies and how long it is
+//            behind trim() and the view that comes in — the quality cut's when a cut is on, else VIEW_ALL — vp_line says.
 //   adapter  both adapters travel in the kernel's by-value arguments, 16 dwords each.  The mate in turn has its 16 dwords in scalar
 //            registers, fetched from the argument segment by one s_load_dwordx16 per mate and round: with both mates' 32 dwords
 //            live at once the kernel spills 56 scalar registers.  There is no table in device memory.
@@ -124,13 +123,6 @@ VP_HD int adp_lane_first(const uint32_t* row, int n, const uint32_t (&A)[ADP_WOR
     return best;
 }
 
-// the view a mate leaves the pass with: the one it came with, ended at its first match
-VP_HD uint32_t adp_view(uint32_t view_in, int p) {
-    if (p == ADP_NONE) return view_in;
-    const int c0 = view_c0(view_in);
-    return view_word(c0, c0 + p);
-}
-
 }  // namespace aqc
 
 #if defined(__HIPCC__)
@@ -138,12 +130,9 @@ VP_HD uint32_t adp_view(uint32_t view_in, int p) {
 
 namespace aqc {
 
-// what the pass takes of one mate: its sequence lines, its fixed trim (aqc_config::trim_front / trim_front2, ...) and its adapter,
-// side by side so that the mate in turn is one scalar base
+// what the pass takes of one mate: its line (ViewMate) and its adapter, side by side so that the mate in turn is one scalar base
 struct AdapterMate {
-    const uint8_t* seq;
-    const uint32_t *off, *len;
-    int32_t trim_front, trim_tail;
+    ViewMate v;
     int32_t alen, pad_;                        // adapter length, 0: the mate is not searched
     uint32_t w[ADP_WORDS];                     // AdapterOpts::w of the mate
 };
@@ -199,24 +188,17 @@ __global__ __launch_bounds__(VP_THREADS) void adapter_cut_kernel(AdapterArgs K) 
         const bool have = rec < n_rec;
         bool r1_kept = true;                        // read 1 leaves the trim stage with 5 bases or more: read 2 is trimmed and cut too
         for (int k = 0; k < nm; ++k) {
-            // ---- the read: where, how long behind trim() and the quality cut
+            // ---- the read: where, how long behind trim() and the passes in front
             const AdapterMate& M = K.m[k];
-            int L = have ? (int)(M.len[rec] & LEN_MASK) : 0;
-            const bool too_long = vp_too_long<G>(L);
-            if (!have || too_long) L = 0;
-            uint32_t vin = VIEW_ALL;
             const uint32_t vi = (uint32_t)rec * (uint32_t)nm + (uint32_t)k;       // (a slot holds fewer than 2^31 records)
-            if (have && K.view_in) vin = K.view_in[vi];
-            int t0, tl, s0, n;
-            vp_trim(L, M.trim_front, M.trim_tail, t0, tl);
-            view_slice(tl, vin, s0, n);
+            const auto [too_long, vin, start, n] = vp_line<G>(M.v, rec, have, K.view_in, vi);
             const int m = M.alen;
             int p = ADP_NONE;
             if (m > 0) {                            // (wave-uniform)
                 // ---- 16 bytes per lane into the group's row
                 const int nvalid = vp_nvalid(n, g);
                 const uint8_t* s = nullptr;
-                if (nvalid > 0) s = M.seq + M.off[rec] + (t0 + s0);        // (no off[rec] behind the batch's last record)
+                if (nvalid > 0) s = M.v.seq + M.v.off[rec] + start;        // (no off[rec] behind the batch's last record)
                 const uint4 v = vp_load16(s, nvalid, g);
                 uint32_t d[4] = {v.x, v.y, v.z, v.w};
                 adp_keep16(d, nvalid);
@@ -227,7 +209,7 @@ __global__ __launch_bounds__(VP_THREADS) void adapter_cut_kernel(AdapterArgs K) 
                 vp_release_row();                                                   // (the next read overwrites the row)
             }
             if (have && g == 0) {
-                K.view[vi] = adp_view(vin, p);
+                K.view[vi] = view_end(vin, p != ADP_NONE, p);
                 if (too_long) vp_raise_too_long(K.status);
                 const int kept = p == ADP_NONE ? n : p;
                 vp_count(cnt, k, rec < K.accum_limit && r1_kept, n, kept);

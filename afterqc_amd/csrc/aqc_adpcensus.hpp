@@ -20,7 +20,7 @@
 //            stand in for letters (an N has G's bits).  A lane whose code compare hit walks its places again, from the row, and
 //            compares the three dwords themselves: that decides.
 //   count    the probes a lane holds are a bit mask, OR-reduced over the group; the group's first lane counts reads looked at and
-//            reads per probe in registers; cen_flush adds them through the workgroup's LDS words to the context's, one global
+//            reads per probe in registers; vp_flush adds them through the workgroup's LDS words to the context's, one global
 //            atomic per probe and workgroup.
 //
 // The per-read functions are __host__ __device__: tests/native/adpcensus_selftest.cpp includes this header without HIP, deals the
@@ -138,25 +138,6 @@ struct CensusArgs {
     CensusProbes probes;
 };
 
-// OR over the G lanes of a group (every lane of the wave runs it)
-template <int G>
-__device__ __forceinline__ uint32_t cen_group_or(uint32_t v) {
-#pragma unroll
-    for (int d = 1; d < G; d <<= 1) v |= (uint32_t)__shfl_xor((int)v, d, WAVE);
-    return v;
-}
-
-// the counts of the groups' first lanes -> the workgroup's (tot: zeroed by the kernel before its first barrier) -> acc: vp_flush's shape
-__device__ __forceinline__ void cen_flush(const uint32_t (&cnt)[CEN_COUNTS], unsigned long long (&tot)[CEN_COUNTS], unsigned long long* acc, int g) {
-    if (g == 0) {
-#pragma unroll
-        for (int j = 0; j < CEN_COUNTS; ++j)
-            if (cnt[j]) atomicAdd(&tot[j], (unsigned long long)cnt[j]);
-    }
-    __syncthreads();
-    if (threadIdx.x < CEN_COUNTS && tot[threadIdx.x]) atomicAdd(&acc[threadIdx.x], tot[threadIdx.x]);
-}
-
 template <int G>
 __global__ __launch_bounds__(VP_THREADS) void adapter_census_kernel(CensusArgs K) {
     static_assert(G == 8 || G == 16 || G == 32 || G == 64, "a group is a power-of-two part of a wave");
@@ -193,7 +174,7 @@ __global__ __launch_bounds__(VP_THREADS) void adapter_census_kernel(CensusArgs K
         vp_publish_row();
         // ---- the search
         uint32_t held = cen_lane_held(row, K.probes, g);
-        if (vp_wave_any(held != 0u)) held = cen_group_or<G>(held);
+        if (vp_wave_any(held != 0u)) held = vp_group_or<G>(held);
         vp_release_row();                                                         // (the next read overwrites the row)
         if (have && g == 0) {
             if (too_long) vp_raise_too_long(K.status);
@@ -202,7 +183,7 @@ __global__ __launch_bounds__(VP_THREADS) void adapter_census_kernel(CensusArgs K
             for (int i = 0; i < CEN_MAX_PROBES; ++i) cnt[1 + i] += (held >> i) & 1u;
         }
     }
-    cen_flush(cnt, tot, K.acc, g);
+    vp_flush(cnt, tot, K.acc, g);
 }
 
 }  // namespace aqc

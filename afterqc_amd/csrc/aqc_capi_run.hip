@@ -207,6 +207,64 @@ static int fill_slot(aqc_ctx* c, Slot& s, const aqc_batch* b, bool need_qual, bo
     return 0;
 }
 
+// ---- the view passes.  What a launch of any of them is given: the mates' fixed trims, one view per mate and record into `view`
+// (n_mates per record), the four counts into `stats` (may be NULL), and — the passes behind the quality cut — the views the mates
+// come with (view_in: may be `view`; NULL: everything)
+struct ViewPassJob {
+    int32_t trim_front[2], trim_tail[2];
+    int n_mates;
+    const uint32_t* view_in;
+    uint32_t* view;
+    unsigned long long* stats;
+    uint64_t accum_limit;
+};
+
+// the pass's kernel over the slot's records: kernel_of(G) names its instance for G lanes per read
+template <class Args, class KernelOf>
+static int launch_pass(aqc_ctx* c, Slot& s, const Args& A, KernelOf kernel_of) {
+    vp_dispatch(view_pass_lanes(s), s.n, c->n_cu, [&](auto G, dim3 grid, dim3 block) { hipLaunchKernelGGL(kernel_of(G), grid, block, 0, s.stream, A); });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the quality cut's pass (aqc_qcut.hpp): it reads the quality lines through the batch view, and no views come in
+static int launch_cut(aqc_ctx* c, Slot& s, const QcutOpts& o, const ViewPassJob& j) {
+    QcutArgs A{};
+    A.b = s.view; A.o = o; A.n_mates = j.n_mates; A.view = j.view; A.stats = j.stats; A.accum_limit = j.accum_limit; A.status = s.status;
+    for (int k = 0; k < 2; ++k) { A.trim_front[k] = j.trim_front[k]; A.trim_tail[k] = j.trim_tail[k]; }
+    return launch_pass(c, s, A, [](auto G) { return quality_cut_kernel<decltype(G)::value>; });
+}
+
+// the sequence-line passes (aqc_adapter.hpp, aqc_polytail.hpp): mate k's lines in the slot's batch view and its fixed trim ...
+static ViewMate view_mate(const Slot& s, const ViewPassJob& j, int k) {
+    return ViewMate{k ? s.view.seq2 : s.view.seq1, k ? s.view.off2 : s.view.off1, k ? s.view.len2 : s.view.len1, j.trim_front[k], j.trim_tail[k]};
+}
+// ... and the frame fields their *Args share
+template <class Args>
+static void fill_frame(Args& A, const Slot& s, const ViewPassJob& j) {
+    A.n = s.view.n; A.n_mates = j.n_mates; A.view_in = j.view_in; A.view = j.view; A.stats = j.stats; A.accum_limit = j.accum_limit; A.status = s.status;
+}
+
+static int launch_adapter(aqc_ctx* c, Slot& s, const AdapterOpts& a, const ViewPassJob& j) {
+    AdapterArgs A{};
+    fill_frame(A, s, j);
+    A.min_overlap = a.min_overlap;
+    for (int k = 0; k < j.n_mates; ++k) {
+        A.m[k].v = view_mate(s, j, k);
+        A.m[k].alen = a.len[k];
+        for (int i = 0; i < ADP_WORDS; ++i) A.m[k].w[i] = a.w[k][i];
+    }
+    return launch_pass(c, s, A, [](auto G) { return adapter_cut_kernel<decltype(G)::value>; });
+}
+
+static int launch_poly(aqc_ctx* c, Slot& s, const PolyOpts& o, const ViewPassJob& j) {
+    PolyArgs A{};
+    fill_frame(A, s, j);
+    for (int x = 0; x < POLY_LETTERS; ++x) A.min_len[x] = o.min_len[x];
+    for (int k = 0; k < j.n_mates; ++k) A.m[k] = view_mate(s, j, k);
+    return launch_pass(c, s, A, [](auto G) { return poly_tail_kernel<decltype(G)::value>; });
+}
+
 extern "C" {
 
 // ---- upload and run ----------------------------------------------------------------------------------------------
@@ -276,76 +334,20 @@ static int prepare_fuse(Slot& s, FuseArgs& fz) {
     return 0;
 }
 
-// ---- the quality cut's pass (aqc_qcut.hpp): one view per mate and record into `view` (n_mates per record), the four counts into `stats` (may be NULL)
-static int launch_cut(aqc_ctx* c, Slot& s, const QcutOpts& o, const int32_t trim_front[2], const int32_t trim_tail[2], int n_mates, uint32_t* view,
-                      unsigned long long* stats, uint64_t accum_limit) {
-    QcutArgs A{};
-    A.b = s.view; A.o = o; A.n_mates = n_mates; A.view = view; A.stats = stats; A.accum_limit = accum_limit; A.status = s.status;
-    for (int k = 0; k < 2; ++k) { A.trim_front[k] = trim_front[k]; A.trim_tail[k] = trim_tail[k]; }
-    vp_dispatch(view_pass_lanes(s), s.n, c->n_cu, [&](auto G, dim3 grid, dim3 block) {
-        hipLaunchKernelGGL(quality_cut_kernel<decltype(G)::value>, grid, block, 0, s.stream, A);
-    });
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ---- the adapter pass (aqc_adapter.hpp): the view each mate leaves it with into `view`; view_in: the views they come with (may be `view`; NULL: everything)
-static int launch_adapter(aqc_ctx* c, Slot& s, const AdapterOpts& a, const int32_t trim_front[2], const int32_t trim_tail[2], int n_mates,
-                          const uint32_t* view_in, uint32_t* view, unsigned long long* stats, uint64_t accum_limit) {
-    AdapterArgs A{};
-    A.n = s.view.n; A.min_overlap = a.min_overlap; A.n_mates = n_mates; A.view_in = view_in; A.view = view; A.stats = stats; A.accum_limit = accum_limit; A.status = s.status;
-    for (int k = 0; k < n_mates; ++k) {
-        AdapterMate& M = A.m[k];
-        M.seq = k ? s.view.seq2 : s.view.seq1; M.off = k ? s.view.off2 : s.view.off1; M.len = k ? s.view.len2 : s.view.len1;
-        M.trim_front = trim_front[k]; M.trim_tail = trim_tail[k]; M.alen = a.len[k];
-        for (int j = 0; j < ADP_WORDS; ++j) M.w[j] = a.w[k][j];
-    }
-    vp_dispatch(view_pass_lanes(s), s.n, c->n_cu, [&](auto G, dim3 grid, dim3 block) {
-        hipLaunchKernelGGL(adapter_cut_kernel<decltype(G)::value>, grid, block, 0, s.stream, A);
-    });
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ---- the poly-tail pass (aqc_polytail.hpp): the view each mate leaves it with into `view`; view_in: the views they come with (may be `view`; NULL: everything)
-static int launch_poly(aqc_ctx* c, Slot& s, const PolyOpts& o, const int32_t trim_front[2], const int32_t trim_tail[2], int n_mates,
-                       const uint32_t* view_in, uint32_t* view, unsigned long long* stats, uint64_t accum_limit) {
-    PolyArgs A{};
-    A.n = s.view.n; A.n_mates = n_mates; A.view_in = view_in; A.view = view; A.stats = stats; A.accum_limit = accum_limit; A.status = s.status;
-    for (int x = 0; x < POLY_LETTERS; ++x) A.min_len[x] = o.min_len[x];
-    for (int k = 0; k < n_mates; ++k) {
-        PolyMate& M = A.m[k];
-        M.seq = k ? s.view.seq2 : s.view.seq1; M.off = k ? s.view.off2 : s.view.off1; M.len = k ? s.view.len2 : s.view.len1;
-        M.trim_front = trim_front[k]; M.trim_tail = trim_tail[k];
-    }
-    vp_dispatch(view_pass_lanes(s), s.n, c->n_cu, [&](auto G, dim3 grid, dim3 block) {
-        hipLaunchKernelGGL(poly_tail_kernel<decltype(G)::value>, grid, block, 0, s.stream, A);
-    });
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 // A view pass of an aqc_run: both mates' views into the slot's array, timed by an event pair of its own.  The first pass that runs
-// fills the array; a pass behind it updates the views in place.
+// fills the array; a pass behind it — the views come in if any pass with a smaller ViewPassId ran — updates them in place.
 static int run_view_pass(aqc_ctx* c, Slot& s, ViewPassId which, const aqc_config& cfg, uint64_t accum_limit) {
     ViewPass& vp = s.pass[which];
     const int nm = cfg.paired ? 2 : 1;
     if (s.cut.reserve(sizeof(uint32_t) * s.n * nm)) return fail(AQC_ERR_HIP, "hipMalloc failed");
     for (hipEvent_t& e : vp.ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
-    const int32_t tf[2] = {cfg.trim_front, cfg.trim_front2}, tt[2] = {cfg.trim_tail, cfg.trim_tail2};
     uint32_t* const view = (uint32_t*)s.cut.p;
-    unsigned long long* const stats = c->pass_stats[which].p;
+    bool earlier = false;
+    for (int p = 0; p < which; ++p) earlier = earlier || s.pass[p].ran;
+    const ViewPassJob j{{cfg.trim_front, cfg.trim_front2}, {cfg.trim_tail, cfg.trim_tail2}, nm, earlier ? view : nullptr, view, c->pass_stats[which].p, accum_limit};
     HIP_TRY(hipEventRecord(vp.ev[0], s.stream));
-    int rc;
-    if (which == VP_CUT) rc = launch_cut(c, s, c->cut, tf, tt, nm, view, stats, accum_limit);
-    else if (which == VP_POLY)
-        rc = launch_poly(c, s, c->poly, tf, tt, nm, (s.pass[VP_CUT].ran || s.pass[VP_ADAPTER].ran) ? view : nullptr, view, stats, accum_limit);
-    else {
-        AdapterOpts a = c->adapter;
-        if (nm == 1) a.len[1] = 0;
-        rc = launch_adapter(c, s, a, tf, tt, nm, s.pass[VP_CUT].ran ? view : nullptr, view, stats, accum_limit);
-    }
+    const int rc = which == VP_CUT ? launch_cut(c, s, c->cut, j) : which == VP_ADAPTER ? launch_adapter(c, s, c->adapter, j) : launch_poly(c, s, c->poly, j);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(vp.ev[1], s.stream));
     vp.ran = true;
@@ -643,9 +645,10 @@ int aqc_edit_distance(aqc_ctx* c, const aqc_batch* b, int32_t* dist) {
 }
 
 // The function seam of a view pass: read 1 of the batch through the pass alone, one view per record out.  view_in (may be NULL): the
-// views the reads come with, uploaded into the array the pass then updates in place.  launch(slot, device views) starts the kernel.
-static int view_seam(aqc_ctx* c, const aqc_batch* b, bool need_qual, const uint32_t* view_in, uint32_t* view,
-                     const std::function<int(Slot&, uint32_t*)>& launch) {
+// views the reads come with, uploaded into the array the pass then updates in place.  launch(slot, job) starts the kernel.
+using SeamLaunch = std::function<int(Slot&, const ViewPassJob&)>;
+static int view_seam(aqc_ctx* c, const aqc_batch* b, bool need_qual, int32_t trim_front, int32_t trim_tail, const uint32_t* view_in, uint32_t* view,
+                     const SeamLaunch& launch) {
     Slot* s;
     int rc = seam_prepare(c, b, need_qual, false, &s);
     if (rc) return rc;
@@ -654,7 +657,8 @@ static int view_seam(aqc_ctx* c, const aqc_batch* b, bool need_qual, const uint3
     DevBuf out;
     if (out.reserve(4 * n)) return fail(AQC_ERR_HIP, "hipMalloc failed");
     if (view_in) HIP_TRY(hipMemcpyAsync(out.p, view_in, 4 * n, hipMemcpyHostToDevice, s->stream));
-    if ((rc = launch(*s, (uint32_t*)out.p))) return rc;
+    uint32_t* const v = (uint32_t*)out.p;
+    if ((rc = launch(*s, ViewPassJob{{trim_front, 0}, {trim_tail, 0}, 1, view_in ? v : nullptr, v, nullptr, UINT64_MAX}))) return rc;
     if ((rc = seam_out(s, out, view, n))) return rc;
     HIP_TRY(slot_sync(*s));
     return check_status(*s);
@@ -664,31 +668,32 @@ int aqc_quality_cut_views(aqc_ctx* c, const aqc_batch* b, const aqc_cut_config* 
     if (!cut || !view) return fail(AQC_ERR_ARG, "aqc_quality_cut_views: null argument");
     const QcutOpts o{cut->front ? 1 : 0, cut->tail ? 1 : 0, cut->right ? 1 : 0, cut->window, cut->mean_quality};
     if (!qcut_opts_ok(o) || trim_front < 0 || trim_tail < 0) return fail(AQC_ERR_ARG, "aqc_quality_cut_views: window / mean quality / trim out of range");
-    const int32_t tf[2] = {trim_front, 0}, tt[2] = {trim_tail, 0};
-    return view_seam(c, b, true, nullptr, view, [&](Slot& s, uint32_t* v) { return launch_cut(c, s, o, tf, tt, 1, v, nullptr, UINT64_MAX); });
+    return view_seam(c, b, true, trim_front, trim_tail, nullptr, view, [&](Slot& s, const ViewPassJob& j) { return launch_cut(c, s, o, j); });
+}
+
+// ... of a sequence-line pass: `cfg` its options as the caller gave them, opts_ok: they are in range (`what`: their names in the error
+// text).  The pass reads sequence lines only; a batch that brings quality lines is taken as aqc_run takes it, LEN_IRR marks included.
+static int line_pass_seam(aqc_ctx* c, const aqc_batch* b, const char* who, const void* cfg, bool opts_ok, const char* what, int32_t trim_front,
+                          int32_t trim_tail, const uint32_t* view_in, uint32_t* view, const SeamLaunch& launch) {
+    if (!cfg || !view) return fail(AQC_ERR_ARG, "%s: null argument", who);
+    if (!opts_ok || trim_front < 0 || trim_tail < 0) return fail(AQC_ERR_ARG, "%s: %s / trim out of range", who, what);
+    return view_seam(c, b, b && b->qual1 != nullptr, trim_front, trim_tail, view_in, view, launch);
 }
 
 int aqc_adapter_views(aqc_ctx* c, const aqc_batch* b, const aqc_adapter_config* adapter, int32_t trim_front, int32_t trim_tail, const uint32_t* view_in,
                       uint32_t* view) {
-    if (!adapter || !view) return fail(AQC_ERR_ARG, "aqc_adapter_views: null argument");
     AdapterOpts a{};
-    if (!adp_from_config(adapter, a) || trim_front < 0 || trim_tail < 0) return fail(AQC_ERR_ARG, "aqc_adapter_views: adapter / min overlap / trim out of range");
-    a.len[1] = 0;
-    const int32_t tf[2] = {trim_front, 0}, tt[2] = {trim_tail, 0};
-    // (the search reads sequence lines only; a batch that brings quality lines is taken as aqc_run takes it, LEN_IRR marks included)
-    return view_seam(c, b, b && b->qual1 != nullptr, view_in, view,
-                     [&](Slot& s, uint32_t* v) { return launch_adapter(c, s, a, tf, tt, 1, view_in ? v : nullptr, v, nullptr, UINT64_MAX); });
+    const bool ok = adp_from_config(adapter, a);
+    return line_pass_seam(c, b, "aqc_adapter_views", adapter, ok, "adapter / min overlap", trim_front, trim_tail, view_in, view,
+                          [&](Slot& s, const ViewPassJob& j) { return launch_adapter(c, s, a, j); });
 }
 
 int aqc_poly_views(aqc_ctx* c, const aqc_batch* b, const aqc_poly_config* poly, int32_t trim_front, int32_t trim_tail, const uint32_t* view_in,
                    uint32_t* view) {
-    if (!poly || !view) return fail(AQC_ERR_ARG, "aqc_poly_views: null argument");
     PolyOpts o{};
-    if (!poly_from_config(poly, o) || trim_front < 0 || trim_tail < 0) return fail(AQC_ERR_ARG, "aqc_poly_views: minimum length / trim out of range");
-    const int32_t tf[2] = {trim_front, 0}, tt[2] = {trim_tail, 0};
-    // (the pass reads sequence lines only; a batch that brings quality lines is taken as aqc_run takes it, LEN_IRR marks included)
-    return view_seam(c, b, b && b->qual1 != nullptr, view_in, view,
-                     [&](Slot& s, uint32_t* v) { return launch_poly(c, s, o, tf, tt, 1, view_in ? v : nullptr, v, nullptr, UINT64_MAX); });
+    const bool ok = poly_from_config(poly, o);
+    return line_pass_seam(c, b, "aqc_poly_views", poly, ok, "minimum length", trim_front, trim_tail, view_in, view,
+                          [&](Slot& s, const ViewPassJob& j) { return launch_poly(c, s, o, j); });
 }
 
 // ---- the reference's existing native seam: libed.so (editdistance/_editdistance.h:16,23, loaded by util.py:16-24) ----

@@ -9,8 +9,8 @@
 //
 // The frame — lanes per read, the 16-byte load, the view word, the counts — is that of every view pass: aqc_viewpass.hpp.  Here:
 //
-//   line     the sequence line as adapter_cut_kernel forms it: [t0 + s0, +n) of the arena from the length word (its LEN_IRR mark
-//            taken off) and the view that comes in — an earlier pass's, else VIEW_ALL.  No LDS row: a lane keeps its 16 bytes.
+//   line     the sequence line as vp_line forms it, behind trim() and the view that comes in — an earlier pass's, else VIEW_ALL.
+//            No LDS row: a lane keeps its 16 bytes.
 //   masks    per enabled letter 16 bits, one per byte of the lane that is not the letter; the bytes behind the line are no bytes.
 //   scan     the lanes' mismatch counts, two letters to a dword (a wave holds at most 1024 a letter), go through one wave-wide
 //            prefix sum; what a lane has BEHIND it in its group is the group's last sum minus its own.
@@ -134,13 +134,6 @@ VP_HD int poly_lane_last(uint32_t eq16, int n, int g, int scanned) {
 // where the letter ends the line: n - t, or n (nothing cut)
 VP_HD int poly_end(int n, int L, int scanned, int t) { return (scanned >= L && t > 0) ? n - t : n; }
 
-// the view a mate leaves the pass with: the one it came with, ended at `end` of its n bytes
-VP_HD uint32_t poly_view(uint32_t view_in, int n, int end) {
-    if (end >= n) return view_in;
-    const int c0 = view_c0(view_in);
-    return view_word(c0, c0 + end);
-}
-
 }  // namespace aqc
 
 #if defined(__HIPCC__)
@@ -148,15 +141,8 @@ VP_HD uint32_t poly_view(uint32_t view_in, int n, int end) {
 
 namespace aqc {
 
-// what the pass takes of one mate: its sequence lines and its fixed trim (aqc_config::trim_front / trim_front2, ...)
-struct PolyMate {
-    const uint8_t* seq;
-    const uint32_t *off, *len;
-    int32_t trim_front, trim_tail;
-};
-
 struct PolyArgs {
-    PolyMate m[2];
+    ViewMate m[2];
     uint64_t n;                                // records
     int32_t min_len[POLY_LETTERS];             // PolyOpts::min_len
     int32_t n_mates;                           // 1: read 1 only (single-end input, the function seam)
@@ -194,20 +180,13 @@ __global__ __launch_bounds__(VP_THREADS) void poly_tail_kernel(PolyArgs K) {
         bool r1_kept = true;                        // read 1 leaves the trim stage with 5 bases or more: read 2 is trimmed and cut too
         for (int k = 0; k < nm; ++k) {
             // ---- the read: where, how long behind trim() and the passes in front
-            const PolyMate& M = K.m[k];
-            int len = have ? (int)(M.len[rec] & LEN_MASK) : 0;
-            const bool too_long = vp_too_long<G>(len);
-            if (!have || too_long) len = 0;
-            uint32_t vin = VIEW_ALL;
+            const ViewMate& M = K.m[k];
             const uint32_t vi = (uint32_t)rec * (uint32_t)nm + (uint32_t)k;       // (a slot holds fewer than 2^31 records)
-            if (have && K.view_in) vin = K.view_in[vi];
-            int t0, tl, s0, n;
-            vp_trim(len, M.trim_front, M.trim_tail, t0, tl);
-            view_slice(tl, vin, s0, n);
+            const auto [too_long, vin, start, n] = vp_line<G>(M, rec, have, K.view_in, vi);
             // ---- 16 bytes per lane
             const int nvalid = vp_nvalid(n, g);
             const uint8_t* s = nullptr;
-            if (nvalid > 0) s = M.seq + M.off[rec] + (t0 + s0);            // (no off[rec] behind the batch's last record)
+            if (nvalid > 0) s = M.seq + M.off[rec] + start;            // (no off[rec] behind the batch's last record)
             const uint4 v = vp_load16(s, nvalid, g);
             const uint32_t d[4] = {v.x, v.y, v.z, v.w};
             // ---- per letter: the mismatch mask, the mismatches behind the lane, scanned
@@ -252,7 +231,7 @@ __global__ __launch_bounds__(VP_THREADS) void poly_tail_kernel(PolyArgs K) {
                 }
             }
             if (have && g == 0) {
-                K.view[vi] = poly_view(vin, n, end);
+                K.view[vi] = view_end(vin, end < n, end);
                 if (too_long) vp_raise_too_long(K.status);
                 vp_count(cnt, k, rec < K.accum_limit && r1_kept, n, end);
                 if (k == 0) r1_kept = vp_read1_kept(end);

@@ -65,7 +65,7 @@ int main(int argc, char** argv) {
         } else if (buf[0] == 'V') {
             int c0, c1, p, o0, o1;
             if (sscanf(buf, "V %d %d %d %d %d", &c0, &c1, &p, &o0, &o1) != 5) { fprintf(stderr, "bad line: %s", buf); return 2; }
-            const uint32_t v = adp_view(view_word(c0, c1), p < 0 ? ADP_NONE : p);
+            const uint32_t v = view_end(view_word(c0, c1), p >= 0, p);
             ++views;
             if (view_c0(v) != o0 || view_c1(v) != o1) {
                 if (++failed <= 20) printf("FAIL view: %s got %d %d\n", buf, view_c0(v), view_c1(v));

@@ -77,7 +77,7 @@ int main(int argc, char** argv) {
         } else if (buf[0] == 'V') {
             int c0, c1, n, end, o0, o1;
             if (sscanf(buf, "V %d %d %d %d %d %d", &c0, &c1, &n, &end, &o0, &o1) != 6) { fprintf(stderr, "bad line: %s", buf); return 2; }
-            const uint32_t v = poly_view(view_word(c0, c1), n, end);
+            const uint32_t v = view_end(view_word(c0, c1), end < n, end);
             ++views;
             if (view_c0(v) != o0 || view_c1(v) != o1) {
                 if (++failed <= 20) printf("FAIL view: %s got %d %d\n", buf, view_c0(v), view_c1(v));

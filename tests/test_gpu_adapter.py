@@ -16,7 +16,6 @@ tests/adapter_rule.py.
 import json
 import os
 import random
-import subprocess
 import sys
 
 import numpy as np
@@ -45,8 +44,7 @@ def adcfg(a1=b"", a2=b"", K=4):
     return capi.AdapterConfig(a1, a2, K)
 
 
-def views(c0, c1):
-    return list(zip(c0.tolist(), c1.tolist()))
+views, se, run_pairs = vc.views, vc.se, vc.run_pairs
 
 
 # ---- the seam against the model ---------------------------------------------------------------------------------------------
@@ -121,40 +119,33 @@ def adapter_pairs(n, L, seed, a1, a2, short=()):
     return adapter_rule.with_adapters(random.Random(seed), vc.tailed_pairs(n, L, seed, short), a1, a2)
 
 
-run_pairs = vc.run_pairs
-
-
 def model_of(a1, a2, K, modes=None, trim=(0, 0)):
-    cut = cut_rule.CutConfig(*(modes or (0, 0, 0)), window=4, mean_quality=20, trim_front=trim[0], trim_tail=trim[1])
-    return adapter_rule.AdapterConfig(a1, a2, K, cut)
-
-
-def se(pairs, paired):
-    return [p if paired else (p[0], p[1], None, None) for p in pairs]
+    return vc.model_of(modes, trim, a1, a2, K)
 
 
 def check_against_precut(eng, pairs, paired, trim, a1, a2, K, words):
     """the adapter on, without and with a quality cut, each against the same build on the model's pre-cut records, options off"""
     plain = None
-    for modes in (None, (0, 1, 0)):
-        model = model_of(a1, a2, K, modes, trim)
-        pre = adapter_rule.precut_pairs(pairs, model, paired)
-        assert min(len(p[0]) for p in pre) >= 5 and (not paired or min(len(p[2]) for p in pre) >= 5)
-        A = run_pairs(eng, pairs, paired, vc.base_config(paired, trim), vc.cutcfg(modes) if modes else None, adcfg(a1, a2 if paired else b"", K))
-        B = run_pairs(eng, pre, paired, vc.base_config(paired), None, None)
-        assert A["words"] == words
-        assert A["adapter_ms"] > 0 and B["adapter_ms"] == 0 and (A["cut_ms"] > 0) == bool(modes)
-        vc.compare_runs(pairs, pre, A, B, paired)
-        want = adapter_rule.adapter_counts(se(pairs, paired), model)
-        assert A["adapter_stats"].tolist() == want and want[0] > len(pairs) // 8
-        # the quality cut's own counts are what they are without the adapter
-        assert A["cut_stats"].tolist() == (cut_rule.cut_counts(se(pairs, paired), model.cut) if modes else [0, 0, 0, 0])
-        if modes is None:
-            plain = pre
-        else:
-            assert pre != plain                                 # (the cut does take part)
-    eng.set_quality_cut(None)
-    eng.set_adapter_trim(None)
+    try:
+        for modes in (None, (0, 1, 0)):
+            model = model_of(a1, a2, K, modes, trim)
+            pre = adapter_rule.precut_pairs(pairs, model, paired)
+            assert min(len(p[0]) for p in pre) >= 5 and (not paired or min(len(p[2]) for p in pre) >= 5)
+            A = run_pairs(eng, pairs, paired, vc.base_config(paired, trim), vc.cutcfg(modes) if modes else None, adcfg(a1, a2 if paired else b"", K))
+            B = run_pairs(eng, pre, paired, vc.base_config(paired), None, None)
+            assert A["words"] == words
+            assert A["adapter_ms"] > 0 and B["adapter_ms"] == 0 and (A["cut_ms"] > 0) == bool(modes)
+            vc.compare_runs(pairs, pre, A, B, paired)
+            want = adapter_rule.adapter_counts(se(pairs, paired), model)
+            assert A["adapter_stats"].tolist() == want and want[0] > len(pairs) // 8
+            # the quality cut's own counts are what they are without the adapter
+            assert A["cut_stats"].tolist() == (cut_rule.cut_counts(se(pairs, paired), model.cut) if modes else [0, 0, 0, 0])
+            if modes is None:
+                plain = pre
+            else:
+                assert pre != plain                                 # (the cut does take part)
+    finally:
+        vc.set_passes(eng)
 
 
 VERDICT_CASES = [(150, 10, True, (2, 3)), (150, 10, False, (0, 0)), (250, 16, True, (0, 0)), (250, 16, False, (2, 3)),
@@ -199,21 +190,7 @@ def test_reads_trimmed_below_five_bases(gpu_engine):
     model = model_of(A1, A2, 4)
     A = run_pairs(gpu_engine, pairs, True, vc.base_config(True), None, adcfg(A1, A2, 4), accum_limit=300)
     gpu_engine.set_adapter_trim(None)
-    n1 = n2 = 0
-    for p, r in zip(pairs, A["res"]):
-        k1, k2 = adapter_rule.cut_lines(p[0], p[1], model, 0), adapter_rule.cut_lines(p[2], p[3], model, 1)
-        assert len(k1[0]) < 5 or len(k2[0]) < 5
-        a1, l1, a2, l2 = int(r["start1"]), int(r["len1"]), int(r["start2"]), int(r["len2"])
-        assert p[0][a1:a1 + l1] == k1[0]
-        if len(k1[0]) < 5:
-            assert int(r["flag"]) == capi.BADTRIM1
-            assert (a2, l2) == (0, len(p[2]))                   # read 2 is written as it came
-            n1 += 1
-        else:
-            assert int(r["flag"]) == capi.BADTRIM2
-            assert p[2][a2:a2 + l2] == k2[0]
-            n2 += 1
-    assert n1 >= 200 and n2 >= 100
+    vc.check_below_five(pairs, A["res"], adapter_rule, model)
     # records below accum_limit only, and read 2 is not counted where read 1 ended the record
     assert A["adapter_stats"].tolist() == adapter_rule.adapter_counts(pairs, model, accum_limit=300)
     assert int(A["counters"][capi.C_FLAG0 + capi.BADTRIM1]) + int(A["counters"][capi.C_FLAG0 + capi.BADTRIM2]) == 300
@@ -224,30 +201,12 @@ def test_bad_file_text_of_reads_trimmed_below_five_bases(gpu_engine):
     pairs = sub5_pairs(300, 150, 6)
     model = model_of(A1, A2, 4)
     gpu_engine.set_config(vc.base_config(True))
-    gpu_engine.set_quality_cut(None)
-    gpu_engine.set_adapter_trim(adcfg(A1, A2, 4))
-    gpu_engine.reset_stats()
-    t = [vc.fastq_text(pairs, 0), vc.fastq_text(pairs, 1)]
-    pad = lambda b: np.frombuffer(b + b"\0" * 4096, dtype=np.uint8).copy()
-    info = gpu_engine.frame(1, pad(t[0]), len(t[0]), True, pad(t[1]), len(t[1]), True)
-    assert int(info.n) == len(pairs)
-    gpu_engine.run(1)
-    sizes = gpu_engine.format(1, len(pairs), False)
-    gpu_engine.set_adapter_trim(None)
-    want = [[], []]
-    for i, p in enumerate(pairs):
-        k1, k2 = adapter_rule.cut_lines(p[0], p[1], model, 0), adapter_rule.cut_lines(p[2], p[3], model, 1)
-        flag = b"BADTRIM1" if len(k1[0]) < 5 else b"BADTRIM2"
-        if flag == b"BADTRIM1":
-            k2 = (p[2], p[3])
-        want[0].append(b"@%sr%d/1\n%s\n+\n%s\n" % (flag, i, k1[0], k1[1]))
-        want[1].append(b"@%sr%d/2\n%s\n+\n%s\n" % (flag, i, k2[0], k2[1]))
-    for file in (0, 1):
-        assert sizes[file * 3] == 0
-        nb = sizes[file * 3 + 1]
-        buf = np.zeros(nb + 64, dtype=np.uint8)
-        gpu_engine.fetch_text(1, file, 1, buf, buf.size)
-        assert buf[:nb].tobytes() == b"".join(want[file])
+    vc.set_passes(gpu_engine, adapter=adcfg(A1, A2, 4))
+    try:
+        got = vc.bad_streams(gpu_engine, pairs)
+    finally:
+        vc.set_passes(gpu_engine)
+    assert got == vc.badtrim_text(pairs, adapter_rule, model)
 
 
 # ---- the counts ---------------------------------------------------------------------------------------------------------------
@@ -275,8 +234,7 @@ def test_adapter_stats_over_two_contexts_with_a_cut_on(gpu_engine):
         assert gpu_engine.adapter_stats().tolist() == [0, 0, 0, 0]
     finally:
         other.close()
-        gpu_engine.set_quality_cut(None)
-        gpu_engine.set_adapter_trim(None)
+        vc.set_passes(gpu_engine)
 
 
 # ---- off is off -------------------------------------------------------------------------------------------------------------
@@ -317,11 +275,7 @@ def child_generic():
 
 
 def test_general_kernel_alone_in_a_child_process():
-    e = dict(os.environ)
-    e["AQC_FORCE_GENERIC"] = "1"
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), "generic"], capture_output=True, text=True, timeout=300, env=e, cwd=os.path.join(ROOT, "tests"))
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    assert json.loads(p.stdout.strip().splitlines()[-1]) == {"ok": True}
+    assert vc.run_child(__file__, "generic", {"AQC_FORCE_GENERIC": "1"}) == {"ok": True}
 
 
 # ---- end to end -------------------------------------------------------------------------------------------------------------
@@ -407,16 +361,7 @@ def test_cli_equals_a_run_on_precut_files(name, tmp_path, gpu_engine):
         assert json.dumps(sa["quality_cut"], sort_keys=True) == json.dumps(sc["quality_cut"], sort_keys=True)
         assert sa["quality_cut"]["read1_cut_reads"] > 100
     assert sorted(k for k in sa if k not in ("adapter_trim", "quality_cut")) == sorted(sb)
-    for k in sb:
-        if k == "command":
-            continue
-        if k == "afterqc_main_summary":
-            skip = ("total_bases", "readlen")
-            assert {x: v for x, v in sa[k].items() if x not in skip} == {x: v for x, v in sb[k].items() if x not in skip}
-        elif isinstance(sb[k], dict) and any("prefilter" in x for x in sb[k]):
-            assert {x: v for x, v in sa[k].items() if "prefilter" not in x} == {x: v for x, v in sb[k].items() if "prefilter" not in x}, k
-        else:
-            assert sa[k] == sb[k], k
+    vc.compare_cli_stats(sa, sb)
 
 
 def test_folder_mode_with_debubble(tmp_path):

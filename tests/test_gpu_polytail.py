@@ -14,7 +14,6 @@
 import json
 import os
 import random
-import subprocess
 import sys
 
 import numpy as np
@@ -45,8 +44,7 @@ def pcfg(lens):
     return capi.PolyConfig(*lens)
 
 
-def views(c0, c1):
-    return list(zip(c0.tolist(), c1.tolist()))
+views, se, run_pairs = vc.views, vc.se, vc.run_pairs
 
 
 # ---- the seam against the model ---------------------------------------------------------------------------------------------
@@ -137,24 +135,8 @@ def poly_pairs(n, L, seed, short=()):
     return poly_rule.with_tails(random.Random(seed), vc.tailed_pairs(n, L, seed, short))
 
 
-def run_pairs(eng, pairs, paired, cfg, cut, adapter, poly, slot=0, accum_limit=capi.UINT64_MAX):
-    """vc.run_pairs with the poly-tail pass as given (None: off); the pass is off again when this returns"""
-    eng.set_poly_trim(poly)
-    try:
-        out = vc.run_pairs(eng, pairs, paired, cfg, cut, adapter, slot, accum_limit)
-        out["poly_ms"], out["poly_stats"] = eng.poly_ms(slot), eng.poly_stats()
-    finally:
-        eng.set_poly_trim(None)
-    return out
-
-
 def model_of(lens, modes=None, trim=(0, 0), a1=b"", a2=b"", K=4):
-    cut = cut_rule.CutConfig(*(modes or (0, 0, 0)), window=4, mean_quality=20, trim_front=trim[0], trim_tail=trim[1])
-    return poly_rule.PolyConfig(lens, adapter_rule.AdapterConfig(a1, a2, K, cut))
-
-
-def se(pairs, paired):
-    return [p if paired else (p[0], p[1], None, None) for p in pairs]
+    return vc.model_of(modes, trim, a1, a2, K, lens)
 
 
 def check_against_precut(eng, pairs, paired, trim, words):
@@ -180,9 +162,7 @@ def check_against_precut(eng, pairs, paired, trim, words):
             assert pre not in seen                                  # (each set of options does take part)
             seen.append(pre)
     finally:
-        eng.set_quality_cut(None)
-        eng.set_adapter_trim(None)
-        eng.set_poly_trim(None)
+        vc.set_passes(eng)
 
 
 VERDICT_CASES = [(150, 10, True, (2, 3)), (150, 10, False, (0, 0)), (250, 16, True, (0, 0)), (250, 16, False, (2, 3)),
@@ -213,21 +193,7 @@ def test_reads_trimmed_below_five_bases(gpu_engine):
     pairs = sub5_pairs()
     model = model_of((0, 0, 10, 0))
     A = run_pairs(gpu_engine, pairs, True, vc.base_config(True), None, None, pcfg((0, 0, 10, 0)), accum_limit=300)
-    n1 = n2 = 0
-    for p, r in zip(pairs, A["res"]):
-        k1, k2 = poly_rule.cut_lines(p[0], p[1], model, 0), poly_rule.cut_lines(p[2], p[3], model, 1)
-        assert len(k1[0]) < 5 or len(k2[0]) < 5
-        a1, l1, a2, l2 = int(r["start1"]), int(r["len1"]), int(r["start2"]), int(r["len2"])
-        assert p[0][a1:a1 + l1] == k1[0]
-        if len(k1[0]) < 5:
-            assert int(r["flag"]) == capi.BADTRIM1
-            assert (a2, l2) == (0, len(p[2]))                   # read 2 is written as it came
-            n1 += 1
-        else:
-            assert int(r["flag"]) == capi.BADTRIM2
-            assert p[2][a2:a2 + l2] == k2[0]
-            n2 += 1
-    assert n1 >= 200 and n2 >= 100
+    vc.check_below_five(pairs, A["res"], poly_rule, model)
     # records below accum_limit only, and read 2 is not counted where read 1 ended the record
     assert A["poly_stats"].tolist() == poly_rule.poly_counts(pairs, model, accum_limit=300)
     assert int(A["counters"][capi.C_FLAG0 + capi.BADTRIM1]) + int(A["counters"][capi.C_FLAG0 + capi.BADTRIM2]) == 300
@@ -238,33 +204,12 @@ def test_bad_file_text_of_reads_trimmed_below_five_bases(gpu_engine):
     pairs = sub5_pairs(300, 150, 6)
     model = model_of((0, 0, 10, 0))
     gpu_engine.set_config(vc.base_config(True))
-    gpu_engine.set_quality_cut(None)
-    gpu_engine.set_adapter_trim(None)
-    gpu_engine.set_poly_trim(pcfg((0, 0, 10, 0)))
+    vc.set_passes(gpu_engine, poly=pcfg((0, 0, 10, 0)))
     try:
-        gpu_engine.reset_stats()
-        t = [vc.fastq_text(pairs, 0), vc.fastq_text(pairs, 1)]
-        pad = lambda b: np.frombuffer(b + b"\0" * 4096, dtype=np.uint8).copy()
-        info = gpu_engine.frame(1, pad(t[0]), len(t[0]), True, pad(t[1]), len(t[1]), True)
-        assert int(info.n) == len(pairs)
-        gpu_engine.run(1)
-        sizes = gpu_engine.format(1, len(pairs), False)
+        got = vc.bad_streams(gpu_engine, pairs)
     finally:
-        gpu_engine.set_poly_trim(None)
-    want = [[], []]
-    for i, p in enumerate(pairs):
-        k1, k2 = poly_rule.cut_lines(p[0], p[1], model, 0), poly_rule.cut_lines(p[2], p[3], model, 1)
-        flag = b"BADTRIM1" if len(k1[0]) < 5 else b"BADTRIM2"
-        if flag == b"BADTRIM1":
-            k2 = (p[2], p[3])
-        want[0].append(b"@%sr%d/1\n%s\n+\n%s\n" % (flag, i, k1[0], k1[1]))
-        want[1].append(b"@%sr%d/2\n%s\n+\n%s\n" % (flag, i, k2[0], k2[1]))
-    for file in (0, 1):
-        assert sizes[file * 3] == 0
-        nb = sizes[file * 3 + 1]
-        buf = np.zeros(nb + 64, dtype=np.uint8)
-        gpu_engine.fetch_text(1, file, 1, buf, buf.size)
-        assert buf[:nb].tobytes() == b"".join(want[file])
+        vc.set_passes(gpu_engine)
+    assert got == vc.badtrim_text(pairs, poly_rule, model)
 
 
 # ---- the counts ---------------------------------------------------------------------------------------------------------------
@@ -295,9 +240,7 @@ def test_poly_stats_over_two_contexts_with_a_cut_and_an_adapter_on(gpu_engine):
         assert gpu_engine.poly_stats().tolist() == [0, 0, 0, 0]
     finally:
         other.close()
-        gpu_engine.set_quality_cut(None)
-        gpu_engine.set_adapter_trim(None)
-        gpu_engine.set_poly_trim(None)
+        vc.set_passes(gpu_engine)
 
 
 # ---- off is off -------------------------------------------------------------------------------------------------------------
@@ -339,11 +282,7 @@ def child_generic():
 
 
 def test_general_kernel_alone_in_a_child_process():
-    e = dict(os.environ)
-    e["AQC_FORCE_GENERIC"] = "1"
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), "generic"], capture_output=True, text=True, timeout=300, env=e, cwd=os.path.join(ROOT, "tests"))
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    assert json.loads(p.stdout.strip().splitlines()[-1]) == {"ok": True}
+    assert vc.run_child(__file__, "generic", {"AQC_FORCE_GENERIC": "1"}) == {"ok": True}
 
 
 # ---- end to end -------------------------------------------------------------------------------------------------------------
@@ -436,19 +375,9 @@ def test_cli_equals_a_run_on_precut_files(name, tmp_path, gpu_engine):
             assert sa["quality_cut"]["read1_cut_reads"] > 100 and sa["adapter_trim"]["read1_trimmed_reads"] > 20
             assert "poly_trim" not in sc
         assert sorted(k for k in sa if k not in ("poly_trim", "adapter_trim", "quality_cut")) == sorted(sb)
-        for k in sb:
-            if k == "command":
-                continue
-            if k == "afterqc_main_summary":
-                skip = ("total_bases", "readlen")
-                assert {x: v for x, v in sa[k].items() if x not in skip} == {x: v for x, v in sb[k].items() if x not in skip}
-            elif isinstance(sb[k], dict) and any("prefilter" in x for x in sb[k]):
-                assert {x: v for x, v in sa[k].items() if "prefilter" not in x} == {x: v for x, v in sb[k].items() if "prefilter" not in x}, k
-            else:
-                assert sa[k] == sb[k], k
+        vc.compare_cli_stats(sa, sb)
     finally:
-        for setter in ("set_quality_cut", "set_adapter_trim", "set_poly_trim"):
-            getattr(gpu_engine, setter)(None)
+        vc.set_passes(gpu_engine)
 
 
 def test_cli_refuses_barcoded_input(tmp_path, gpu_engine):

@@ -13,7 +13,6 @@
 import json
 import os
 import random
-import subprocess
 import sys
 
 import numpy as np
@@ -25,9 +24,10 @@ for _p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golde
         sys.path.insert(0, _p)
 
 import cut_rule
+import viewpass_cases as vc
 from afterqc_amd import capi
-from viewpass_cases import (ERR_UNSUPPORTED, GROUP_LENGTHS, GROUP_RANGE, base_config, bases, compare_runs, cutcfg, driver_kw, fastq_text, pack,
-                            read_outputs, run_cli, run_pairs, tailed_pairs, write_inputs)
+from viewpass_cases import (ERR_UNSUPPORTED, GROUP_LENGTHS, GROUP_RANGE, base_config, bases, compare_runs, cutcfg, driver_kw, pack, read_outputs,
+                            run_cli, run_pairs, se, tailed_pairs, views, write_inputs)
 
 pytestmark = pytest.mark.gpu
 
@@ -58,9 +58,8 @@ def test_seam_against_the_model(W, G, gpu_engine, seam_lines):
     assert batch.qlen1 is None and GROUP_RANGE[G][0] <= batch.max_len() <= GROUP_RANGE[G][1]
     for Q in QUALITIES:
         for modes in cut_rule.MODES:
-            c0, c1 = gpu_engine.quality_cut_views(batch, cutcfg(modes, W, Q))
+            got = views(*gpu_engine.quality_cut_views(batch, cutcfg(modes, W, Q)))
             want = [cut_rule.cut_window(x, W, Q, *modes) for x in lines]
-            got = list(zip(c0.tolist(), c1.tolist()))
             bad = [i for i in range(len(lines)) if got[i] != want[i]]
             assert not bad, (W, G, Q, modes, len(bad), [(len(lines[i]), got[i], want[i]) for i in bad[:5]])
 
@@ -81,15 +80,14 @@ def test_seam_fixed_trim_and_irregular_lines(trim, gpu_engine):
     assert batch.qlen1 is not None
     for modes in cut_rule.MODES:
         for W, Q in ((4, 20), (17, 25)):
-            c0, c1 = gpu_engine.quality_cut_views(batch, cutcfg(modes, W, Q), trim[0], trim[1])
             want = [cut_rule.cut_window(cut_rule.trim(x, *trim), W, Q, *modes) for x in quals]
-            assert list(zip(c0.tolist(), c1.tolist())) == want, (modes, W, Q)
+            assert views(*gpu_engine.quality_cut_views(batch, cutcfg(modes, W, Q), trim[0], trim[1])) == want, (modes, W, Q)
     regular = [x[:150] + bytes([33 + 30]) * (150 - len(x)) for x in quals]
     batch = pack(seqs, regular)
     assert batch.qlen1 is None
     for modes in cut_rule.MODES:
-        c0, c1 = gpu_engine.quality_cut_views(batch, cutcfg(modes, 4, 20), trim[0], trim[1])
-        assert list(zip(c0.tolist(), c1.tolist())) == [cut_rule.cut_window(cut_rule.trim(x, *trim), 4, 20, *modes) for x in regular], modes
+        got = views(*gpu_engine.quality_cut_views(batch, cutcfg(modes, 4, 20), trim[0], trim[1]))
+        assert got == [cut_rule.cut_window(cut_rule.trim(x, *trim), 4, 20, *modes) for x in regular], modes
 
 
 def test_seam_refuses_bad_options(gpu_engine):
@@ -133,7 +131,7 @@ def test_verdicts_equal_a_run_on_precut_records(L, words, paired, modes, trim, g
     assert A["words"] == words
     assert A["cut_ms"] > 0 and B["cut_ms"] == 0
     compare_runs(pairs, pre, A, B, paired)
-    assert A["cut_stats"].tolist() == cut_rule.cut_counts([p if paired else (p[0], p[1], None, None) for p in pairs], model)
+    assert A["cut_stats"].tolist() == cut_rule.cut_counts(se(pairs, paired), model)
     if words:
         # the fast path is kept: only a mate the cut leaves under 16 bases sends its record to the general kernel
         under16 = sum(1 for p in pre if len(p[0]) < 16 or (paired and len(p[2]) < 16))
@@ -187,21 +185,7 @@ def test_reads_cut_below_five_bases(gpu_engine):
     model = cut_rule.CutConfig(0, 1, 0, window=4, mean_quality=20, trim_front=trim[0], trim_tail=trim[1])
     A = run_pairs(gpu_engine, pairs, True, base_config(True, trim), cutcfg((0, 1, 0)), accum_limit=300)
     gpu_engine.set_quality_cut(None)
-    n1 = n2 = 0
-    for i, (p, r) in enumerate(zip(pairs, A["res"])):
-        k1, k2 = cut_rule.cut_lines(p[0], p[1], model, 0), cut_rule.cut_lines(p[2], p[3], model, 1)
-        assert len(k1[0]) < 5 or len(k2[0]) < 5
-        a1, l1, a2, l2 = int(r["start1"]), int(r["len1"]), int(r["start2"]), int(r["len2"])
-        assert p[0][a1:a1 + l1] == k1[0]
-        if len(k1[0]) < 5:
-            assert int(r["flag"]) == capi.BADTRIM1
-            assert (a2, l2) == (0, len(p[2]))                   # read 2 is neither trimmed nor cut
-            n1 += 1
-        else:
-            assert int(r["flag"]) == capi.BADTRIM2
-            assert p[2][a2:a2 + l2] == k2[0]
-            n2 += 1
-    assert n1 >= 200 and n2 >= 100
+    vc.check_below_five(pairs, A["res"], cut_rule, model)
     # records below accum_limit only, and read 2 is not counted where it was left as it is
     assert A["cut_stats"].tolist() == cut_rule.cut_counts(pairs, model, accum_limit=300)
     assert int(A["counters"][capi.C_FLAG0 + capi.BADTRIM1]) + int(A["counters"][capi.C_FLAG0 + capi.BADTRIM2]) == 300
@@ -212,29 +196,12 @@ def test_bad_file_text_of_reads_cut_below_five_bases(gpu_engine):
     pairs = sub5_pairs(300, 150, 6)
     model = cut_rule.CutConfig(0, 1, 0, window=4, mean_quality=20)
     gpu_engine.set_config(base_config(True))
-    gpu_engine.set_quality_cut(cutcfg((0, 1, 0)))
-    gpu_engine.reset_stats()
-    t = [fastq_text(pairs, 0), fastq_text(pairs, 1)]
-    pad = lambda b: np.frombuffer(b + b"\0" * 4096, dtype=np.uint8).copy()
-    info = gpu_engine.frame(1, pad(t[0]), len(t[0]), True, pad(t[1]), len(t[1]), True)
-    assert int(info.n) == len(pairs)
-    gpu_engine.run(1)
-    sizes = gpu_engine.format(1, len(pairs), False)
-    gpu_engine.set_quality_cut(None)
-    want = [[], []]
-    for i, p in enumerate(pairs):
-        k1, k2 = cut_rule.cut_lines(p[0], p[1], model, 0), cut_rule.cut_lines(p[2], p[3], model, 1)
-        flag = b"BADTRIM1" if len(k1[0]) < 5 else b"BADTRIM2"
-        if flag == b"BADTRIM1":
-            k2 = (p[2], p[3])
-        want[0].append(b"@%sr%d/1\n%s\n+\n%s\n" % (flag, i, k1[0], k1[1]))
-        want[1].append(b"@%sr%d/2\n%s\n+\n%s\n" % (flag, i, k2[0], k2[1]))
-    for file in (0, 1):
-        assert sizes[file * 3] == 0
-        nb = sizes[file * 3 + 1]
-        buf = np.zeros(nb + 64, dtype=np.uint8)
-        gpu_engine.fetch_text(1, file, 1, buf, buf.size)
-        assert buf[:nb].tobytes() == b"".join(want[file])
+    vc.set_passes(gpu_engine, cut=cutcfg((0, 1, 0)))
+    try:
+        got = vc.bad_streams(gpu_engine, pairs)
+    finally:
+        vc.set_passes(gpu_engine)
+    assert got == vc.badtrim_text(pairs, cut_rule, model)
 
 
 # ---- the counts over two contexts ---------------------------------------------------------------------------------------------
@@ -300,34 +267,24 @@ def child_fused():
     """AQC_FUSED=1: with the cut on the verdict kernel never places the records itself; with the cut off again it does"""
     eng = capi.Engine(0, 2)
     pairs = tailed_pairs(512, 150, 72)
-    t = [fastq_text(pairs, 0), fastq_text(pairs, 1)]
-    pad = lambda b: np.frombuffer(b + b"\0" * 4096, dtype=np.uint8).copy()
     out = []
     for cut in (cutcfg((0, 1, 0)), None):
         eng.set_config(base_config(True))
         eng.set_quality_cut(cut)
         eng.reset_stats()
-        info = eng.frame(0, pad(t[0]), len(t[0]), True, pad(t[1]), len(t[1]), True)
+        n = vc.frame_text(eng, 0, pairs)
         eng.run(0)
-        eng.format(0, int(info.n), False)
+        eng.format(0, n, False)
         out.append((eng.format_fused(0), eng.cut_ms(0) > 0))
     print(json.dumps({"fused": out}))
 
 
-def run_child(role, env):
-    e = dict(os.environ)
-    e.update(env)
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), role], capture_output=True, text=True, timeout=300, env=e, cwd=os.path.join(ROOT, "tests"))
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    return json.loads(p.stdout.strip().splitlines()[-1])
-
-
 def test_general_kernel_alone_in_a_child_process():
-    assert run_child("generic", {"AQC_FORCE_GENERIC": "1"}) == {"words": 0, "cut_ms_on": True}
+    assert vc.run_child(__file__, "generic", {"AQC_FORCE_GENERIC": "1"}) == {"words": 0, "cut_ms_on": True}
 
 
 def test_fused_placement_is_back_with_the_cut_off_in_a_child_process():
-    assert run_child("fused", {"AQC_FUSED": "1"}) == {"fused": [[0, True], [1, False]]}
+    assert vc.run_child(__file__, "fused", {"AQC_FUSED": "1"}) == {"fused": [[0, True], [1, False]]}
 
 
 # ---- end to end -------------------------------------------------------------------------------------------------------------
@@ -398,22 +355,13 @@ def test_cli_equals_a_run_on_precut_files(name, tmp_path, gpu_engine):
     #  counted are the records the cut's counts cover)
     counted = sb["afterqc_main_summary"]["total_reads"] if "--qc_only" in argv_cut else None
     assert counted is None or 300 <= counted < len(pairs)
-    want = cut_rule.cut_counts([p if paired else (p[0], p[1], None, None) for p in pairs], model, accum_limit=counted)
+    want = cut_rule.cut_counts(se(pairs, paired), model, accum_limit=counted)
     qc = sa["quality_cut"]
     assert [qc["read1_cut_reads"], qc["read1_cut_bases"], qc["read2_cut_reads"], qc["read2_cut_bases"]] == want
     assert (qc["cut_front"], qc["cut_tail"], qc["cut_right"]) == (model.front, model.tail, model.right)
     assert (qc["cut_window_size"], qc["cut_mean_quality"]) == (model.window, model.mean_quality)
     assert sorted(k for k in sa if k != "quality_cut") == sorted(sb)
-    for k in sb:
-        if k == "command":
-            continue
-        if k == "afterqc_main_summary":
-            skip = ("total_bases", "readlen")
-            assert {x: v for x, v in sa[k].items() if x not in skip} == {x: v for x, v in sb[k].items() if x not in skip}
-        elif isinstance(sb[k], dict) and any("prefilter" in x for x in sb[k]):
-            assert {x: v for x, v in sa[k].items() if "prefilter" not in x} == {x: v for x, v in sb[k].items() if "prefilter" not in x}, k
-        else:
-            assert sa[k] == sb[k], k
+    vc.compare_cli_stats(sa, sb)
 
 
 if __name__ == "__main__":

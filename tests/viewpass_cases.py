@@ -1,14 +1,20 @@
-"""What test_gpu_qcut.py and test_gpu_adapter.py share: the two view passes in front of the verdict kernel (csrc/aqc_viewpass.hpp) are
-tested the same way — byte strings packed into a batch, a run with the option on against a run of the same build on the model's
-pre-cut records, the CLI on files against the CLI on pre-cut files.  Not a test module."""
+"""What test_gpu_qcut.py, test_gpu_adapter.py and test_gpu_polytail.py share: the view passes in front of the verdict kernel
+(csrc/aqc_viewpass.hpp) are tested the same way — byte strings packed into a batch, a run with the options on against a run of the
+same build on the model's pre-cut records, the records a pass leaves under 5 bases, the CLI on files against the CLI on pre-cut
+files.  Not a test module."""
 import bz2
 import gzip
+import json
 import os
 import random
+import subprocess
+import sys
 
 import numpy as np
 
+import adapter_rule
 import cut_rule
+import poly_rule
 import test_host_golden as thg
 from afterqc_amd import after, capi, preprocesser, synth
 
@@ -56,6 +62,29 @@ def bases(rng, n):
     return bytes(rng.choice(b"ACGT") for _ in range(n))
 
 
+def views(c0, c1):
+    return list(zip(c0.tolist(), c1.tolist()))
+
+
+def se(pairs, paired):
+    return [p if paired else (p[0], p[1], None, None) for p in pairs]
+
+
+def model_of(modes=None, trim=(0, 0), a1=b"", a2=b"", K=4, lens=None):
+    """the models of the passes, each around that of the pass in front of it: the cut's (the fixed trim is its), the adapter's and —
+    lens given — the poly-tail pass's"""
+    cut = cut_rule.CutConfig(*(modes or (0, 0, 0)), window=4, mean_quality=20, trim_front=trim[0], trim_tail=trim[1])
+    adapter = adapter_rule.AdapterConfig(a1, a2, K, cut)
+    return adapter if lens is None else poly_rule.PolyConfig(lens, adapter)
+
+
+def set_passes(eng, cut=None, adapter=None, poly=None):
+    """the three passes as given; None: off"""
+    eng.set_quality_cut(cut)
+    eng.set_adapter_trim(adapter)
+    eng.set_poly_trim(poly)
+
+
 # ---- a run with the options on against a run on the pre-cut records
 def base_config(paired, trim=(0, 0)):
     cfg = capi.Config()
@@ -98,20 +127,24 @@ def tailed_pairs(n, L, seed, short=()):
     return out
 
 
-def run_pairs(eng, pairs, paired, cfg, cut, adapter=None, slot=0, accum_limit=capi.UINT64_MAX):
-    """one upload + run with the quality cut and the adapters as given (None: off) -> what the comparison looks at"""
+def run_pairs(eng, pairs, paired, cfg, cut, adapter=None, poly=None, slot=0, accum_limit=capi.UINT64_MAX):
+    """one upload + run with the quality cut, the adapters and the poly-tail pass as given (None: off) -> what the comparison looks
+    at.  The cut and the adapters stay as given, the poly-tail pass is off again when this returns."""
     batch = pack([p[0] for p in pairs], [p[1] for p in pairs], [p[2] for p in pairs] if paired else None, [p[3] for p in pairs] if paired else None)
     eng.set_config(cfg)
-    eng.set_quality_cut(cut)
-    eng.set_adapter_trim(adapter)
-    eng.reset_stats()
-    eng.upload(slot, batch)
-    eng.run(slot, accum_limit)
-    res = eng.fetch_results(slot)
-    qv = [eng.fetch_quality_views(slot, m) for m in ((0, 1) if paired else (0,))]
-    ovl, dist = eng.histograms()
-    return dict(res=res, qv=qv, counters=eng.counters(), ovl=ovl, dist=dist, words=eng.last_verdict_words(slot), deferred=eng.last_deferred(slot),
-                cut_ms=eng.cut_ms(slot), cut_stats=eng.cut_stats(), adapter_ms=eng.adapter_ms(slot), adapter_stats=eng.adapter_stats())
+    set_passes(eng, cut, adapter, poly)
+    try:
+        eng.reset_stats()
+        eng.upload(slot, batch)
+        eng.run(slot, accum_limit)
+        res = eng.fetch_results(slot)
+        qv = [eng.fetch_quality_views(slot, m) for m in ((0, 1) if paired else (0,))]
+        ovl, dist = eng.histograms()
+        return dict(res=res, qv=qv, counters=eng.counters(), ovl=ovl, dist=dist, words=eng.last_verdict_words(slot), deferred=eng.last_deferred(slot),
+                    cut_ms=eng.cut_ms(slot), cut_stats=eng.cut_stats(), adapter_ms=eng.adapter_ms(slot), adapter_stats=eng.adapter_stats(),
+                    poly_ms=eng.poly_ms(slot), poly_stats=eng.poly_stats())
+    finally:
+        eng.set_poly_trim(None)
 
 
 def view_bytes(pairs, run, paired):
@@ -138,9 +171,78 @@ def compare_runs(pairs, pre, A, B, paired):
     assert np.array_equal(A["ovl"], B["ovl"]) and np.array_equal(A["dist"], B["dist"])
 
 
-# ---- text, and the CLI on files
+# ---- records a pass leaves under 5 bases.  rule: cut_rule, adapter_rule or poly_rule, whose cut_lines(seq, qual, model, mate) is the model
+def check_below_five(pairs, res, rule, model):
+    """every record has a mate under 5 bases: BADTRIM1 with read 2 as it came — neither trimmed nor cut —, else BADTRIM2"""
+    n1 = n2 = 0
+    for p, r in zip(pairs, res):
+        k1, k2 = rule.cut_lines(p[0], p[1], model, 0), rule.cut_lines(p[2], p[3], model, 1)
+        assert len(k1[0]) < 5 or len(k2[0]) < 5
+        a1, l1, a2, l2 = int(r["start1"]), int(r["len1"]), int(r["start2"]), int(r["len2"])
+        assert p[0][a1:a1 + l1] == k1[0]
+        if len(k1[0]) < 5:
+            assert int(r["flag"]) == capi.BADTRIM1
+            assert (a2, l2) == (0, len(p[2]))
+            n1 += 1
+        else:
+            assert int(r["flag"]) == capi.BADTRIM2
+            assert p[2][a2:a2 + l2] == k2[0]
+            n2 += 1
+    assert n1 >= 200 and n2 >= 100
+
+
 def fastq_text(pairs, mate):
     return b"".join(b"@r%d/%d\n%s\n+\n%s\n" % (i, mate + 1, p[2 * mate], p[2 * mate + 1]) for i, p in enumerate(pairs))
+
+
+def frame_text(eng, slot, pairs):
+    """both mates' text framed into the slot -> the records it holds"""
+    t = [fastq_text(pairs, 0), fastq_text(pairs, 1)]
+    pad = lambda b: np.frombuffer(b + b"\0" * 4096, dtype=np.uint8).copy()
+    return int(eng.frame(slot, pad(t[0]), len(t[0]), True, pad(t[1]), len(t[1]), True).n)
+
+
+def bad_streams(eng, pairs):
+    """text in, text out with the passes as the engine has them: both texts framed into slot 1, run, formatted -> the two bad
+    streams; nothing is good"""
+    eng.reset_stats()
+    assert frame_text(eng, 1, pairs) == len(pairs)
+    eng.run(1)
+    sizes = eng.format(1, len(pairs), False)
+    out = []
+    for file in (0, 1):
+        assert sizes[file * 3] == 0
+        nb = sizes[file * 3 + 1]
+        buf = np.zeros(nb + 64, dtype=np.uint8)
+        eng.fetch_text(1, file, 1, buf, buf.size)
+        out.append(buf[:nb].tobytes())
+    return out
+
+
+def badtrim_text(pairs, rule, model):
+    """... and what they hold: every record as @BADTRIM1... / @BADTRIM2..., read 1 as the pass leaves it, read 2 only under BADTRIM2"""
+    want = [[], []]
+    for i, p in enumerate(pairs):
+        k1, k2 = rule.cut_lines(p[0], p[1], model, 0), rule.cut_lines(p[2], p[3], model, 1)
+        flag = b"BADTRIM1" if len(k1[0]) < 5 else b"BADTRIM2"
+        if flag == b"BADTRIM1":
+            k2 = (p[2], p[3])
+        want[0].append(b"@%sr%d/1\n%s\n+\n%s\n" % (flag, i, k1[0], k1[1]))
+        want[1].append(b"@%sr%d/2\n%s\n+\n%s\n" % (flag, i, k2[0], k2[1]))
+    return [b"".join(w) for w in want]
+
+
+# ---- a child process: a test module run as a script, with a role and an environment of its own
+def run_child(script, role, env):
+    """-> the JSON object on the last line the child wrote"""
+    e = dict(os.environ)
+    e.update(env)
+    p = subprocess.run([sys.executable, os.path.abspath(script), role], capture_output=True, text=True, timeout=300, env=e, cwd=os.path.dirname(os.path.abspath(__file__)))
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    return json.loads(p.stdout.strip().splitlines()[-1])
+
+
+# ---- the CLI on files
 
 
 def write_inputs(work, tag, pairs, paired, gz, index=False):
@@ -188,6 +290,21 @@ def read_outputs(work):
                 # the two runs' inputs are named "raw_*" and "pre_*"
                 out[folder + "/" + f[4:]] = fh.read()
     return out
+
+
+def compare_cli_stats(sa, sb):
+    """the statistics of the run with the options (sa), key by key of the run without them: equal but for what sees the raw reads —
+    total_bases, readlen (the pre-filter sample's read length) and the pre-filter QC sections — and the command line"""
+    for k in sb:
+        if k == "command":
+            continue
+        if k == "afterqc_main_summary":
+            skip = ("total_bases", "readlen")
+            assert {x: v for x, v in sa[k].items() if x not in skip} == {x: v for x, v in sb[k].items() if x not in skip}
+        elif isinstance(sb[k], dict) and any("prefilter" in x for x in sb[k]):
+            assert {x: v for x, v in sa[k].items() if "prefilter" not in x} == {x: v for x, v in sb[k].items() if "prefilter" not in x}, k
+        else:
+            assert sa[k] == sb[k], k
 
 
 def driver_kw(driver):

@@ -24,9 +24,7 @@ import sys
 import viewpass_bench as vb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-A1 = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"
-A2 = b"AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT"
-LOADS = {"se150": (150, False), "pe150": (150, True), "pe300": (300, True)}
+A1, A2, LOADS, batch_of, moved_bytes = vb.A1, vb.A2, vb.LOADS, vb.batch_of, vb.moved_bytes
 
 
 def make_input(n, L, frac=0.3):
@@ -53,17 +51,6 @@ def make_input(n, L, frac=0.3):
     return d
 
 
-def batch_of(d, paired):
-    from afterqc_amd import capi
-    if paired:
-        return capi.Batch.from_matrices(d["seq1"], d["qual1"], d["len1"], d["seq2"], d["qual2"], d["len2"])
-    return capi.Batch.from_matrices(d["seq1"], d["qual1"], d["len1"])
-
-
-def moved_bytes(L, paired, n):
-    return (2 if paired else 1) * (L + 12) * n
-
-
 def kernels(a):
     import numpy as np
     from afterqc_amd import capi
@@ -75,10 +62,7 @@ def kernels(a):
         batch = batch_of(make_input(a.records, L), paired)
         engines = (("plain", plain), ("adapter", adp))
         for tag, eng in engines:
-            eng.set_config(vb.base_config(paired))
-            eng.set_adapter_trim(capi.AdapterConfig(A1, A2 if paired else b"", 4) if tag == "adapter" else None)
-            eng.reset_stats()
-            eng.upload(0, batch)
+            vb.prepare(eng, batch, paired, lambda e: e.set_adapter_trim(capi.AdapterConfig(A1, A2 if paired else b"", 4) if tag == "adapter" else None))
         ms, ams = vb.alternate(engines, a, "adapter", lambda eng: eng.adapter_ms(0))
         vb.verdict_rows(engines, ms, ams, "adapter", load, batch.n, moved_bytes(L, paired, batch.n), 8, 10)
         st = adp.adapter_stats() // (a.warmup + a.reps)
@@ -97,17 +81,9 @@ def early_exit(a):
     print("# adapter_bench exit on %s: %d pairs of 2 x 150, the adapter pass (aqc_adapter_ms), %d warm-up + %d timed aqc_run" % (eng.device_name(), a.records, a.warmup, a.reps), flush=True)
     for frac in (0.0, 0.3, 1.0):
         batch = batch_of(make_input(a.records, L, frac), paired)
-        eng.set_config(vb.base_config(paired))
-        eng.set_adapter_trim(capi.AdapterConfig(A1, A2, 4))
-        eng.reset_stats()
-        eng.upload(0, batch)
-        t = []
-        for k in range(a.warmup + a.reps):
-            eng.run(0)
-            if k >= a.warmup:
-                t.append(eng.adapter_ms(0))
+        vb.prepare(eng, batch, paired, lambda e: e.set_adapter_trim(capi.AdapterConfig(A1, A2, 4)))
+        v, = vb.pass_times([(eng, lambda e: e.adapter_ms(0))], a)
         st = eng.adapter_stats() // (a.warmup + a.reps)
-        v = np.array(t)
         print("  adapter in %3d %% of the reads: adapter_ms median %.4f min %.4f  of_peak %.4f  reads trimmed %d + %d"
               % (round(100 * frac), float(np.median(v)), float(v.min()), vb.of_peak(moved_bytes(L, paired, batch.n), float(np.median(v))), int(st[0]), int(st[2])), flush=True)
     eng.close()
@@ -115,30 +91,14 @@ def early_exit(a):
 
 def step(a):
     from afterqc_amd import capi
-    eng = capi.Engine(0, 2)
-    label = "this adapter" if a.adapter else "this"
-    for L in (150, 300):
-        d = make_input(a.records, L)
-        eng.set_config(vb.base_config())
-        eng.set_adapter_trim(capi.AdapterConfig(A1, A2, 4) if a.adapter else None)
-        eng.reset_stats()
-        v, sizes, _ = vb.device_step(eng, d, L, a)
-        print("%s  adapter_ms %.4f" % (vb.step_line(label, L, v, sizes), eng.adapter_ms(0)), flush=True)
-    eng.close()
+    vb.step(a, lambda L: make_input(a.records, L), "this adapter" if a.adapter else "this",
+            lambda eng: eng.set_adapter_trim(capi.AdapterConfig(A1, A2, 4) if a.adapter else None), "adapter_ms")
 
 
 def once(a):
     from afterqc_amd import capi
     L, paired = LOADS[a.load]
-    eng = capi.Engine(0, 1)
-    eng.set_config(vb.base_config(paired))
-    eng.set_adapter_trim(capi.AdapterConfig(A1, A2 if paired else b"", 4))
-    eng.reset_stats()
-    eng.upload(0, batch_of(make_input(a.records, L), paired))
-    for _ in range(a.reps):
-        eng.run(0)
-    print("%s: %d aqc_run, adapter_ms of the last %.4f" % (a.load, a.reps, eng.adapter_ms(0)), flush=True)
-    eng.close()
+    vb.once(a, make_input(a.records, L), paired, lambda eng: eng.set_adapter_trim(capi.AdapterConfig(A1, A2 if paired else b"", 4)), "adapter_ms")
 
 
 def main():

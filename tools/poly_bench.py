@@ -24,19 +24,17 @@ import sys
 import viewpass_bench as vb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-A1 = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"
-A2 = b"AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT"
-LOADS = {"se150": (150, False), "pe150": (150, True), "pe300": (300, True)}
-KEYS = ("seq1", "qual1", "len1", "seq2", "qual2", "len2")
+A1, A2, LOADS, batch_of, moved_bytes = vb.A1, vb.A2, vb.LOADS, vb.batch_of, vb.moved_bytes
 
 
 def make_input(n, L, frac=0.3, cache=""):
     """synth.make_pairs with a tail of one letter written over the end of `frac` of the reads"""
+    return vb.cached_input(cache, "poly_%d_%d_%d" % (n, L, round(100 * frac)), lambda: generate(n, L, frac))
+
+
+def generate(n, L, frac):
     import numpy as np
     from afterqc_amd import synth
-    stem = os.path.join(cache, "poly_%d_%d_%d" % (n, L, round(100 * frac))) if cache else ""
-    if stem and all(os.path.exists("%s_%s.npy" % (stem, k)) for k in KEYS):
-        return {k: np.load("%s_%s.npy" % (stem, k)) for k in KEYS}
     d = synth.make_pairs(n, L, seed=1003, workers=min(16, os.cpu_count() or 1))
     rng = np.random.Generator(np.random.PCG64(1919 + L))
     j = np.arange(L, dtype=np.int32)[None, :]
@@ -51,22 +49,7 @@ def make_input(n, L, frac=0.3, cache=""):
         new = np.where(j >= L - t, letter, seq)
         new = np.where(j == sub, letters[(np.searchsorted(letters, np.minimum(new, 84)) + 1) % 4], new)
         d[key] = np.where(has[:, None], new, seq).astype(np.uint8)
-    if stem:
-        os.makedirs(cache, exist_ok=True)
-        for k in KEYS:
-            np.save("%s_%s.npy" % (stem, k), d[k])
     return d
-
-
-def batch_of(d, paired):
-    from afterqc_amd import capi
-    if paired:
-        return capi.Batch.from_matrices(d["seq1"], d["qual1"], d["len1"], d["seq2"], d["qual2"], d["len2"])
-    return capi.Batch.from_matrices(d["seq1"], d["qual1"], d["len1"])
-
-
-def moved_bytes(L, paired, n):
-    return (2 if paired else 1) * (L + 12) * n
 
 
 def passes(a):
@@ -87,18 +70,9 @@ def passes(a):
     for load, (L, paired) in LOADS.items():
         batch = batch_of(make_input(a.records, L, cache=a.cache), paired)
         for (tag, setter, _), eng in zip(contexts, engines):
-            eng.set_config(vb.base_config(paired))
-            setter(eng, paired)
-            eng.reset_stats()
-            eng.upload(0, batch)
-        t = {tag: [] for tag, _, _ in contexts}
-        for k in range(a.warmup + a.reps):
-            for (tag, _, ms), eng in zip(contexts, engines):
-                eng.run(0)
-                if k >= a.warmup:
-                    t[tag].append(ms(eng))
-        for (tag, _, _), eng in zip(contexts, engines):
-            v = np.array(t[tag])
+            vb.prepare(eng, batch, paired, lambda e: setter(e, paired))
+        times = vb.pass_times([(eng, ms) for (_, _, ms), eng in zip(contexts, engines)], a)
+        for (tag, _, _), eng, v in zip(contexts, engines, times):
             row = "  %-7s %-6s %-9s %9.4f %9.4f %9.4f %8.4f" % (build, load, tag, float(np.median(v)), float(v.min()), float(v.max()),
                                                               vb.of_peak(moved_bytes(L, paired, batch.n), float(np.median(v))))
             if not a.sisters:
@@ -111,30 +85,14 @@ def passes(a):
 
 def step(a):
     from afterqc_amd import capi
-    eng = capi.Engine(0, 2)
-    label = "this poly_g" if a.poly else "this"
-    for L in (150, 300):
-        d = make_input(a.records, L, cache=a.cache)
-        eng.set_config(vb.base_config())
-        eng.set_poly_trim(capi.PolyConfig(0, 0, 10, 0) if a.poly else None)
-        eng.reset_stats()
-        v, sizes, _ = vb.device_step(eng, d, L, a)
-        print("%s  poly_ms %.4f" % (vb.step_line(label, L, v, sizes), eng.poly_ms(0)), flush=True)
-    eng.close()
+    vb.step(a, lambda L: make_input(a.records, L, cache=a.cache), "this poly_g" if a.poly else "this",
+            lambda eng: eng.set_poly_trim(capi.PolyConfig(0, 0, 10, 0) if a.poly else None), "poly_ms")
 
 
 def once(a):
     from afterqc_amd import capi
     L, paired = LOADS[a.load]
-    eng = capi.Engine(0, 1)
-    eng.set_config(vb.base_config(paired))
-    eng.set_poly_trim(capi.PolyConfig(0, 0, 10, 0))
-    eng.reset_stats()
-    eng.upload(0, batch_of(make_input(a.records, L, cache=a.cache), paired))
-    for _ in range(a.reps):
-        eng.run(0)
-    print("%s: %d aqc_run, poly_ms of the last %.4f" % (a.load, a.reps, eng.poly_ms(0)), flush=True)
-    eng.close()
+    vb.once(a, make_input(a.records, L, cache=a.cache), paired, lambda eng: eng.set_poly_trim(capi.PolyConfig(0, 0, 10, 0)), "poly_ms")
 
 
 def main():

@@ -46,14 +46,10 @@ def kernels(a):
           % (plain.device_name(), a.pairs, a.warmup, a.reps), flush=True)
     print("# %-6s %-6s %5s %10s %9s %7s %9s | %9s %9s %8s" % ("load", "ctx", "words", "verdict_ms", "min_ms", "max/min", "deferred", "cut_ms", "min_ms", "of_peak"))
     for L in (150, 300):
-        d = make_input(a.pairs, L)
-        batch = capi.Batch.from_matrices(d["seq1"], d["qual1"], d["len1"], d["seq2"], d["qual2"], d["len2"])
+        batch = vb.batch_of(make_input(a.pairs, L), True)
         engines = (("plain", plain), ("cut", cut))
         for tag, eng in engines:
-            eng.set_config(vb.base_config(trim=(2, 3)))
-            eng.set_quality_cut(capi.CutConfig(0, 1, 0, 4, 20) if tag == "cut" else None)
-            eng.reset_stats()
-            eng.upload(0, batch)
+            vb.prepare(eng, batch, True, lambda e: e.set_quality_cut(capi.CutConfig(0, 1, 0, 4, 20) if tag == "cut" else None), trim=(2, 3))
         ms, cms = vb.alternate(engines, a, "cut", lambda eng: eng.cut_ms(0))
         vb.verdict_rows(engines, ms, cms, "cut", "pe%d" % L, batch.n, (2 * L + 8) * batch.n, 6, 9)
         st = cut.cut_stats()

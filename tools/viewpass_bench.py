@@ -1,9 +1,43 @@
-"""What tools/qcut_bench.py and tools/adapter_bench.py share: the verdict configuration, the two-context alternating loop around
-aqc_run with the view pass's own time beside the verdict kernel's, the device step on text resident in HBM, and the rate of a
-pass as a share of the HBM peak.  Each tool keeps its input, its option and its output lines."""
+"""What tools/qcut_bench.py, tools/adapter_bench.py and tools/poly_bench.py share: the verdict configuration, the loads and the
+batch of one, generated reads kept as .npy, the two-context alternating loop around aqc_run with the view pass's own time beside
+the verdict kernel's, the passes' own times alone, the device step on text resident in HBM, the single run for a profiler, and the
+rate of a pass as a share of the HBM peak.  Each tool keeps its input, its option and its output lines.  (afterqc_amd is imported
+inside the functions: a tool may first put another checkout in front of this one.)"""
+import os
 import time
 
 PEAK = 8.0e12          # HBM_PEAK_GBS of bench.py
+A1 = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"
+A2 = b"AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT"
+LOADS = {"se150": (150, False), "pe150": (150, True), "pe300": (300, True)}
+KEYS = ("seq1", "qual1", "len1", "seq2", "qual2", "len2")
+
+
+def cached_input(cache, name, generate):
+    """generate() -> the six arrays of synth.make_pairs; with a cache directory they are kept there as <name>_<key>.npy, so that
+    the processes of a job make them once"""
+    import numpy as np
+    stem = os.path.join(cache, name) if cache else ""
+    if stem and all(os.path.exists("%s_%s.npy" % (stem, k)) for k in KEYS):
+        return {k: np.load("%s_%s.npy" % (stem, k)) for k in KEYS}
+    d = generate()
+    if stem:
+        os.makedirs(cache, exist_ok=True)
+        for k in KEYS:
+            np.save("%s_%s.npy" % (stem, k), d[k])
+    return d
+
+
+def batch_of(d, paired):
+    from afterqc_amd import capi
+    if paired:
+        return capi.Batch.from_matrices(d["seq1"], d["qual1"], d["len1"], d["seq2"], d["qual2"], d["len2"])
+    return capi.Batch.from_matrices(d["seq1"], d["qual1"], d["len1"])
+
+
+def moved_bytes(L, paired, n):
+    """what a sequence-line pass must move: per mate the sequence bytes, a length word, an offset word and 4 bytes of view"""
+    return (2 if paired else 1) * (L + 12) * n
 
 
 def base_config(paired=True, trim=(0, 0)):
@@ -18,6 +52,14 @@ def base_config(paired=True, trim=(0, 0)):
     cfg.trim_front = cfg.trim_front2 = trim[0]
     cfg.trim_tail = cfg.trim_tail2 = trim[1]
     return cfg
+
+
+def prepare(eng, batch, paired, set_pass, trim=(0, 0)):
+    """the verdict configuration, the passes as set_pass(engine) leaves them, the counts at zero and the batch in slot 0"""
+    eng.set_config(base_config(paired, trim))
+    set_pass(eng)
+    eng.reset_stats()
+    eng.upload(0, batch)
 
 
 def of_peak(moved, ms):
@@ -54,6 +96,45 @@ def verdict_rows(engines, ms, pms, pass_tag, load, n, moved, tag_width, pass_wid
             c = np.array(pms)
             row += " | %*.4f %9.4f %8.4f" % (pass_width, float(np.median(c)), float(c.min()), of_peak(moved, float(np.median(c))))
         print(row, flush=True)
+
+
+def pass_times(contexts, a):
+    """a.warmup + a.reps aqc_run on slot 0 of each of `contexts` ((engine, pass_ms), ...) in turn -> per context the times
+    pass_ms(engine) gave, warm-up left out"""
+    import numpy as np
+    t = [[] for _ in contexts]
+    for k in range(a.warmup + a.reps):
+        for i, (eng, pass_ms) in enumerate(contexts):
+            eng.run(0)
+            if k >= a.warmup:
+                t[i].append(pass_ms(eng))
+    return [np.array(v) for v in t]
+
+
+def once(a, d, paired, set_pass, ms_name):
+    """a.reps aqc_run on the reads `d` with the pass set_pass(engine) switches on, for a profiler's kernel trace"""
+    from afterqc_amd import capi
+    eng = capi.Engine(0, 1)
+    prepare(eng, batch_of(d, paired), paired, set_pass)
+    for _ in range(a.reps):
+        eng.run(0)
+    print("%s: %d aqc_run, %s of the last %.4f" % (a.load, a.reps, ms_name, getattr(eng, ms_name)(0)), flush=True)
+    eng.close()
+
+
+def step(a, make_input, label, set_pass, ms_name):
+    """the device step on 2 x 150 and 2 x 300 of make_input(L) with the passes as set_pass(engine) leaves them: a step_line each,
+    the pass's own time of the last run behind it"""
+    from afterqc_amd import capi
+    eng = capi.Engine(0, 2)
+    for L in (150, 300):
+        d = make_input(L)
+        eng.set_config(base_config())
+        set_pass(eng)
+        eng.reset_stats()
+        v, sizes, _ = device_step(eng, d, L, a)
+        print("%s  %s %.4f" % (step_line(label, L, v, sizes), ms_name, getattr(eng, ms_name)(0)), flush=True)
+    eng.close()
 
 
 def device_step(eng, d, L, a):
