@@ -18,6 +18,7 @@
 #include "aqc_dev.hpp"
 #include "aqc_bunzip2_dev.hpp"
 #include "aqc_bz2.hpp"
+#include "aqc_keep.hpp"
 
 using namespace aqc;
 
@@ -34,6 +35,7 @@ constexpr uint32_t BZB_CAND_CAP = 65536u;
 class DeviceBunzip2 : public aqcbz::StreamDecoder {
 public:
     DeviceBunzip2(int device, size_t group_blocks) : device_(device), group_blocks_(group_blocks) {}
+    // (runs when a pipe drops a decoder that gave up or that the keeper had no room for — never at exit(): aqc_keep.hpp)
     ~DeviceBunzip2() override {
         (void)hipSetDevice(device_);
         if (stream_) (void)hipStreamSynchronize(stream_);
@@ -192,6 +194,9 @@ private:
     size_t pin_cap_ = 0, meta_cap_ = 0;
 };
 
+// aqc_bunzip2_dev's decoders, lent to its callers for the life of the process (aqc_keep.hpp); keyed by (device, blocks per group)
+Keep<std::pair<int, uint64_t>, aqcbz::StreamDecoder>* const g_dev_keep = new Keep<std::pair<int, uint64_t>, aqcbz::StreamDecoder>;
+
 }  // namespace
 
 namespace aqcbz {
@@ -222,17 +227,7 @@ int aqc_bunzip2_dev(int device, const uint8_t* bz, uint64_t size, uint8_t* out, 
     if (!size) return 0;
     if (!aqcbz::Bz2Api::get().ok) return fail(AQC_ERR_ARG, "device bunzip2: libbz2 could not be loaded (the host takes what the device hands back)");
     // (one decoder per device and group size for the life of the process, as aqc_gunzip_dev keeps its own)
-    static std::mutex cache_mu;
-    static std::vector<std::pair<std::pair<int, uint64_t>, std::unique_ptr<aqcbz::StreamDecoder>>> cache;
-    aqcbz::StreamDecoder* dec = nullptr;
-    {
-        std::lock_guard<std::mutex> g(cache_mu);
-        for (auto& e : cache) if (e.first.first == device && e.first.second == group_blocks) dec = e.second.get();
-        if (!dec) {
-            std::unique_ptr<aqcbz::StreamDecoder> made(aqcbz::make_device_bunzip2(device, (size_t)group_blocks));
-            if (made) { dec = made.get(); cache.emplace_back(std::make_pair(device, group_blocks), std::move(made)); }
-        }
-    }
+    aqcbz::StreamDecoder* dec = g_dev_keep->lend({device, group_blocks}, [&] { return aqcbz::make_device_bunzip2(device, (size_t)group_blocks); });
     if (!dec || dec->gave_up()) return fail(AQC_ERR_HIP, "device bunzip2: cannot set up device %d", device);
     // stream starts, byte aligned, as Bz2Source::produce finds them
     std::vector<size_t> starts;

@@ -20,8 +20,11 @@ __attribute__((visibility("hidden"))) int fail(int code, const char* fmt, ...);
     } while (0)
 
 // A device allocation that grows on demand and is freed with its owner.  The owner sees to it that the buffer's device is
-// current when it dies (aqc_destroy, ~DeviceInflate), and no DevBuf has static storage: a static destructor would call hipFree
-// at exit(), in no fixed order against the HIP runtime's own tear-down.
+// current when it dies (aqc_destroy, ~DeviceInflate), and no DevBuf and no object that owns one — nor one that owns a stream, an
+// event or page-locked memory — has static storage, at namespace scope, in a function or inside a container that has: a static
+// destructor would call hipFree at exit(), in no fixed order against the HIP runtime's own tear-down and against the statics of
+// other units (aqc_host_free's region list).  What is to live as long as the process is held through a plain pointer and never
+// deleted: aqc::Keep (aqc_keep.hpp) for objects found by a key, `new` into a `T* const` for a single one (g_compat_buf).
 struct __attribute__((visibility("hidden"))) DevBuf {
     void* p = nullptr;
     size_t cap = 0;

@@ -24,6 +24,7 @@
 #include "aqc_gunzip_dev.hpp"
 #include "aqc_gunzip_ref.hpp"
 #include "aqc_gz.hpp"
+#include "aqc_keep.hpp"
 #include <zlib.h>
 
 using namespace aqc;
@@ -58,18 +59,12 @@ constexpr size_t GZB_SLACK = 4u << 20;              // compressed bytes uploaded
 
 class DeviceInflate : public aqcgz::SectionOffload {
 public:
-    DeviceInflate(int device, size_t group_bytes) : device_(device), group_bytes_(std::min<size_t>(std::max<size_t>(group_bytes, 1u << 20), 448u << 20)) {
-        if (const char* e = getenv("AQC_GZ_RESIDENT")) resident_ = e[0] != '0';
-        if (const char* e = getenv("AQC_GZ_RATIO")) ratio_ = (uint32_t)std::max(2, std::min(64, atoi(e)));
-        if (const char* e = getenv("AQC_GZ_TOK_RATIO")) tok_ratio_ = (uint32_t)std::max(1, std::min(16, atoi(e)));
-    }
-    // the budgets given, not taken from the defaults and the environment, and kept: a group that comes back short is not decoded
-    // again with more room (aqc_gunzip_probe: what a test sees is then one pass of the kernels with the budgets it named)
-    DeviceInflate(int device, size_t group_bytes, uint32_t ratio_cap, uint32_t tok_ratio, uint32_t overlap_tokens, bool grow) : DeviceInflate(device, group_bytes) {
-        resident_ = true;
-        ratio_ = ratio_cap; tok_ratio_ = tok_ratio; overlap_tokens_ = overlap_tokens;
-        grow_ = grow;
-    }
+    // Everything it is built with comes in `o` (aqcgz::offload_opts: the defaults and the environment; aqc_gunzip_probe: the
+    // budgets a test names, with grow off — a group that comes back short is then not decoded again with more room, and what the
+    // test sees is one pass of the kernels).  Nothing here reads the environment for them: (device, o) is the key it is kept under.
+    DeviceInflate(int device, const aqcgz::OffloadOpts& o)
+        : device_(device), group_bytes_(o.group_bytes), resident_(o.resident), ratio_(o.ratio_cap), tok_ratio_(o.tok_ratio), overlap_tokens_(o.overlap_tokens), grow_(o.grow) {}
+    // (runs when a pipe drops a decoder that gave up or that the keeper had no room for — never at exit(): aqc_keep.hpp)
     ~DeviceInflate() override {
         {
             std::lock_guard<std::mutex> g(mu_);
@@ -658,9 +653,9 @@ private:
 
     int device_;
     size_t group_bytes_;
-    bool resident_ = true;
-    uint32_t ratio_ = 6, tok_ratio_ = 1, overlap_tokens_ = GZB_OVERLAP_TOKENS;
-    bool grow_ = true, grown_ = false;
+    bool resident_;
+    uint32_t ratio_, tok_ratio_, overlap_tokens_;       // (raised once, when a group comes back short: grow_)
+    bool grow_, grown_ = false;
     std::mutex mu_;
     std::condition_variable cv_;
     bool stop_ = false, broken_ = false;
@@ -680,11 +675,19 @@ private:
     uint32_t adv_piece_[32] = {};
 };
 
+static_assert(aqcgz::OffloadOpts{}.overlap_tokens == GZB_OVERLAP_TOKENS, "aqc_gz.hpp states the kernels' default");
+
+// The decoders of the two C entries below, lent to their callers for the life of the process (aqc_keep.hpp), a keeper per entry:
+// a probe's decoder keeps the budgets it was given, aqc_gunzip_dev's grow — and the pipe's own (aqc_pipe.cpp) have one consumer each.
+using GzKey = std::pair<int, aqcgz::OffloadOpts>;
+Keep<GzKey, aqcgz::SectionOffload>* const g_dev_keep = new Keep<GzKey, aqcgz::SectionOffload>;
+Keep<GzKey, aqcgz::SectionOffload>* const g_probe_keep = new Keep<GzKey, aqcgz::SectionOffload>;
+
 }  // namespace
 
 namespace aqcgz {
-SectionOffload* make_device_offload(int device, size_t group_bytes) {
-    std::unique_ptr<DeviceInflate> d(new DeviceInflate(device, group_bytes));
+SectionOffload* make_device_offload(int device, const OffloadOpts& opts) {
+    std::unique_ptr<DeviceInflate> d(new DeviceInflate(device, opts));
     if (!d->start()) { (void)hipGetLastError(); return nullptr; }
     return d.release();
 }
@@ -706,20 +709,10 @@ extern "C" {
 int aqc_gunzip_dev(int device, const uint8_t* gz, uint64_t size, uint8_t* out, uint64_t cap, uint64_t* n_out, uint64_t stats[8], int threads,
                    uint64_t section_bytes, uint64_t group_bytes) {
     if (!gz || !out || !n_out || !stats) return fail(AQC_ERR_ARG, "null argument");
-    // (one decoder per device and group size for the life of the process: its device buffers and page-locked arenas cost more to
-    //  set up than a gigabyte takes to decode)
-    static std::mutex cache_mu;
-    static std::vector<std::pair<std::pair<int, size_t>, std::unique_ptr<aqcgz::SectionOffload>>> cache;
-    const size_t gb = group_bytes ? (size_t)group_bytes : (256u << 20);
-    aqcgz::SectionOffload* off = nullptr;
-    {
-        std::lock_guard<std::mutex> g(cache_mu);
-        for (auto& e : cache) if (e.first.first == device && e.first.second == gb) off = e.second.get();
-        if (!off) {
-            std::unique_ptr<aqcgz::SectionOffload> made(aqcgz::make_device_offload(device, gb));
-            if (made) { off = made.get(); cache.emplace_back(std::make_pair(device, gb), std::move(made)); }
-        }
-    }
+    // (one decoder per device and set of options for the life of the process: its device buffers and page-locked arenas cost more
+    //  to set up than a gigabyte takes to decode)
+    const GzKey key(device, aqcgz::offload_opts(group_bytes ? (size_t)group_bytes : (256u << 20)));
+    aqcgz::SectionOffload* off = g_dev_keep->lend(key, [&] { return aqcgz::make_device_offload(key.first, key.second); });
     if (!off) return fail(AQC_ERR_HIP, "device gunzip: cannot set up device %d", device);
     uint64_t before[8], after[8];
     aqcgz::device_offload_stats(before);
@@ -768,8 +761,6 @@ int aqc_gunzip_probe(int engine, int device, const uint8_t* gz, uint64_t size, i
         if (nominal[k] > stop[k] || (stop[k] >> 3) >= size || (k > 0 && nominal[k] < nominal[k - 1])) return fail(AQC_ERR_ARG, "gunzip probe: section %d is not inside the image, or out of order", k);
     static std::mutex mu;       // (one probe at a time: a decoder takes two groups at most, and the done callbacks below are this call's)
     std::lock_guard<std::mutex> lock(mu);
-    struct Key { int device; uint32_t ratio, tok, overlap; };
-    static std::vector<std::pair<Key, std::unique_ptr<aqcgz::SectionOffload>>> cache;       // (as aqc_gunzip_dev keeps its decoders: buffers are set up once)
     std::unique_ptr<CpuOffload> cpu;
     aqcgz::SectionOffload* off = nullptr;
     if (engine == 0) {
@@ -780,14 +771,10 @@ int aqc_gunzip_probe(int engine, int device, const uint8_t* gz, uint64_t size, i
         cpu->slack = GZB_SLACK; cpu->sec_ratio = 2 * ratio_cap; cpu->total_unbounded = true;
         off = cpu.get();
     } else {
-        for (auto& e : cache)
-            if (e.first.device == device && e.first.ratio == ratio_cap && e.first.tok == tok_ratio && e.first.overlap == overlap_tokens) off = e.second.get();
-        if (!off) {
-            std::unique_ptr<DeviceInflate> made(new DeviceInflate(device, 1u << 20, ratio_cap, tok_ratio, overlap_tokens, false));
-            if (!made->start()) { (void)hipGetLastError(); return fail(AQC_ERR_HIP, "gunzip probe: cannot set up device %d", device); }
-            off = made.get();
-            cache.emplace_back(Key{device, ratio_cap, tok_ratio, overlap_tokens}, std::move(made));
-        }
+        // (as aqc_gunzip_dev keeps its decoders: buffers are set up once.  Resident results, the budgets given, no second attempt)
+        const GzKey key(device, aqcgz::OffloadOpts{1u << 20, true, ratio_cap, tok_ratio, overlap_tokens, false});
+        off = g_probe_keep->lend(key, [&] { return aqcgz::make_device_offload(key.first, key.second); });
+        if (!off) return fail(AQC_ERR_HIP, "gunzip probe: cannot set up device %d", device);
     }
     // (1) one group, (2) its done callbacks
     std::vector<aqcgz::OffloadResult> res((size_t)n);

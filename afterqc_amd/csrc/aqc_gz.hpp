@@ -13,6 +13,8 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
+#include <algorithm>
 #include <functional>
 #include <map>
 #include <memory>
@@ -155,11 +157,40 @@ public:
     // where a resolved section's text is (nullptr: not in device memory)
     virtual const uint8_t* text_ptr(void* token, int* device) { (void)token; (void)device; return nullptr; }
     // bytes [off, off + len) of a resolved section -> dst (queued; fetch_wait() returns once every queued copy has landed)
+    // SINGLE CONSUMER: resolve(), fetch() and fetch_wait() of one decoder are called by one thread at a time — the thread that
+    // reads the stream (ParallelGunzip::read and the pipe's reader behind it).  fetch() and fetch_wait() take no lock: they queue
+    // on and wait for the stream resolve() works on, and two consumers would wait for each other's copies and share its staging
+    // buffers.  A decoder therefore has one user at a time: the pipe's are taken out of their keeper (aqc_keep.hpp), the lent one
+    // of aqc_gunzip_probe is used under that call's mutex, and aqc_gunzip_dev is not to be called from two threads at once with
+    // one device and group size.
     virtual bool fetch(void* token, size_t off, size_t len, uint8_t* dst) { (void)token; (void)off; (void)len; (void)dst; return false; }
     virtual bool fetch_wait() { return false; }
 };
+// What a device decoder is built with, all of it: two decoders with equal options on one device are interchangeable, so
+// (device, options) is the key under which one is kept for its next user (aqc_keep.hpp).
+struct OffloadOpts {
+    size_t group_bytes = 96u << 20;     // compressed bytes per group, 1 MiB ... 448 MiB
+    bool resident = true;               // the symbols stay in HBM and are resolved there (AQC_GZ_RESIDENT=0: page-locked arenas, the host translates)
+    uint32_t ratio_cap = 6;             // symbol space per compressed byte (AQC_GZ_RATIO, 2 ... 64)
+    uint32_t tok_ratio = 1;             // token entries per compressed byte (AQC_GZ_TOK_RATIO, 1 ... 16)
+    uint32_t overlap_tokens = 512;      // token entries a lane has for its successor's share (GZB_OVERLAP_TOKENS)
+    bool grow = true;                   // a group that comes back short is decoded again with more room, and the budgets stay raised
+    bool operator==(const OffloadOpts& o) const {
+        return group_bytes == o.group_bytes && resident == o.resident && ratio_cap == o.ratio_cap && tok_ratio == o.tok_ratio &&
+               overlap_tokens == o.overlap_tokens && grow == o.grow;
+    }
+};
+// the defaults and what the environment says right now, for groups of `group_bytes`; everything clamped to what a decoder takes
+inline OffloadOpts offload_opts(size_t group_bytes) {
+    OffloadOpts o;
+    o.group_bytes = std::min<size_t>(std::max<size_t>(group_bytes, 1u << 20), 448u << 20);
+    if (const char* e = getenv("AQC_GZ_RESIDENT")) o.resident = e[0] != '0';
+    if (const char* e = getenv("AQC_GZ_RATIO")) o.ratio_cap = (uint32_t)std::max(2, std::min(64, atoi(e)));
+    if (const char* e = getenv("AQC_GZ_TOK_RATIO")) o.tok_ratio = (uint32_t)std::max(1, std::min(16, atoi(e)));
+    return o;
+}
 // the device decoder of GPU `device` (aqc_gunzip_offload.hip); nullptr when it cannot be set up
-SectionOffload* make_device_offload(int device, size_t group_bytes);
+SectionOffload* make_device_offload(int device, const OffloadOpts& opts);
 // kernel / copy microseconds of every device decoder of the process so far: scan, decode, chain + gather, H2D, D2H, groups, sections given, sections found
 void device_offload_stats(uint64_t out[8]);
 // resident results (round 6): runs resolved on the devices, their sections, microseconds inside resolve(), bytes of text resolved

@@ -47,6 +47,7 @@
 
 #include "../../include/afterqc_hip.h"
 #include "aqc_gz.hpp"
+#include "aqc_keep.hpp"
 #include "aqc_pool.hpp"
 #include "aqc_pipe_prim.hpp"
 #include "aqc_pipe_source.hpp"
@@ -116,16 +117,31 @@ inline void walk_spans(const aqc_span_event* ev, size_t e0, size_t e1, uint64_t 
     if (end > cursor) own(cursor, end - cursor);
 }
 
-// Device decoders of .gz inputs outlive the pipe that made them: a decoder that has worked holds gigabytes of device
+// Device decoders of .gz and .bz2 inputs outlive the pipe that made them: a decoder that has worked holds gigabytes of device
 // buffers and page-locked stages — freeing them took a one-shot CLI run 34 ms of its pass 2 (two decoders, one after the other),
-// and a folder of inputs (after.py -d: a pipe per file) would set them up again for every file.  A pipe that is destroyed hands
-// its decoders back, the next pipe on that device takes them over warm; they are freed when the process ends.
-struct PooledOffload { int device; size_t group; bool warm; std::unique_ptr<aqcgz::SectionOffload> dec; };
-std::mutex g_offload_mu;
-std::vector<PooledOffload> g_offload_pool;
-// the same for the device decoders of .bz2 inputs (aqc_bunzip2_offload.hip)
-struct PooledBunzip2 { int device; std::unique_ptr<aqcbz::StreamDecoder> dec; };
-std::vector<PooledBunzip2> g_bz2_pool;
+// and a folder of inputs (after.py -d: a pipe per file) would set them up again for every file.  A pipe that is destroyed gives
+// its decoders to a keeper (aqc_keep.hpp: never destroyed, nothing is freed at exit()), the next pipe that asks with an equal key
+// — the device and everything the decoder was built with — takes them over warm.
+struct GzDecoder {
+    std::unique_ptr<aqcgz::SectionOffload> dec;
+    bool warm = false;       // it has run before: its device buffers and page-locked arenas exist
+    bool gave_up() { return dec->gave_up(); }
+};
+using GzKey = std::pair<int, aqcgz::OffloadOpts>;       // device, options
+using Bz2Key = std::pair<int, size_t>;                  // device, blocks per group (aqc_bunzip2_offload.hip)
+aqc::Keep<GzKey, GzDecoder>* const g_gz_keep = new aqc::Keep<GzKey, GzDecoder>;
+aqc::Keep<Bz2Key, aqcbz::StreamDecoder>* const g_bz2_keep = new aqc::Keep<Bz2Key, aqcbz::StreamDecoder>;
+
+// The decoder of one kind that one input file of a pipe holds: taken from its keeper or made with the first input that wants it
+// (Run::take), given back when the pipe is destroyed if it still works.
+template <class Key, class T>
+struct Held {
+    Key key{};
+    std::unique_ptr<T> dec;
+    bool tried = false;
+    // (what comes back from a keeper that is full dies with the pipe)
+    void give_back(aqc::Keep<Key, T>* keep) { if (dec && !dec->gave_up()) dec = keep->give(key, std::move(dec)); }
+};
 
 }  // namespace
 
@@ -136,16 +152,12 @@ struct aqc_pipe {
     int slots = 2;
     int io_threads = 8;
     std::unique_ptr<Pool> pool;
-    // per input file: the device decoder of its gzip stream (created with the first .gz input, kept: its device buffers and
-    // page-locked arenas are as expensive to set up as a whole run)
-    std::unique_ptr<aqcgz::SectionOffload> gz_offload[2];
-    int gz_offload_device[2] = {-1, -1};
-    size_t gz_offload_group[2] = {0, 0};
-    bool gz_offload_tried[2] = {false, false};
-    bool gz_offload_warm[2] = {false, false};       // the decoder of this file slot has run before: its device buffers and page-locked arenas exist
-    // per input file: the device decoder of its bzip2 blocks (created with the first .bz2 input that is given to the device)
-    std::unique_ptr<aqcbz::StreamDecoder> bz2_dec[2];
-    int bz2_dec_device[2] = {-1, -1};
+    // per input file: the device decoder of its gzip stream (with the first .gz input, kept: its device buffers and page-locked
+    // arenas are as expensive to set up as a whole run) and of its bzip2 blocks (with the first .bz2 input given to the device)
+    struct InputDecoders {
+        Held<GzKey, GzDecoder> gz;
+        Held<Bz2Key, aqcbz::StreamDecoder> bz2;
+    } dec[2];
     // The buffers come last: they are the first thing `delete` frees (aqc_pipe_destroy), ahead of the decoders and the pool.
     // per input file: ring of page-locked chunk buffers
     std::vector<HostBuf> in_buf[2];
@@ -479,7 +491,7 @@ struct Run {
         GzSource* stretches = nullptr;
         std::unique_ptr<Source> src = open_source(f, &stretches);
         if (!src) return;
-        if (stretches) read_stretches(f, stretches, aqc_device_index(P->ctx[(size_t)f % P->ctx.size()]));
+        if (stretches) read_stretches(f, stretches, file_device(f));
         else read_source(f, *src);
     }
 
@@ -505,14 +517,24 @@ struct Run {
             struct stat bst;
             aqcbz::StreamDecoder* bz_dec = nullptr;
             if (bz_in && bz_in[0] == '1' && !P->ctx.empty() && stat(io->in_path[f], &bst) == 0 && (size_t)bst.st_size >= bz_min) {
-                take_bunzip2(f);
-                bz_dec = P->bz2_dec[f].get();
+                // (the pipe's own from an earlier run while it works, else a kept or a new one)
+                auto& h = P->dec[f].bz2;
+                if (!h.dec || h.dec->gave_up()) take(f, "bunzip2", g_bz2_keep, h, Bz2Key(file_device(f), 0), [&] { return aqcbz::make_device_bunzip2(h.key.first, h.key.second); });
+                bz_dec = h.dec.get();
             }
             src.reset(new Bz2Source(io->in_path[f], P->pool.get(), bz_dec, bz_min));
         } else if (io->gzip_in[f]) {
             // gzip input: the GPUs take groups of sections off the pool's hands (file f -> the device of context f % n)
             const bool device_in = env_on("AQC_GZ_DEVICE_IN");
-            if (device_in && !P->gz_offload_tried[f] && !P->ctx.empty()) take_offload(f);      // (set up with the first .gz input of this file slot)
+            auto& h = P->dec[f].gz;
+            if (device_in && !h.tried && !P->ctx.empty()) {      // (set up with the first .gz input of this file slot)
+                size_t group = 96u << 20;       // (measured, warm pipe, 0.59 GB inputs: groups of 16 / 32 / 96 MiB = 34 / 38 / 42.5 Mreads/s — profiles/r06_gz_hbm_ab.txt)
+                if (const char* g = getenv("AQC_GZ_GROUP")) group = (size_t)std::max(1ll, atoll(g));
+                take(f, "gunzip", g_gz_keep, h, GzKey(file_device(f), aqcgz::offload_opts(group)), [&]() -> GzDecoder* {
+                    aqcgz::SectionOffload* d = aqcgz::make_device_offload(h.key.first, h.key.second);
+                    return d ? new GzDecoder{std::unique_ptr<aqcgz::SectionOffload>(d)} : nullptr;
+                });
+            }
             // Which files the device is asked for.  A cold decoder — buffers by need (2 - 3 GB for groups of 62 MiB), set up in the
             // background while the pool keeps every section (SectionOffload::prepare), markers + CRC-32 resolved on the device — is
             // started for every input of >= 448 MiB compressed (about 8 M reads).  Measured through the CLI, a fresh process per
@@ -522,12 +544,12 @@ struct Run {
             // decoded a .gz input of this slot with it before: a service, a folder of files, bench.py — for everything the pool
             // would need longer for than a group takes the device (48 MiB).  AQC_GZ_DEVICE_MIN=<bytes> sets the limit for both.
             // (How the limit came down from 4 GiB: DESIGN.md §4, profiles/r05_gz_cold_decoder.txt.)
-            size_t dev_min = P->gz_offload_warm[f] ? (size_t)(48u << 20) : (size_t)(448u << 20);
+            size_t dev_min = h.dec && h.dec->warm ? (size_t)(48u << 20) : (size_t)(448u << 20);
             if (const char* m = getenv("AQC_GZ_DEVICE_MIN")) dev_min = (size_t)std::max(0ll, atoll(m));
             struct stat gst;
-            const bool use_dev = device_in && P->gz_offload[f] && stat(io->in_path[f], &gst) == 0 && (size_t)gst.st_size >= dev_min;
-            if (use_dev) P->gz_offload_warm[f] = true;
-            GzSource* gs = new GzSource(io->in_path[f], P->pool.get(), 0, use_dev ? P->gz_offload[f].get() : nullptr);
+            const bool use_dev = device_in && h.dec && stat(io->in_path[f], &gst) == 0 && (size_t)gst.st_size >= dev_min;
+            if (use_dev) h.dec->warm = true;
+            GzSource* gs = new GzSource(io->in_path[f], P->pool.get(), 0, use_dev ? h.dec->dec.get() : nullptr);
             src.reset(gs);
             // the text of the sections the device decodes stays in HBM and is framed from there — for the chunks that are dealt
             // to the decoder's own device, with plain chunk buffers (the spans mode writes good records FROM them)
@@ -536,43 +558,16 @@ struct Run {
         if (src->failed()) { fail(AQC_ERR_ARG, "cannot open %s", io->in_path[f]); return nullptr; }
         return src;
     }
-    // the device decoder of file slot f: a warm one from the pool of decoders earlier pipes left, or a new one
-    void take_offload(int f) {
-        P->gz_offload_tried[f] = true;
-        size_t group = 96u << 20;       // (measured, warm pipe, 0.59 GB inputs: groups of 16 / 32 / 96 MiB = 34 / 38 / 42.5 Mreads/s — profiles/r06_gz_hbm_ab.txt)
-        if (const char* g = getenv("AQC_GZ_GROUP")) group = (size_t)std::max(1ll, atoll(g));
-        const int dev = aqc_device_index(P->ctx[(size_t)f % P->ctx.size()]);
-        {
-            std::lock_guard<std::mutex> g(g_offload_mu);
-            for (size_t i = 0; i < g_offload_pool.size(); ++i)
-                if (g_offload_pool[i].device == dev && g_offload_pool[i].group == group) {
-                    P->gz_offload[f] = std::move(g_offload_pool[i].dec);
-                    P->gz_offload_warm[f] = g_offload_pool[i].warm;
-                    g_offload_pool.erase(g_offload_pool.begin() + (long)i);
-                    break;
-                }
-        }
-        if (!P->gz_offload[f]) P->gz_offload[f].reset(aqcgz::make_device_offload(dev, group));
-        P->gz_offload_device[f] = dev;
-        P->gz_offload_group[f] = group;
-    }
-
-    // the device bunzip2 decoder of file slot f: the pipe's own from an earlier run, one from the pool earlier pipes left, or a new one
-    void take_bunzip2(int f) {
-        const int dev = aqc_device_index(P->ctx[(size_t)f % P->ctx.size()]);
-        if (P->bz2_dec[f] && (P->bz2_dec_device[f] != dev || P->bz2_dec[f]->gave_up())) P->bz2_dec[f].reset();
-        if (P->bz2_dec[f]) return;
-        {
-            std::lock_guard<std::mutex> g(g_offload_mu);
-            for (size_t i = 0; i < g_bz2_pool.size(); ++i)
-                if (g_bz2_pool[i].device == dev) {
-                    P->bz2_dec[f] = std::move(g_bz2_pool[i].dec);
-                    g_bz2_pool.erase(g_bz2_pool.begin() + (long)i);
-                    break;
-                }
-        }
-        if (!P->bz2_dec[f]) P->bz2_dec[f].reset(aqcbz::make_device_bunzip2(dev, 0));
-        P->bz2_dec_device[f] = dev;
+    int file_device(int f) const { return aqc_device_index(P->ctx[(size_t)f % P->ctx.size()]); }
+    // a decoder for input file f: the one that waits in the keeper under `key`, left there by an earlier pipe, or a new one
+    // (null: it cannot be made — nobody asks again)
+    template <class Key, class T, class Make>
+    void take(int f, const char* kind, aqc::Keep<Key, T>* keep, Held<Key, T>& h, const Key& key, Make&& make) {
+        h.tried = true;
+        h.key = key;
+        h.dec = keep->take(key);
+        if (dbg) fprintf(stderr, "pipe: input %d takes its %s decoder on device %d: %s\n", f, kind, key.first, h.dec ? "warm from the keeper" : "new");
+        if (!h.dec) h.dec.reset(make());
     }
 
     // host memory: zero-copy chunks, counted over a span that grows until it holds K records
@@ -1467,16 +1462,8 @@ int aqc_pipe_create(aqc_ctx** ctxs, int32_t n_ctx, int32_t slots_per_ctx, int32_
 
 void aqc_pipe_destroy(aqc_pipe* p) {
     if (!p) return;
-    {
-        // the device decoders stay for the next pipe (g_offload_pool)
-        std::lock_guard<std::mutex> g(g_offload_mu);
-        for (int f = 0; f < 2; ++f)
-            if (p->gz_offload[f] && !p->gz_offload[f]->gave_up() && g_offload_pool.size() < 16)
-                g_offload_pool.push_back(PooledOffload{p->gz_offload_device[f], p->gz_offload_group[f], p->gz_offload_warm[f], std::move(p->gz_offload[f])});
-        for (int f = 0; f < 2; ++f)
-            if (p->bz2_dec[f] && !p->bz2_dec[f]->gave_up() && g_bz2_pool.size() < 16)
-                g_bz2_pool.push_back(PooledBunzip2{p->bz2_dec_device[f], std::move(p->bz2_dec[f])});
-    }
+    // the device decoders stay for the next pipe
+    for (auto& d : p->dec) { d.gz.give_back(g_gz_keep); d.bz2.give_back(g_bz2_keep); }
     delete p;       // (its buffers free themselves, here: HostBuf)
 }
 
