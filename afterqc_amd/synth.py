@@ -17,6 +17,9 @@ import numpy as np
 BASES = np.frombuffer(b"ACGT", dtype=np.uint8)
 COMP_IDX = np.array([3, 2, 1, 0], dtype=np.uint8)  # A<->T, C<->G on indices into BASES
 # quality alphabet / weights measured on the reference's testdata
+# (bytes 35, 47, 54, 60, 65, 69: none lies in 61..64 or in 48..53, so these batches straddle neither threshold of the correction walk —
+#  q1 >= 30 is byte 63, q2 <= 14 is byte 47 — and a walk whose thresholds have moved a little passes every synth parity test.  The pairs
+#  that sit on both thresholds are those of tests/verdict_walk_cases.py)
 QUAL_CHARS = np.frombuffer(b"#/6<AE", dtype=np.uint8)
 QUAL_WEIGHTS = np.array([0.01, 0.09, 0.02, 0.06, 0.18, 0.64])
 ADAPTER1 = np.frombuffer(b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA", dtype=np.uint8)
