@@ -9,8 +9,8 @@
 //   aqc_fmtcopy.hpp   fmt_plan_kernel, fmt_place_copy_kernel, fmt_plan_listed_kernel, fmt_copy_whole_kernel,
 //                     fmt_copy_whole_list_kernel, fmt_copy_kernel
 //   aqc_census.hpp    poly_census_kernel, census_names_kernel
-// aqc_fast.hpp is here for FastWaveLds<>::PPW, the batch size of a fused placement (it defines a template kernel only, and none
-// of it is instantiated in this unit).
+// aqc_fast_args.hpp is here for FastWaveLds<>::PPW, the batch size of a fused placement (the verdict kernel's host-visible part: no
+// device code).
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -20,7 +20,7 @@
 
 #include "aqc_ctx.hpp"
 #include "aqc_prim.hpp"
-#include "aqc_fast.hpp"
+#include "aqc_fast_args.hpp"
 #include "aqc_textin.hpp"
 #include "aqc_fmt.hpp"
 #include "aqc_fmtcopy.hpp"
